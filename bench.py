@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json metric: frames/s on synthetic 7x256x256 septuplets, STEM training step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +14,9 @@ One "step" = one pass of the hot path over one batch of 16 synthetic septuplets 
 7x I-frame analysis transform g_a (getY) + 6 P-frame optimisation steps of SpatioTemporalPriorModel_Res(256,192)
 (forward, EMLoss, backward, [RCCL all-reduce], fused clip+Adam, aux loss + aux Adam) = the loop body of
 stem/trainSTEM.py:174-226 with all 7 frames used.  value = 7*16*N*K / t  frames/s (weak scaling).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run only sets up, warms up, times the K steps and prints that line; --full adds the
+CPU baseline and the roofline figures of the analysis transform's dominant kernels; --dump-outputs DIR writes what the last
+timed step computed as DIR/<name>.npy.
 """
 import argparse
 import contextlib
@@ -48,7 +50,7 @@ def RUNTIME():
     from spatiotemporalentropymodel_amd import config
     return config.runtime()
 
-PEAK_FP32_MFMA_TFLOPS = 157.3        # /opt/skills/guides/MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak
+PEAK_FP32_MFMA_TFLOPS = 157.3        # MI355X (CDNA4) microarchitecture: v_mfma_f32_32x32x2_f32 dense peak
 BATCH, SIZE, FRAMES = 16, 256, 7
 # the 192-ch 5x5 stride-2 analysis conv g_a.2 (7.550 GF/frame) + the GDN contraction fused
 # into its epilogue (g_a.3, 0.302 GF/frame): one kernel launch per frame batch
@@ -517,12 +519,44 @@ def bench_eval(args):
                                         "(phase stamps of the instrumented library, profiles/r05f_eval_1080p_persistent_phases.log: ctx 0.42 + h1 0.83 + h2 0.74 + gp 0.62 us); "
                                         "the rest of a position is hand-overs between the products (4.9 us) and the host's symbol decoding + mailbox round trip (6.5 us)",
                      "traffic": None}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         k = next(i for i, f in enumerate(last) if f["type"] == "P")
         pf = last[k]
         enc = {"strings": pf["strings"], "shape": pf["shape"]}
         res["cpu_baseline"] = _cpu_baseline_eval(stem, enc, last[k - 1]["y_conditioned"], pf["y_conditioned"])
     _emit(res)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_LOSSES = ("y_bpp_loss", "z_bpp_loss", "loss")
+
+
+def dump_outputs(out_dir, steps, out, opt, aux_opt, max_params=1 << 21):
+    """--dump-outputs: what the timed path computed in its last step, as <out_dir>/<name>.npy (float64 for the losses, float32 for
+    the tensors).  steps = [(losses [3] in DUMP_LOSSES order, aux_loss, grad_norm)] of the step's P-frame steps, in order: one
+    entry per P-frame step in y_bpp_loss / z_bpp_loss / loss / aux_loss / grad_norm.npy; out = the last P-frame step's outputs.
+    The main parameters after the step are written whole up to `max_params` elements, beyond that as a fixed, seeded sample
+    (params_index.npy holds its flat indices as float64)."""
+    losses = np.stack([l.cpu().numpy() for l, _, _ in steps])
+    arrays = {k: losses[:, i].copy() for i, k in enumerate(DUMP_LOSSES)}
+    arrays["aux_loss"] = np.array([float(a) for _, a, _ in steps], np.float64)
+    arrays["grad_norm"] = np.array([float(g) for _, _, g in steps], np.float64)
+    host = lambda t: t.detach().float().cpu().numpy()          # noqa: E731
+    arrays["y_hat"] = host(out["y_hat"])
+    arrays["likelihoods_y"] = host(out["likelihoods"]["y"])
+    arrays["likelihoods_z"] = host(out["likelihoods"]["z"])
+    params = host(opt.flat.data).reshape(-1)
+    if params.size > max_params:
+        idx = np.sort(np.random.default_rng(1234).choice(params.size, max_params, replace=False))
+        arrays["params_index"] = idx.astype(np.float64)
+        params = params[idx]
+    arrays["params"] = params
+    arrays["aux_params"] = host(aux_opt.flat.data).reshape(-1)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET_BYTES}-byte budget"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def _emit(res):
@@ -610,7 +644,14 @@ def main():
     ap.add_argument("--roi-batch", type=int, default=16)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default 10; 2 for --config roi)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps (default 3; 6 for --config roi: the first process that runs the variable-rate models on a box needs about that many iterations before an iteration takes what it takes in every later process -- 1.40 s after two, 0.95-1.0 s after six)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the CPU baseline and, "
+                    "for --config stem, the HIP-event probes of the analysis transform's dominant kernels (roofline, roofline_first_layer), "
+                    "including a repeat of their launches alone on the chip after the timed steps.  Off by default: a plain run sets up, "
+                    "warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="--config stem: after the timed steps, write what the last "
+                    "timed step computed (every P-frame step's losses, aux loss and gradient norm; the last one's y_hat and likelihoods; the parameters "
+                    "after the step) as DIR/<name>.npy (float32 / float64); the inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--latents", default="prefetch", choices=["first", "prefetch"], help="prefetch (default): getY of frame t + 1 runs on a second "
                     "stream while P-frame step t runs (trainer.LatentPrefetcher); first: getY of all 7 frames before the P-frame steps")
     ap.add_argument("--latents-ahead", type=int, default=1)
@@ -640,6 +681,8 @@ def main():
         PINNED_CPUS = pin_rank_to_gpu_cores(int(os.environ.get("LOCAL_RANK", "0")), int(os.environ.get("LOCAL_WORLD_SIZE", os.environ["WORLD_SIZE"])))
     if args.rendezvous_only:
         return rendezvous_only(args)
+    if args.dump_outputs is not None and args.config != "stem":
+        ap.error("--dump-outputs: --config stem only")
     if args.config == "roi":
         return bench_roi(args)
     if args.config == "eval":
@@ -689,8 +732,9 @@ def main():
 
     # HIP-event probe around the dominant kernel (g_a.2 + fused GDN, the 192-ch 5x5 stride-2 analysis conv) on the
     # stream it is launched on (= torch's current stream, which is what the C ABI receives)
+    # (--full only: a plain run times the steps without them)
     probe, probe0 = [], []
-    if os.environ.get("STEM_BENCH_NOPROBE", "0") != "1":
+    if args.full and os.environ.get("STEM_BENCH_NOPROBE", "0") != "1":
         imodel.g_a.probe = {2: probe, 0: probe0}
     f16_chain = RUNTIME().analysis_f16x3
 
@@ -713,7 +757,17 @@ def main():
         graphed = GraphedPFrameStep(stem, crit, opt, aux_opt, (SIZE, SIZE))
         fused_step = None
 
+    # --dump-outputs: what the P-frame steps of the LAST timed step return -- a copy of each one's losses, aux loss and gradient norm
+    # (the launch tape and the graph write them into the same buffers at every P-frame step; a LazyScalar's tensor() orders the copy
+    # after the auxiliary stream's work) and the outputs of the last one
+    dump = {"on": False, "steps": [], "out": None}
+
     def _mark(t, out, oc, aux, gn):
+        if dump["on"]:
+            losses = torch.stack([oc[k].detach().reshape(()) for k in DUMP_LOSSES]).to(torch.float64)
+            scalars = [v.detach() if torch.is_tensor(v) else v.tensor() for v in (aux, gn)]
+            dump["steps"].append((losses, *(v.reshape(()).to(torch.float64, copy=True) for v in scalars)))
+            dump["out"] = out
         if TIMELINE is not None:
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()
@@ -748,8 +802,13 @@ def main():
     TIMELINE = [] if os.environ.get("STEM_BENCH_TIMELINE") else None
 
     with compute:
-        for _ in range(args.warmup):
+        for i in range(args.warmup):
+            # --dump-outputs: the last warm-up step makes the same copies as the last timed step, so that the first use of their
+            # kernels (loaded on first use) falls outside the timed region
+            dump["on"] = args.dump_outputs is not None and i == args.warmup - 1
             one_step()
+        dump["on"] = False
+        dump["steps"].clear()
         probe.clear()
         probe0.clear()
         # device idle BEFORE the barrier too: the gradient exchanges of the last warm-up step run on libstem_dp's own communicator,
@@ -762,7 +821,8 @@ def main():
             TIMELINE.clear()
             tl0 = torch.cuda.Event(enable_timing=True)
             tl0.record()
-        for _ in range(args.steps):
+        for i in range(args.steps):
+            dump["on"] = args.dump_outputs is not None and i == args.steps - 1
             last = one_step()
         torch.cuda.synchronize()
         if TIMELINE is not None and rank == 0:
@@ -772,23 +832,24 @@ def main():
         D.barrier()
         dt = D.max_over_ranks(time.perf_counter() - t0, dev)
 
-    # launch durations inside the timed region: with --latents prefetch these launches share the chip with the P-frame step running
-    # on the compute stream, so they measure the schedule, not the kernel
-    kern_ms_overlap = float(np.mean([a.elapsed_time(b) for a, b in probe])) if probe else float("nan")
-    kern0_ms_overlap = float(np.mean([a.elapsed_time(b) for a, b in probe0])) if probe0 else float("nan")
-    n_overlap = len(probe)
     loss = float(last["loss"].detach())
-    # the kernels' own rate: the same launches (same frames, same weights) with the chip to themselves, timed by the same HIP events on
-    # the launching stream, right after the timed region (prefetch: 3 x 7 launches; latents first: the timed region's launches already are)
-    if prefetch is not None:
-        probe.clear()
-        probe0.clear()
-        with torch.no_grad():
-            for _ in range(3):
-                for f in frames:
-                    imodel.getY(f)
-        torch.cuda.synchronize()
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in probe])) if probe else float("nan")
+    if args.full:
+        # launch durations inside the timed region: with --latents prefetch these launches share the chip with the P-frame step running
+        # on the compute stream, so they measure the schedule, not the kernel
+        kern_ms_overlap = float(np.mean([a.elapsed_time(b) for a, b in probe])) if probe else float("nan")
+        kern0_ms_overlap = float(np.mean([a.elapsed_time(b) for a, b in probe0])) if probe0 else float("nan")
+        n_overlap = len(probe)
+        # the kernels' own rate: the same launches (same frames, same weights) with the chip to themselves, timed by the same HIP events on
+        # the launching stream, right after the timed region (prefetch: 3 x 7 launches; latents first: the timed region's launches already are)
+        if prefetch is not None:
+            probe.clear()
+            probe0.clear()
+            with torch.no_grad():
+                for _ in range(3):
+                    for f in frames:
+                        imodel.getY(f)
+            torch.cuda.synchronize()
+        kern_ms = float(np.mean([a.elapsed_time(b) for a, b in probe])) if probe else float("nan")
     # ---- what a data-parallel run says about ITSELF (every rank takes part; outside the timed region) -------------------------------
     # rccl_nranks: the rank count the communicator that carried the gradients reports (ncclCommCount of libstem_dp's own
     # communicator; the torch group's size on the other routes) -- n_gpus alone is only WORLD_SIZE read back from the environment;
@@ -819,69 +880,75 @@ def main():
                                                         "frames of every rank's seed, closed-form noise sliced per rank"}
     if rank != 0:
         return
-    kern0_ms = float(np.mean([a.elapsed_time(b) for a, b in probe0])) if probe0 else float("nan")
-    flop = GA2_FLOP_PER_FRAME * BATCH
-    tfile = os.path.join(REPO, "profiles", "hbm_traffic.json")
-    tj = json.load(open(tfile)) if os.path.exists(tfile) else {}
-    # g_a.0 + GDN g_a.1 (csrc/c4gdn_f16x3.hip since round 3; igemm.hip's fp32-MFMA kernel with STEM_C4GDN_F16X3=0), measured the same
-    # way; the probe brackets the NCHW -> NHWC4 layout kernel (~20 us) and the convolution kernel
-    flop0 = GA0_FLOP_PER_FRAME * BATCH
-    c4_f16 = RUNTIME().first_layer_f16x3 and f16_chain
-    exec0 = F16_PRODUCTS * (2 * 192 * 80 * 128 * 128 + 2 * 192 * 192 * 128 * 128) * BATCH       # conv K: 75 real products in 80 slots (128 until round 5), GDN K = 192; x3 products
-    peak0 = PEAK_F16_MFMA_TFLOPS if c4_f16 else PEAK_FP32_MFMA_TFLOPS
-    work0 = exec0 if c4_f16 else flop0
-    first_line = {"bound": "mfma",
-                  "kernel": ("c4gdn_f16x3_kernel<6> = g_a.0 conv (3->192, 5x5 s2, 256^2->128^2, B=16) + GDN g_a.1 in one kernel: transposed "
-                             "contractions, squared outputs handed accumulator -> B operand in registers, 3 fp16 MFMAs per fp32 product") if c4_f16 else
-                            "igemm_kernel<128,192,32,96,C4,FUSE> = g_a.0 + fused GDN g_a.1 (v_mfma_f32_32x32x2_f32)",
-                  "achieved": work0 / (kern0_ms_overlap * 1e-3) / 1e12, "peak": peak0, "unit": "TFLOP/s",
-                  "frac": work0 / (kern0_ms_overlap * 1e-3) / 1e12 / peak0, "flop_per_launch": work0,
-                  "avg_launch_ms": kern0_ms_overlap, "launches_timed": len(probe0) if prefetch is None else n_overlap,
-                  "isolated": {"achieved": work0 / (kern0_ms * 1e-3) / 1e12, "frac": work0 / (kern0_ms * 1e-3) / 1e12 / peak0, "avg_launch_ms": kern0_ms,
-                               "launches_timed": len(probe0)},
-                  "useful_flop_per_launch": flop0, "useful_tflops": flop0 / (kern0_ms_overlap * 1e-3) / 1e12,
-                  "useful_tflops_isolated": flop0 / (kern0_ms * 1e-3) / 1e12, "traffic": tj.get("g_a0_c4gdn_bytes_per_launch")}
-    if f16_chain:
-        # Dominant kernel: g_a.2 + GDN on the fp16 matrix cores.  Every fp32 product is THREE fp16 MFMA products (conv_f16x3.hip), so
-        # the matrix pipe executes 3x the algorithmic flop (convolution and GDN contraction); `achieved` / `frac` are that executed fp16 rate against
-        # the dense fp16 peak (never mixed into an fp32 fraction), taken on the launches INSIDE the timed region (the
-        # headline is the in-region figure); the same launches alone on the chip are under "isolated", the algorithmic
-        # (fp32-equivalent, "useful") rate next to both.
-        executed = F16_PRODUCTS * GA2_FLOP_PER_FRAME * BATCH        # convolution and the fused GDN contraction, both on the fp16 instruction
-        in_ms = kern_ms_overlap if prefetch is not None else kern_ms
-        roof = {"bound": "mfma", "kernel": "conv_f16x3_kernel<128> = g_a.2 conv (192->192, 5x5 s2, 128^2->64^2, B=16) + fused GDN g_a.3: operands "
-                                           "pre-split into 2 scaled fp16 planes, 3 fp16 MFMAs (v_mfma_f32_16x16x32_f16 in this launch) per fp32 product, fp32 accumulate",
-                "achieved": executed / (in_ms * 1e-3) / 1e12, "peak": PEAK_F16_MFMA_TFLOPS, "unit": "TFLOP/s",
-                "frac": executed / (in_ms * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS,
-                "flop_per_launch": executed, "flop_definition": "executed fp16 MFMA flop = 3 x algorithmic flop of the convolution and of the fused GDN contraction",
-                "avg_launch_ms": in_ms, "launches_timed": n_overlap if prefetch is not None else len(probe),
-                # the launches of the timed region run on the latent-prefetch stream, which the schedule confines to a subset of the
-                # CUs (trainer.SCHEDULE_DEFAULTS): the same in-region rate against the peak of THOSE CUs
-                "cu_mask_cus": _masked_cus(),
-                "frac_of_masked_cus": executed / (in_ms * 1e-3) / 1e12 / (PEAK_F16_MFMA_TFLOPS * _masked_cus() / 256.0),
-                "isolated": {"achieved": executed / (kern_ms * 1e-3) / 1e12, "frac": executed / (kern_ms * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS,
-                             "avg_launch_ms": kern_ms, "launches_timed": len(probe)},
-                "useful_flop_per_launch": flop, "useful_tflops": flop / (in_ms * 1e-3) / 1e12, "useful_tflops_isolated": flop / (kern_ms * 1e-3) / 1e12,
-                "useful_isolated_vs_fp32_mfma_peak": flop / (kern_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS,
-                "timing_note": ("achieved / frac / avg_launch_ms: the launches of the timed region, which run on the latent-prefetch stream "
-                                "(confined to the CUs of config.stream_cu_masks; the isolated launches below run on the unmasked compute stream) next to "
-                                "a P-frame step (HIP events on the launching stream); isolated: the same launches (same frames, weights) repeated 3 x 7 "
-                                "times right after the timed region with the chip to themselves") if prefetch is not None else
-                               "the launches of the timed region run alone (latents first): in-region = isolated",
-                "clock_note": "counters of this kernel: profiles/r06_pmc_ga2.csv (DESIGN.md 7); the guide's sustained 16-bit MFMA rate on "
-                              "random data is ~1250 TFLOP/s (power-limited clock)",
-                "traffic": tj.get("g_a2_f16x3_bytes_per_launch"),
-                "traffic_source": ("profiles/hbm_traffic.json (tools/update_hbm_traffic.py): %s, measured in %s from %s -- separate rocprofv3 --pmc passes "
-                                   "(FETCH_SIZE x2 + WRITE_SIZE, tools/debug/prof_tcc.sh over tools/debug/f16x3_prof.py planes); NOT re-measured in this run"
-                                   % (tj.get("g_a2_f16x3", {}).get("kernel", "?").split(" = ")[0], tj.get("g_a2_f16x3", {}).get("round", "round 3"),
-                                      tj.get("g_a2_f16x3", {}).get("source", "the round's profile run")))}
-    else:
-        achieved = flop / (kern_ms * 1e-3) / 1e12
-        roof = {"bound": "mfma", "kernel": "igemm_kernel<128,192,32,96,FUSE> = g_a.2 conv (192->192, 5x5 s2, 128^2->64^2, B=16) + fused GDN g_a.3",
-                "achieved": achieved, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_FP32_MFMA_TFLOPS,
-                "flop_per_launch": flop, "avg_launch_ms": kern_ms, "launches_timed": len(probe), "traffic": tj.get("g_a2_bytes_per_launch"),
-                "traffic_source": "profiles/hbm_traffic.json: HBM bytes per launch from separate rocprofv3 --pmc passes (FETCH_SIZE x2 + "
-                                  "WRITE_SIZE, tools/kernel_bench.py --only g_a.2+gdn), NOT re-measured in this run"}
+    if args.dump_outputs is not None:
+        septuplets.finish()
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, dump["steps"], dump["out"], opt, aux_opt)
+    roof = first_line = None
+    if args.full:
+        kern0_ms = float(np.mean([a.elapsed_time(b) for a, b in probe0])) if probe0 else float("nan")
+        flop = GA2_FLOP_PER_FRAME * BATCH
+        tfile = os.path.join(REPO, "profiles", "hbm_traffic.json")
+        tj = json.load(open(tfile)) if os.path.exists(tfile) else {}
+        # g_a.0 + GDN g_a.1 (csrc/c4gdn_f16x3.hip since round 3; igemm.hip's fp32-MFMA kernel with STEM_C4GDN_F16X3=0), measured the same
+        # way; the probe brackets the NCHW -> NHWC4 layout kernel (~20 us) and the convolution kernel
+        flop0 = GA0_FLOP_PER_FRAME * BATCH
+        c4_f16 = RUNTIME().first_layer_f16x3 and f16_chain
+        exec0 = F16_PRODUCTS * (2 * 192 * 80 * 128 * 128 + 2 * 192 * 192 * 128 * 128) * BATCH       # conv K: 75 real products in 80 slots (128 until round 5), GDN K = 192; x3 products
+        peak0 = PEAK_F16_MFMA_TFLOPS if c4_f16 else PEAK_FP32_MFMA_TFLOPS
+        work0 = exec0 if c4_f16 else flop0
+        first_line = {"bound": "mfma",
+                      "kernel": ("c4gdn_f16x3_kernel<6> = g_a.0 conv (3->192, 5x5 s2, 256^2->128^2, B=16) + GDN g_a.1 in one kernel: transposed "
+                                 "contractions, squared outputs handed accumulator -> B operand in registers, 3 fp16 MFMAs per fp32 product") if c4_f16 else
+                                "igemm_kernel<128,192,32,96,C4,FUSE> = g_a.0 + fused GDN g_a.1 (v_mfma_f32_32x32x2_f32)",
+                      "achieved": work0 / (kern0_ms_overlap * 1e-3) / 1e12, "peak": peak0, "unit": "TFLOP/s",
+                      "frac": work0 / (kern0_ms_overlap * 1e-3) / 1e12 / peak0, "flop_per_launch": work0,
+                      "avg_launch_ms": kern0_ms_overlap, "launches_timed": len(probe0) if prefetch is None else n_overlap,
+                      "isolated": {"achieved": work0 / (kern0_ms * 1e-3) / 1e12, "frac": work0 / (kern0_ms * 1e-3) / 1e12 / peak0, "avg_launch_ms": kern0_ms,
+                                   "launches_timed": len(probe0)},
+                      "useful_flop_per_launch": flop0, "useful_tflops": flop0 / (kern0_ms_overlap * 1e-3) / 1e12,
+                      "useful_tflops_isolated": flop0 / (kern0_ms * 1e-3) / 1e12, "traffic": tj.get("g_a0_c4gdn_bytes_per_launch")}
+        if f16_chain:
+            # Dominant kernel: g_a.2 + GDN on the fp16 matrix cores.  Every fp32 product is THREE fp16 MFMA products (conv_f16x3.hip), so
+            # the matrix pipe executes 3x the algorithmic flop (convolution and GDN contraction); `achieved` / `frac` are that executed fp16 rate against
+            # the dense fp16 peak (never mixed into an fp32 fraction), taken on the launches INSIDE the timed region (the
+            # headline is the in-region figure); the same launches alone on the chip are under "isolated", the algorithmic
+            # (fp32-equivalent, "useful") rate next to both.
+            executed = F16_PRODUCTS * GA2_FLOP_PER_FRAME * BATCH        # convolution and the fused GDN contraction, both on the fp16 instruction
+            in_ms = kern_ms_overlap if prefetch is not None else kern_ms
+            roof = {"bound": "mfma", "kernel": "conv_f16x3_kernel<128> = g_a.2 conv (192->192, 5x5 s2, 128^2->64^2, B=16) + fused GDN g_a.3: operands "
+                                               "pre-split into 2 scaled fp16 planes, 3 fp16 MFMAs (v_mfma_f32_16x16x32_f16 in this launch) per fp32 product, fp32 accumulate",
+                    "achieved": executed / (in_ms * 1e-3) / 1e12, "peak": PEAK_F16_MFMA_TFLOPS, "unit": "TFLOP/s",
+                    "frac": executed / (in_ms * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS,
+                    "flop_per_launch": executed, "flop_definition": "executed fp16 MFMA flop = 3 x algorithmic flop of the convolution and of the fused GDN contraction",
+                    "avg_launch_ms": in_ms, "launches_timed": n_overlap if prefetch is not None else len(probe),
+                    # the launches of the timed region run on the latent-prefetch stream, which the schedule confines to a subset of the
+                    # CUs (trainer.SCHEDULE_DEFAULTS): the same in-region rate against the peak of THOSE CUs
+                    "cu_mask_cus": _masked_cus(),
+                    "frac_of_masked_cus": executed / (in_ms * 1e-3) / 1e12 / (PEAK_F16_MFMA_TFLOPS * _masked_cus() / 256.0),
+                    "isolated": {"achieved": executed / (kern_ms * 1e-3) / 1e12, "frac": executed / (kern_ms * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS,
+                                 "avg_launch_ms": kern_ms, "launches_timed": len(probe)},
+                    "useful_flop_per_launch": flop, "useful_tflops": flop / (in_ms * 1e-3) / 1e12, "useful_tflops_isolated": flop / (kern_ms * 1e-3) / 1e12,
+                    "useful_isolated_vs_fp32_mfma_peak": flop / (kern_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS,
+                    "timing_note": ("achieved / frac / avg_launch_ms: the launches of the timed region, which run on the latent-prefetch stream "
+                                    "(confined to the CUs of config.stream_cu_masks; the isolated launches below run on the unmasked compute stream) next to "
+                                    "a P-frame step (HIP events on the launching stream); isolated: the same launches (same frames, weights) repeated 3 x 7 "
+                                    "times right after the timed region with the chip to themselves") if prefetch is not None else
+                                   "the launches of the timed region run alone (latents first): in-region = isolated",
+                    "clock_note": "counters of this kernel: profiles/r06_pmc_ga2.csv (DESIGN.md 7); the guide's sustained 16-bit MFMA rate on "
+                                  "random data is ~1250 TFLOP/s (power-limited clock)",
+                    "traffic": tj.get("g_a2_f16x3_bytes_per_launch"),
+                    "traffic_source": ("profiles/hbm_traffic.json (tools/update_hbm_traffic.py): %s, measured in %s from %s -- separate rocprofv3 --pmc passes "
+                                       "(FETCH_SIZE x2 + WRITE_SIZE, tools/debug/prof_tcc.sh over tools/debug/f16x3_prof.py planes); NOT re-measured in this run"
+                                       % (tj.get("g_a2_f16x3", {}).get("kernel", "?").split(" = ")[0], tj.get("g_a2_f16x3", {}).get("round", "round 3"),
+                                          tj.get("g_a2_f16x3", {}).get("source", "the round's profile run")))}
+        else:
+            achieved = flop / (kern_ms * 1e-3) / 1e12
+            roof = {"bound": "mfma", "kernel": "igemm_kernel<128,192,32,96,FUSE> = g_a.2 conv (192->192, 5x5 s2, 128^2->64^2, B=16) + fused GDN g_a.3",
+                    "achieved": achieved, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_FP32_MFMA_TFLOPS,
+                    "flop_per_launch": flop, "avg_launch_ms": kern_ms, "launches_timed": len(probe), "traffic": tj.get("g_a2_bytes_per_launch"),
+                    "traffic_source": "profiles/hbm_traffic.json: HBM bytes per launch from separate rocprofv3 --pmc passes (FETCH_SIZE x2 + "
+                                      "WRITE_SIZE, tools/kernel_bench.py --only g_a.2+gdn), NOT re-measured in this run"}
     res = {
         "metric": "frames/s", "value": FRAMES * BATCH * world * args.steps / dt, "unit": "frames/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -901,13 +968,13 @@ def main():
                    "launch": "hipGraph replay per P-frame step" if use_graph else
                              (("explicit fused schedule (trainer.FusedPFrameStep)" + (" replayed from its launch tape by the native executor (tape.TapedPFrameStep, csrc/tape.hip)"
                                                                                           if args.tape else "")) if fused_step is not None else "generic nn.Module / autograd route")},
-        "roofline": roof,
-        "roofline_first_layer": first_line,
         "useful_tflops_per_gpu": USEFUL_FLOP_PER_STEP / (dt / args.steps) / 1e12,
     }
+    if args.full:
+        res["roofline"], res["roofline_first_layer"] = roof, first_line
     if dp_report is not None:
         res["config"]["data_parallel"] = dp_report
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline()
     _emit(res)
     if dp_report is not None:

@@ -18,10 +18,13 @@ def pytest_configure(config):
 
 
 # ---- 2-rank data-parallel GPU tests ---------------------------------------------------------------------------------
-# The rank processes are started HERE, right after collection and before any test has run, i.e. while this pytest
-# process has not initialised the GPU yet (a GPU-initialised process must not fork+exec children on the GPU pool).
-# They run concurrently with the first tests and write .npz dumps that tests/test_hip_dp2.py waits for and checks.
-DP2 = {"procs": {}, "dir": None}
+# The rank processes are started by tests/dp_launcher.py, itself started HERE, right after collection and before any test has
+# run, i.e. while this pytest process has not initialised the GPU yet (a GPU-initialised process must not fork+exec children).
+# The launcher never touches the GPU; it keeps at most DP2_MAX_GPU_PROCS of its processes on the GPU at a time, so that the
+# suite never holds more than DP2_MAX_GPU_PROCS + 1 GPU processes at once (a shared GPU machine caps that count).  The ranks
+# run concurrently with the tests and write .npz dumps that tests/test_hip_dp2.py waits for and checks.
+DP2 = {"jobs": {}, "dir": None, "launcher": None}
+DP2_MAX_GPU_PROCS = 8
 
 
 def _free_port():
@@ -32,63 +35,96 @@ def _free_port():
 
 
 def pytest_collection_finish(session):
-    cases = sorted({m.args[0] for item in session.items for m in item.iter_markers("dp2") if m.args})
+    order = []                                           # cases in the order the tests ask for them
+    for item in session.items:
+        for m in item.iter_markers("dp2"):
+            if m.args and m.args[0] not in order:
+                order.append(m.args[0])
     want_bench = any(item.get_closest_marker("bench_gpus2") for item in session.items)
-    if (not cases and not want_bench) or session.config.option.collectonly:
+    if (not order and not want_bench) or session.config.option.collectonly:
         return
+    import json
     import subprocess
     import tempfile
-    DP2["dir"] = tempfile.mkdtemp(prefix="stem_dp2_")
+    DP2["dir"] = d = tempfile.mkdtemp(prefix="stem_dp2_")
     env = dict(os.environ, PYTHONPATH=REPO + os.pathsep + os.environ.get("PYTHONPATH", ""), HSA_ENABLE_IPC_MODE_LEGACY="0")
     import torch
     if torch.cuda.device_count() < 2:                    # counting devices does not initialise the GPU
-        cases = [c for c in cases if not c.startswith("rccl2_")]      # two real RCCL ranks need a device each: those tests skip
-    for case in cases:                                   # one pair at a time would serialise; pairs are small, run them all
+        order = [c for c in order if not c.startswith("rccl2_")]      # two real RCCL ranks need a device each: those tests skip
+    jobs = []
+    for case in order:
         port = _free_port()
         world = 1 if case.startswith("rccl1_") else 2    # rccl1_*: ONE rank in a world-size-1 RCCL ("nccl") process group
-        DP2["procs"][case] = [
-            subprocess.Popen([sys.executable, os.path.join(REPO, "tests", "dp_worker.py"), "--case", case, "--rank", str(r),
-                              "--world", str(world), "--port", str(port), "--out", DP2["dir"]], env=env,
-                             stdout=open(os.path.join(DP2["dir"], f"{case}_rank{r}.log"), "w"), stderr=subprocess.STDOUT)
-            for r in range(world)]
+        procs = [{"argv": [sys.executable, os.path.join(REPO, "tests", "dp_worker.py"), "--case", case, "--rank", str(r), "--world", str(world),
+                           "--port", str(port), "--out", d],
+                  "log": os.path.join(d, f"{case}_rank{r}.log"), "err": None, "rc": os.path.join(d, f"{case}_rank{r}.rc")} for r in range(world)]
+        jobs.append({"name": case, "gpu_procs": world, "env": env, "procs": procs})
 
-
-    # `python bench.py --gpus 2` typed bare on the GPU box (the command form the driver uses): started here for the same reason
-    if any(item.get_closest_marker("bench_gpus2") for item in session.items):
+    # `python bench.py --gpus 2` typed bare on a one-GPU machine (the command form the driver uses): started the same way; its parent
+    # starts the two ranks and never touches the GPU.  --full: the test checks the roofline figures of the run too.
+    if want_bench:
         env_b = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
         env_b["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
         env_b["STEM_BENCH_VERIFY"] = "1"
-        DP2["bench2"] = subprocess.Popen([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                                          "--no-cpu-baseline"], env=env_b, stdout=open(os.path.join(DP2["dir"], "bench2.out"), "w"),
-                                         stderr=open(os.path.join(DP2["dir"], "bench2.err"), "w"))
+        jobs.append({"name": "bench2", "gpu_procs": 2, "env": env_b, "procs": [
+            {"argv": [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
+             "log": os.path.join(d, "bench2.out"), "err": os.path.join(d, "bench2.err"), "rc": os.path.join(d, "bench2.rc")}]})
+    for job in jobs:
+        DP2["jobs"][job["name"]] = [p["rc"] for p in job["procs"]]
+    with open(os.path.join(d, "jobs.json"), "w") as f:
+        json.dump(jobs, f)
+    DP2["launcher"] = subprocess.Popen([sys.executable, os.path.join(REPO, "tests", "dp_launcher.py"), "--jobs", os.path.join(d, "jobs.json"),
+                                        "--max-procs", str(DP2_MAX_GPU_PROCS), "--parent", str(os.getpid())], stdout=open(os.path.join(d, "launcher.log"), "w"),
+                                       stderr=subprocess.STDOUT)
 
 
 def pytest_sessionfinish(session, exitstatus):
-    for procs in DP2["procs"].values():
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    b = DP2.get("bench2")
-    if b is not None and b.poll() is None:
-        b.kill()
+    launcher = DP2.get("launcher")
+    if launcher is not None and launcher.poll() is None:
+        launcher.terminate()                             # kills the jobs it started
+        try:
+            launcher.wait(timeout=30)
+        except Exception:
+            launcher.kill()
+
+
+def dp2_wait(name, timeout=900):
+    """exit statuses of the processes of job `name` (a dp2 case or "bench2"), waiting for them; "timeout" for a process that ran
+    longer than `timeout` seconds (it is killed, with its children: the launcher then starts nothing more), the launcher's
+    "not started: <why>" for a job it did not start.  Time spent queued behind other jobs does not count."""
+    import time
+    from dp_launcher import kill_tree
+    rcs = DP2["jobs"].get(name)
+    assert rcs, f"dp2 job {name!r} was not started (collection hook)"
+    out = []
+    for rc in rcs:
+        while not os.path.exists(rc):
+            if os.path.exists(rc + ".pid") and time.time() - os.path.getmtime(rc + ".pid") > timeout:
+                try:
+                    kill_tree(int(open(rc + ".pid").read()))
+                except ValueError:
+                    pass
+                out.append("timeout")
+                break
+            if DP2["launcher"].poll() is not None and not os.path.exists(rc):
+                log = open(os.path.join(DP2["dir"], "launcher.log")).read()[-2000:]
+                pytest.fail(f"dp2 launcher exited with {DP2['launcher'].returncode} before job {name} finished:\n{log}")
+            time.sleep(0.5)
+        else:
+            text = open(rc).read()
+            out.append(int(text) if text.lstrip("-").isdigit() else text)
+    return out
 
 
 @pytest.fixture(scope="session")
 def dp2_results():
     """wait(case) -> [rank0 dump, rank1 dump] (dicts of numpy arrays); fails with the worker logs if a rank died."""
     def wait(case, timeout=900):
-        procs = DP2["procs"].get(case)
-        assert procs, f"dp2 workers for {case!r} were not started (collection hook)"
-        for r, p in enumerate(procs):
-            try:
-                rc = p.wait(timeout=timeout)
-            except Exception:
-                p.kill()
-                rc = "timeout"
+        for r, rc in enumerate(dp2_wait(case, timeout)):
             if rc != 0:
                 log = open(os.path.join(DP2["dir"], f"{case}_rank{r}.log")).read()[-4000:]
                 pytest.fail(f"dp2 worker {case} rank {r} exited with {rc}:\n{log}")
-        return [dict(np.load(os.path.join(DP2["dir"], f"{case}_rank{r}.npz"))) for r in range(len(procs))]
+        return [dict(np.load(os.path.join(DP2["dir"], f"{case}_rank{r}.npz"))) for r in range(len(DP2["jobs"][case]))]
     return wait
 
 

@@ -309,19 +309,14 @@ def test_rccl_two_devices_taped_equals_the_gloo_pair(dp2_results):
 
 @pytest.mark.bench_gpus2
 def test_bench_gpus2_typed_bare_runs_two_ranks_on_one_device():
-    """`python bench.py --gpus 2 --steps 2 --warmup 1` without any launcher (the driver's command form with N = 2): the parent
+    """`python bench.py --gpus 2 --steps 2 --warmup 1 --full` without any launcher (the driver's command form with N = 2): the parent
     starts the two ranks itself before touching the GPU, they share cuda:0 and exchange through gloo (RCCL refuses two ranks on
     one device), and stdout ends with rank 0's ONE JSON line."""
     import json
     import os
-    from conftest import DP2
-    proc = DP2.get("bench2")
-    assert proc is not None, "bench.py --gpus 2 was not started at collection time"
-    try:
-        rc = proc.wait(timeout=900)
-    except Exception:
-        proc.kill()
-        rc = "timeout"
+    from conftest import DP2, dp2_wait
+    assert "bench2" in DP2["jobs"], "bench.py --gpus 2 was not started at collection time"
+    (rc,) = dp2_wait("bench2", timeout=900)
     out = open(os.path.join(DP2["dir"], "bench2.out")).read()
     err = open(os.path.join(DP2["dir"], "bench2.err")).read()
     assert rc == 0, f"bench.py --gpus 2 exited with {rc}:\n{err[-3000:]}"

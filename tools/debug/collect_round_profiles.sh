@@ -2,8 +2,8 @@
 # collect_round_profiles.sh <tag>: everything profiles/ quotes for a round, in one gpurun call -> gpurun_out/<tag>/
 tag=$1; R=$GRAFT_REPO_ROOT; out=$R/gpurun_out/$tag; mkdir -p $out
 cd $R
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
-python3 bench.py --gpus 2 --steps 2 --warmup 1 > $out/bench_gpus2_one_device.json 2> $out/bench_gpus2.err
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --gpus 2 --steps 2 --warmup 1 --full > $out/bench_gpus2_one_device.json 2> $out/bench_gpus2.err
 STEM_DIST_SINGLE=1 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > $out/bench_rccl_world1.json 2> $out/bench_rccl_world1.err
 STEM_DIST_SINGLE=1 bash tools/debug/ab_env.sh "-" "STEM_DP_THREADED=2" "STEM_DP_THREADED=0" > $out/ab_rccl_world1_issue_modes.log 2>&1
 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > $out/bench_no_group.json 2>/dev/null
