@@ -37,9 +37,7 @@ int stem_abi_version(void);
  * of stem_conv2d_f16x3_gen_fwd / stem_conv2d_wgrad_f16x3, 0 = the planner's; "fx3_depth": 0 automatic | 2 | 4 chunks in
  * flight in stem_conv2d_f16x3_fwd; "fx3_gen_tile": 0 automatic | 64 | 128 pixel workgroups of stem_conv2d_f16x3_gen_fwd; "arp_workers": workgroups of the persistent decoder).  Every setting computes the same
  * contraction (summation order aside); process-wide; not for concurrent use with launches.  There is no reference
- * counterpart (torch picks its kernels internally).  Nothing in the library reads the environment to change results:
- * ablated / instrumented variants exist only in builds with -DSTEM_EXPERIMENTS, which
- * stem_built_with_experiments() reports (0 for the shipped library).                                                  */
+ * counterpart (torch picks its kernels internally).  Nothing in the library reads the environment to change results. */
 /* ---- launch tape: the native executor of a static launch schedule (csrc/tape.hip; reference loop body stem/trainSTEM.py:194-218,
  * which the reference walks through the Python interpreter and autograd every step).  A tape holds calls of THIS library's
  * int-returning entry points (function address + integer-class / float arguments; integer arguments may advance by a fixed
@@ -72,7 +70,6 @@ int stem_stream_flag_wait_ge(void *flag, unsigned value, void *stream);
 int stem_stream_flag_write(void *flag, unsigned value, void *stream);
 int stem_tuning_set(const char *name, int value);
 int stem_tuning_get(const char *name);
-int stem_built_with_experiments(void);
 
 /* ---- weight packing ------------------------------------------------------
  * roles (what the packed copy will be multiplied with):                       */
@@ -419,18 +416,6 @@ int stem_ar_decode_batch(const float *w_ctx, int ld_ctx, const float *b_ctx, con
                          int32_t *idx_host, int32_t *sym_host, stem_symbol_decoder_fn decode, void *const *decs,
                          const int32_t *cdfs, int ncdf, int cdf_stride, const int32_t *sizes, const int32_t *offsets, void *stream);
 
-/* stem_ar_decode_batch without a stream synchronisation per position: device and host hand the indexes / symbols over
- * through flags in pinned memory (owned by the library), the launches of position p + 2 are issued while the device works on
- * p + 1, and the images alternate in two groups so that the host decodes one group while the device advances the other.
- * Every wait is bounded (device ~1 s, host 5 s -> error return).  Same arithmetic per image, same symbols. */
-int stem_ar_decode_batch_pipelined(const float *w_ctx, int ld_ctx, const float *b_ctx, const float *w0, int ld0, const float *b0,
-                                   int n0, const float *w1, int ld1, const float *b1, int n1, const float *w2, int ld2,
-                                   const float *b2, float *buf, int G, int H, int W, int M, int pad, const float *tp,
-                                   const float *hp, float *ctx, float *h1, float *h2, float *gp, const float *table, int T,
-                                   float scale_bound, float slope, stem_symbol_decoder_fn decode, void *const *decs,
-                                   const int32_t *cdfs, int ncdf, int cdf_stride, const int32_t *sizes, const int32_t *offsets,
-                                   void *stream);
-
 /* ---- fp32-accurate convolution on the 16-bit matrix cores (csrc/conv_f16x3.hip, wgrad_f16x3.hip, c4gdn_f16x3.hip) --------
  * Replaces the fp32 convolutions of the reference on this path (compressai/models/priors.py:613-621 under no_grad in
  * stem/trainSTEM.py:128,171; spatiotemporalpriors.py:814-838 with torch autograd).  Every fp32 operand a is stored as two fp16
@@ -537,11 +522,6 @@ size_t stem_conv2d_f16x3_gen_workspace_bytes(int B, int H, int W, int C, int N, 
 int stem_conv2d_f16x3_gen_fwd(const void *xp, const float *xq, int xpix, const void *wp, const float *bias, int epi, float slope,
                                const float *z, int ldz, float *y, int ldy, void *yp, float *yq, int B, int H, int W, int C, int N, int R,
                                int S, int stride, int pad, int taps, void *ws, size_t ws_bytes, void *stream);
-/* ... for rows [n0, n0 + N) of a weight image of N_image rows (whole 128-row tiles): a layer's outputs range by range, so that the
- * consumer of one range need not wait for the others (the input gradient of EPM.0 feeds three independent chains) */
-int stem_conv2d_f16x3_gen_fwd_rows(const void *xp, const float *xq, int xpix, const void *wp_image, int N_image, int n0, const float *bias,
-                                    int epi, float slope, const float *z, int ldz, float *y, int ldy, void *yp, float *yq, int B, int H, int W,
-                                    int C, int N, int R, int S, int stride, int pad, int taps, void *ws, size_t ws_bytes, void *stream);
 /* The TRANSPOSED face of a stride-2, R x R (odd), padding R/2 layer whose fine grid is exactly twice the coarse one, on the same
  * kernel as ONE launch over its four sub-pixel phases (each a stride-1 convolution of the coarse grid with the taps of its parity:
  * 3x3 / 3x2 / 2x3 / 2x2 for 5x5 -- no structural zeros):

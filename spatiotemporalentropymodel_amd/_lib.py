@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
-# STEM_HIP_LIBRARY names another build of the same ABI (tools/debug use `make EXPERIMENTS=1` -> libstem_hip_exper.so)
+# STEM_HIP_LIBRARY names another build of the same ABI (`make variant` -> libstem_hip_<tag>.so, tools/debug/ab_lib.sh)
 HIP_SO = os.environ.get("STEM_HIP_LIBRARY") or os.path.join(_PKG, "libstem_hip.so")
 # STEM_RANS_LIBRARY names another build of the host codec (`make sanitize` -> libstem_rans_asan.so, the sanitizer test)
 RANS_SO = os.environ.get("STEM_RANS_LIBRARY") or os.path.join(_PKG, "libstem_rans.so")
@@ -107,7 +107,6 @@ _HIP_SIG = {
     "stem_f16x2_conv_weight_gen_bytes": [ci, ci, ci, ci],
     "stem_f16x2_pack_conv_weight_gen": [vp, vp, ci, ci, ci, ci, ci, ci, vp],
     "stem_conv2d_f16x3_gen_workspace_bytes": [ci, ci, ci, ci, ci, ci, ci, ci, ci, ci],
-    "stem_conv2d_f16x3_gen_fwd_rows": [vp, vp, ci, vp, ci, ci, vp, ci, cf, vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, sz, vp],
     "stem_tconv2d_f16x3_workspace_bytes": [ci, ci, ci, ci, ci, ci],
     "stem_tconv2d_f16x3_fwd": [vp, vp, ci, vp, vp, ci, cf, vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, sz, vp],
     "stem_wgrad_f16x3_strided_splits": [ci, ci, ci, ci, ci, ci, ci, ci, ci],
@@ -131,8 +130,6 @@ _HIP_SIG = {
     "stem_ar_decode_image_persistent_prefer_xcc": [ci],
     "stem_ar_decode_image_persistent": [vp, ci, vp, vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, cf, cf,
                                         vp, vp, vp, ci, ci, vp, vp, vp],
-    "stem_ar_decode_batch_pipelined": [vp, ci, vp, vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, cf, cf,
-                                       vp, vp, vp, ci, ci, vp, vp, vp],
     "stem_ar_decode_batch": [vp, ci, vp, vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, cf, cf,
                              vp, vp, vp, vp, vp, ci, ci, vp, vp, vp],
     "stem_ar_encode_image": [vp, ci, vp, vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, cf, cf,
@@ -148,7 +145,6 @@ _HIP_SIG = {
     "stem_abi_version": [],
     "stem_adam_chunk": [],
     "stem_adam_step_bmax": [vp, vp, vp, vp, sz, vp, cf, cf, cf, cf, cf, cf, ci, ci, vp, vp],
-    "stem_built_with_experiments": [],
     "stem_tape_create": [],
     "stem_tape_destroy": [vp],
     "stem_tape_length": [vp],

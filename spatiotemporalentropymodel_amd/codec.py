@@ -350,14 +350,8 @@ def _decode_latents(model, strings_y, hp, tp):
                       ar.w1.data_ptr(), ar.w1.shape[1], ar.b1.data_ptr(), ar.w1.shape[0], ar.w2.data_ptr(), ar.w2.shape[1], ar.b2.data_ptr(),
                       buf.data_ptr(), G, H, W, M, _P, tp_b, hp_b, *[t.data_ptr() for t in scratch],
                       ar.table.data_ptr(), ar.table.numel(), ar.bound, F.LRELU_SLOPE)
-            if cfg.ar_pipeline:
-                # flags in pinned memory instead of a stream synchronisation per position, two alternating image groups.
-                # Measured equal for one sequence and slower for 8: the dependent dispatch chain, not the
-                # synchronisation call, is what a position costs.  Kept as a checked alternative, off by default.
-                F._chk(lib.stem_ar_decode_batch_pipelined(*common, decode_fn, C.addressof(handles), *tables.args(), F._stream()))
-            else:
-                F._chk(lib.stem_ar_decode_batch(*common, idx_g.data_ptr(), sym_g.data_ptr(), decode_fn, C.addressof(handles),
-                                                *tables.args(), F._stream()))
+            F._chk(lib.stem_ar_decode_batch(*common, idx_g.data_ptr(), sym_g.data_ptr(), decode_fn, C.addressof(handles),
+                                            *tables.args(), F._stream()))
             out[b0:b0 + G].copy_(buf[:, _P:_P + H, _P:_P + W].permute(0, 3, 1, 2))
     for b, s in enumerate(strings[0] if not lockstep else []):
         if b in decoded:

@@ -44,17 +44,7 @@ class StemRuntimeConfig:
     engine_overlap: bool = True          #: weight gradients on a side stream
     engine_split_pack: bool = True       #: input-gradient weight images packed on the side stream
     engine_pack_pair: bool = True        #: both images of a layer from one read of its weights (after an optimiser pass with maxima)
-    engine_pack_first: bool = False      #: of the forward-role images only the opening layers' on the compute stream (measured: +0.07 ms)
     engine_branch: bool = True           #: hyper path on its own stream
-    engine_tpm_first: bool = True        #: temporal-prior chain enqueued ahead of the hyper branch (forward)
-    engine_tpm_first_bwd: bool = True    #: ... in backward (the hyper chain waits for the EPM input gradient through an event)
-    engine_tpm_wgrad_inline: bool = True #: the TPM chain's weight gradients on the compute stream (behind its input gradients)
-    engine_epm_dgrad_by_prior: bool = False #: EPM.0's input gradient range by range, the hyper chain's range first (measured: +0.19 ms)
-    engine_share_in_planes: bool = True  #: he_in's planes double as the TPM chain's input (channel view)
-    engine_ctx_on_side: bool = False     #: the context model's forward on the weight-gradient stream (experiment)
-    engine_ctx_split_on_side: bool = True #: the planes of t_hat (the context model's input) are made on the weight-gradient stream, idle during the forward, instead of between TPM.4 and the context model
-    engine_fuse_gc_backward: bool = True #: GaussianConditional backward inside the fused forward glue kernel
-    engine_bias_multi: bool = True       #: one launch for a module group's bias-gradient second stages
     stream_prio: str = ""                #: "latents=0,side=-1,compute=-1" (trainer.tuned_schedule installs it)
     stream_cumask: str = ""              #: "latents=block:160"
     # ---- data parallel
@@ -65,7 +55,6 @@ class StemRuntimeConfig:
     pin_ranks: bool = True               #: ranks pin themselves to their GPU's NUMA cores
     # ---- decoder loop (all forms are bit-identical)
     ar_persistent: bool = True
-    ar_pipeline: bool = False
     ar_stepwise: bool = False
     ar_force_batch: bool = False
     ar_concurrent: bool = True           #: several images: one persistent decoder per image, up to 8 at once (one XCD, one stream, one host thread each); off: the lockstep batch loop
@@ -79,11 +68,10 @@ _ENV = {
     "engine_wgrad_f16x3": "STEM_ENGINE_WGRAD_F16X3", "engine_records": "STEM_ENGINE_RECORDS", "layers_f16x3": "STEM_LAYERS_F16X3",
     "layers_f16x3_maxpix": "STEM_LAYERS_F16X3_MAXPIX", "layers_wide_minpix": "STEM_LAYERS_WIDE_MINPIX",
     "adam_block_max": "STEM_ADAM_BLOCK_MAX", "trainer_overwrite_grads": "STEM_TRAINER_OVERWRITE_GRADS", "engine_overlap": "STEM_ENGINE_OVERLAP",
-    "engine_split_pack": "STEM_ENGINE_SPLIT_PACK", "engine_pack_first": "STEM_ENGINE_PACK_FIRST", "engine_pack_pair": "STEM_ENGINE_PACK_PAIR", "engine_branch": "STEM_ENGINE_BRANCH", "engine_tpm_first": "STEM_ENGINE_TPM_FIRST", "engine_tpm_first_bwd": "STEM_ENGINE_TPM_FIRST_BWD", "engine_tpm_wgrad_inline": "STEM_ENGINE_TPM_WGRAD_INLINE",
-    "engine_bias_multi": "STEM_ENGINE_BIAS_MULTI", "engine_fuse_gc_backward": "STEM_ENGINE_FUSE_GC_BACKWARD", "engine_ctx_on_side": "STEM_ENGINE_CTX_ON_SIDE", "engine_ctx_split_on_side": "STEM_ENGINE_CTX_SPLIT_ON_SIDE", "engine_share_in_planes": "STEM_ENGINE_SHARE_IN_PLANES", "engine_epm_dgrad_by_prior": "STEM_ENGINE_EPM_DGRAD_BY_PRIOR",
+    "engine_split_pack": "STEM_ENGINE_SPLIT_PACK", "engine_pack_pair": "STEM_ENGINE_PACK_PAIR", "engine_branch": "STEM_ENGINE_BRANCH",
     "stream_prio": "STEM_STREAM_PRIO", "stream_cumask": "STEM_STREAM_CUMASK", "dp_min_bytes": "STEM_DP_MIN_BYTES", "dp_threaded": "STEM_DP_THREADED",
     "dist_backend": "STEM_DIST_BACKEND", "dist_single": "STEM_DIST_SINGLE", "pin_ranks": "STEM_PIN_RANKS",
-    "ar_persistent": "STEM_AR_PERSISTENT", "ar_pipeline": "STEM_AR_PIPELINE", "ar_stepwise": "STEM_AR_STEPWISE",
+    "ar_persistent": "STEM_AR_PERSISTENT", "ar_stepwise": "STEM_AR_STEPWISE",
     "ar_force_batch": "STEM_AR_FORCE_BATCH", "ar_concurrent": "STEM_AR_CONCURRENT", "ar_no_batch": "STEM_AR_NO_BATCH",
 }
 

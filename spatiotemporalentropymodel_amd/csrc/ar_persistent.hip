@@ -50,9 +50,9 @@ struct ArpArgs {
     int nwg;                            // workers
     int want_xcc;                       // -1: the first candidate to arrive picks the XCD; 0..7: this one (several images at once: one XCD each)
     long long *words;                   // device: tagged 8-byte words {value, position + 1}: ctx [2M] | h1 [n0] | h2 [n1] | gp [2M] | idx [M] | pixel ring [2][M]
-    float *dbg;                         // experiments build: [position][2M + n0 + n1 + 2M] copies of ctx | h1 | h2 | gp (null: off)
-    int *dev;                           // device, one 128-byte line per word group: [0] worker tickets, [1] chosen XCC (-1), [96] abort;
-                                        // [32..] the experiments build's timers
+    const void *unused_;                // keeps `dev` 16 bytes behind `words`: with the two adjacent, the kernel's code shifts and a
+                                        // decoded position took ~0.2 us longer (bench.py --config eval, alternating runs)
+    int *dev;                           // device, one 128-byte line per word group: [0] worker tickets, [1] chosen XCC (-1), [96] abort
 };
 
 __device__ inline int xcc_id() { return __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 15; }      // HW_REG_XCC_ID[3:0]
@@ -277,18 +277,6 @@ __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpAr
         if (t * 256 + l4 < n) v = *reinterpret_cast<const f32x4 *>(xv + t * 256 + l4);
         return v;
     };
-#ifdef STEM_EXPERIMENTS
-    long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = wall_clock64();
-    const long long cyc0 = __builtin_readcyclecounter(), wall0 = tlast;
-#define ARP_MARK(i)                                  \
-    do {                                             \
-        const long long tn_ = wall_clock64();        \
-        tacc[i] += tn_ - tlast;                      \
-        tlast = tn_;                                 \
-    } while (0)
-#else
-#define ARP_MARK(i)
-#endif
     // workgroup 0, one thread per channel: the pixel of position pp = symbol + mean, once the host has posted the symbol
     auto commit_pixel = [&](int pp) {
         const int ph = pp / a.W, pw = pp - ph * a.W;
@@ -355,7 +343,6 @@ __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpAr
             f32x4 x[TCL];
 #pragma unroll
             for (int t = 0; t < TCL; ++t) x[t] = xget(t, 2 * M);
-            ARP_MARK(0);
 #pragma unroll
             for (int r = 0; r < RC; ++r) {
                 const int n = g + NWAVES * r;
@@ -367,7 +354,6 @@ __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpAr
                 if (lane == 0 && n < P) put(ctxw + n, pack(acc + bc[r], tag));
             }
         }
-        ARP_MARK(1);
         // ---- h1 = lrelu(b_0 + W_0 . (tp | hp | ctx)): the partials over tp | hp, continued over ctx
         {
             xwait(ctxw, P, tag);
@@ -375,14 +361,6 @@ __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpAr
             f32x4 x[T0C];
 #pragma unroll
             for (int t = 0; t < T0C; ++t) x[t] = xget(t, P);
-            ARP_MARK(2);
-#ifdef STEM_EXPERIMENTS
-            if (a.dbg && p == 0) {           // what this wavefront multiplies at position 0: its ctx columns and its look-ahead partials
-                float *e = a.dbg + (size_t)N * (2 * P + a.n0 + a.n1) + (size_t)g * (256 + 64 * R0);
-                for (int c = 0; c < 4; ++c) e[l4 + c] = x[0][c];
-                for (int r = 0; r < R0; ++r) e[256 + 64 * r + lane] = epart[r];
-            }
-#endif
 #pragma unroll
             for (int r = 0; r < R0; ++r) {
                 const int n = g + NWAVES * r;
@@ -398,7 +376,6 @@ __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpAr
                 }
             }
         }
-        ARP_MARK(3);
         // ---- h2 = lrelu(b_1 + W_1 . h1)
         {
             xwait(h1w, a.n0, tag);
@@ -406,7 +383,6 @@ __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpAr
             f32x4 x[T1];
 #pragma unroll
             for (int t = 0; t < T1; ++t) x[t] = xget(t, a.n0);
-            ARP_MARK(4);
 #pragma unroll
             for (int r = 0; r < R1; ++r) {
                 const int n = g + NWAVES * r;
@@ -422,7 +398,6 @@ __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpAr
                 }
             }
         }
-        ARP_MARK(5);
         // ---- gp = b_2 + W_2 . h2 (scales | means) and the scales' CDF indexes
         {
             xwait(h2w, a.n1, tag);
@@ -430,7 +405,6 @@ __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpAr
             f32x4 x[T2];
 #pragma unroll
             for (int t = 0; t < T2; ++t) x[t] = xget(t, a.n1);
-            ARP_MARK(4);
 #pragma unroll
             for (int r = 0; r < R2; ++r) {
                 const int n = g + NWAVES * r;
@@ -450,7 +424,6 @@ __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpAr
                 }
             }
         }
-        ARP_MARK(6);
         // ---- workgroup 0 forwards the indexes to the host mailbox (written lane by lane from the products they were separate small
         // PCIe writes from 24 CUs: ~20 us per position)
         if (wg == 0) {
@@ -466,40 +439,12 @@ __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpAr
                 __hip_atomic_store(dst + c, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
         }
-        ARP_MARK(7);
-#ifdef STEM_EXPERIMENTS
-        if (a.dbg && wg == 1) {
-            // (after the look-ahead's first barrier below nobody of this workgroup is still multiplying; the other workgroups cannot
-            // start the next position before the host has answered)
-            float *d = a.dbg + (size_t)p * (2 * P + a.n0 + a.n1);
-            for (int c = tid; c < 2 * P + a.n0 + a.n1; c += NT) {
-                long spins = 0;
-                long long v;
-                for (;;) {
-                    v = __hip_atomic_load(ctxw + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((int)(v >> 32) == tag || give_up(spins)) break;
-                }
-                d[c] = __builtin_bit_cast(float, (int)v);
-            }
-        }
-#endif
         // while the host decodes: the known part of the next position
         if (p + 1 < N) lookahead(p + 1);
     }
-#ifdef STEM_EXPERIMENTS
-    if (wg == 0 && tid == 0)
-    {
-        for (int i = 0; i < 8; ++i) reinterpret_cast<long long *>(a.dev + 32)[i] = tacc[i];
-        reinterpret_cast<long long *>(a.dev + 32)[8] = __builtin_readcyclecounter() - cyc0;
-        reinterpret_cast<long long *>(a.dev + 32)[9] = wall_clock64() - wall0;
-    }
-#endif
     if (wg == 0) commit_pixel(N - 1);                         // the last position's symbols
 }
 
-#ifdef STEM_EXPERIMENTS
-float *g_arp_dbg = nullptr;
-#endif
 struct ArpState {
     int *pinned = nullptr, *dev = nullptr;
     long long *words = nullptr;
@@ -595,9 +540,6 @@ STEM_EXPORT int stem_ar_decode_image_persistent(const float *w_ctx, int ld_ctx, 
     a.ld_ctx = ld_ctx; a.ld0 = ld0; a.n0 = n0; a.ld1 = ld1; a.n1 = n1; a.ld2 = ld2;
     a.buf = buf; a.H = H; a.W = W; a.M = M; a.pad = pad; a.tp = tp; a.hp = hp; a.ctx = ctx; a.h1 = h1; a.h2 = h2; a.gp = gp;
     a.table = table; a.T = T; a.bound = scale_bound; a.slope = slope; a.mail = pin; a.dev = g_arp.dev; a.words = g_arp.words;
-#ifdef STEM_EXPERIMENTS
-    a.dbg = g_arp_dbg;
-#endif
     a.want_xcc = g_arp_want_xcc;
     a.nwg = NWG_DEFAULT;             // the row -> wavefront map is fixed: 32 workgroups x 8 wavefronts (the "arp_workers" selector of round 3 is ignored)
     std::call_once(g_arp_attr_once, [] {
@@ -654,17 +596,6 @@ STEM_EXPORT int stem_ar_decode_image_persistent(const float *w_ctx, int ld_ctx, 
         return -2;
     }
     if (rc_out) return rc_out;
-#ifdef STEM_EXPERIMENTS
-    {
-        long long t[10];
-        if (hipMemcpy(t, g_arp.dev + 32, sizeof(t), hipMemcpyDeviceToHost) == hipSuccess) {
-            fprintf(stderr, "[ar persistent] shader clock %.0f MHz (s_memtime cycles per 100 MHz tick x 100)\n", 100.0 * (double)t[8] / (double)t[9]);
-            fprintf(stderr, "[ar persistent] 100 MHz ticks per position (workgroup 0): mail + look-ahead + host + commit %.1f, ctx %.1f + hand-over %.1f, h1 %.1f, h2 %.1f, "
-                            "hand-overs of h1 and h2 %.1f, gp %.1f + mail %.1f\n", (double)t[0] / N, (double)t[1] / N, (double)t[2] / N, (double)t[3] / N,
-                    (double)t[5] / N, (double)t[4] / N, (double)t[6] / N, (double)t[7] / N);
-        }
-    }
-#endif
     int flags[2] = {0, 0};
     if (hipMemcpy(flags + 1, g_arp.dev + 96, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess || flags[1]) {
         stem_set_error("stem_ar_decode_image_persistent: a device-side wait timed out");
@@ -672,8 +603,3 @@ STEM_EXPORT int stem_ar_decode_image_persistent(const float *w_ctx, int ld_ctx, 
     }
     return 0;
 }
-
-#ifdef STEM_EXPERIMENTS
-// tools/debug/arp_probe.py: per-position copies of the four products' outputs
-STEM_EXPORT void stem_exper_arp_debug(float *p) { g_arp_dbg = p; }
-#endif

@@ -58,12 +58,7 @@ struct C4gArgs {
     int ksc;                       // conv k-steps: R * ceil(S / 5)
     int xbytes;
     float beta_bound;
-    int ablate;                    // libstem_hip_exper.so only (WRONG results, timing ablations): bit 1 = the ring's wait + barrier only at every second
-                                   // step (bit 0 was "5 instead of 8 conv k-steps" before the kernel did that itself: profiles/r06_c4gdn_ablation.log)
 };
-#ifdef STEM_EXPERIMENTS
-int g_c4g_ablate = 0;
-#endif
 
 // ---- A-operand stream -------------------------------------------------------------------------------------------------------
 // chunk t < ksc (conv k-step t = filter row t / SPR, column group u = t % SPR, SPR = ceil(S / 5)): fragment (nb, plane) at
@@ -240,17 +235,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void c4gdn_f16x3_kernel(const C4gArgs 
     patch_load(0, pv);
 
     // ---- convolution: ksc chunks of one k-step x NB tiles x 3 products -----------------------------------------------------------
-#ifdef STEM_EXPERIMENTS
-    const int ksc_run = a.ksc;            // (ablation bit 0 of round 6 -- 5 instead of 8 conv k-steps -- is what the kernel does now)
-    int step_no = 0;
-#define C4G_RING_WAIT() do { if (!((a.ablate & 2) && (step_no++ & 1))) ring_wait(); } while (0)
-#else
-    const int ksc_run = a.ksc;
-#define C4G_RING_WAIT() ring_wait()
-#endif
 #pragma unroll 1
-    for (int t = 0; t < ksc_run; ++t) {
-        C4G_RING_WAIT();
+    for (int t = 0; t < a.ksc; ++t) {
+        ring_wait();
         ring_issue(t + 1);
         h16x8 b[2];
         {
@@ -296,7 +283,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void c4gdn_f16x3_kernel(const C4gArgs 
     for (int kb = 0; kb < NB; ++kb) {
 #pragma unroll
         for (int s = 0; s < 2; ++s, ++c) {
-            C4G_RING_WAIT();
+            ring_wait();
             ring_issue(c + 1);
             const unsigned char *buf = smem + (c & 1) * CHUNK + lane * 16;
             h16x8 b[2];
@@ -389,11 +376,6 @@ __global__ __launch_bounds__(256) void c4gdn_amax_kernel(const float *w, long nw
 
 }   // namespace
 
-#ifdef STEM_EXPERIMENTS
-// tools/debug/c4gdn_time.py <mask>: timing ablations of the first-layer kernel (results are WRONG under them)
-STEM_EXPORT void stem_exper_c4gdn_ablate(int mask) { g_c4g_ablate = mask; }
-#endif
-
 // ---- C ABI --------------------------------------------------------------------------------------------------------------------
 STEM_EXPORT int stem_c4gdn_supported(int N, int R, int S)
 {
@@ -447,9 +429,6 @@ STEM_EXPORT int stem_conv2d_c4_gdn_f16x3(const float *x4, const float *xq, const
     a.ksc = conv_ksteps(R, S);
     a.xbytes = (int)xb;
     a.beta_bound = (float)sqrt((double)beta_min + 1.4551915228366852e-11);
-#ifdef STEM_EXPERIMENTS
-    a.ablate = g_c4g_ablate;
-#endif
     const int M = B * OH * OW;
     const dim3 grid(cdiv(M, WG_PIX)), block(NTHREADS);
     hipStream_t st = (hipStream_t)stream;

@@ -74,30 +74,7 @@ struct ImgArgs {
     int nsplit, cps;
     int xpix;
     int tiles_x, tiles_y;
-    unsigned long long *stamps;     // phase stamps of every workgroup (libstem_hip_exper.so only; null otherwise)
-    int ny;                         // N tiles of the launch (cdiv(N, IBN))
-    int ablate;                     // libstem_hip_exper.so only (WRONG results: timing ablations): 1 = every second chunk's barrier left out, 2 = return after the
-                                    // main loop, 3 = one-dimensional launch with the splits of a tile on one XCD and partial tiles without sc1
 };
-
-#ifndef STEM_IMG_ZFLIP
-#define STEM_IMG_ZFLIP 0        // experiments: the K splits dealt to the workgroups in reverse order
-#endif
-#ifndef STEM_IMG_LAZY_LAST
-#define STEM_IMG_LAZY_LAST 0    // 1: the last ARRIVING split keeps its tile in LDS instead of writing and re-reading it (see the split-K hand-over).
-#endif                          // Built, bit-identical, and measured SLOWER in the step (round 6, profiles/r06_ab_img_lazy_last.log): off
-#ifdef STEM_EXPERIMENTS
-unsigned long long *g_img_stamps = nullptr;
-int g_img_ablate = 0;
-__device__ unsigned long long g_img_waits[4];      // sums over wavefronts: cycles waiting for vmcnt, at the barrier, in the loop
-#define IMG_STAMP(i)                                                                                                              \
-    do {                                                                                                                          \
-        if (a.stamps && threadIdx.x == 0)                                                                                         \
-            a.stamps[((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-#else
-#define IMG_STAMP(i) do { } while (0)
-#endif
 
 // block_max on a caller-provided LDS scratch (the kernel keeps ALL its LDS in the one dynamic array: a second __shared__ object
 // beside an LDS-DMA ring makes hipcc drain the ring before every LDS read)
@@ -133,23 +110,11 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // (tile, N tile, K split) of this workgroup: the launch's three grid dimensions
-    int BX = blockIdx.x, BY = blockIdx.y, BZ = blockIdx.z, GX = gridDim.x, GY = gridDim.y, GZ = gridDim.z;
-#ifdef STEM_EXPERIMENTS
-    if (a.ablate == 3) {
-        // ablation (round 6, timing only): a one-dimensional launch in which the splits of one tile run on ONE XCD (workgroup i is
-        // dispatched to XCD i mod 8): linear id L -> XCD L & 7, slot L >> 3 -> tile (slot / nsplit) * 8 + XCD, split slot % nsplit;
-        // the partial tiles are then stored and read WITHOUT sc1 (they stay in that XCD's L2).  Results are not guaranteed.
-        const int L = blockIdx.x, slot = L >> 3, T = (slot / a.nsplit) * 8 + (L & 7);
-        GX = a.B * a.tiles_x * a.tiles_y; GY = a.ny; GZ = a.nsplit;
-        if (T >= GX * GY) return;
-        BX = T % GX; BY = T / GX; BZ = slot % a.nsplit;
-    }
-#endif
-    IMG_STAMP(0);
+    const int BX = blockIdx.x, BY = blockIdx.y, BZ = blockIdx.z, GX = gridDim.x, GY = gridDim.y;
     const int tpi = a.tiles_x * a.tiles_y;
     const int bimg = BX / tpi, trem = BX - bimg * tpi, tyi = trem / a.tiles_x, txi = trem - tyi * a.tiles_x;
     const int y0 = tyi * TS, x0 = txi * TS;
-    const int bn0 = BY * IBN, zsplit = STEM_IMG_ZFLIP ? GZ - 1 - BZ : BZ;
+    const int bn0 = BY * IBN, zsplit = BZ;
     const int nslab = a.C / KC, T = a.ntaps, nchunks = T * nslab;
     const int q_begin = zsplit * a.cps;
     const int q_end = q_begin + a.cps < nchunks ? q_begin + a.cps : nchunks;
@@ -255,7 +220,6 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
         dmaB(c, 0);
         if (c + 1 < q_end) dmaB(c + 1, 1);
     }
-    IMG_STAMP(1);
     // scales of the epilogue, computed while those loads are in flight (conv_f16x3_gen_kernel); the thread's four output
     // columns are the same in every pass of the epilogue (512 threads = 16 rows x 32 column groups): its bias values are loaded here
     const float fac = q_inv(a.xq) * q_inv(a.wq);
@@ -323,17 +287,12 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
     // The DMA, the barrier and the look-ahead reads are unconditional (beyond the last chunk they re-fetch the last chunk into a
     // free slot and read fragments nobody multiplies): the two blocks stay single basic blocks and vmcnt(2) always means
     // "everything but the youngest chunk's DMA".
-    IMG_STAMP(2);
     // The loop exists twice: for wavefronts with live columns and for the dead ones of a half-empty last N tile (staging and
     // barriers only) -- chosen once, so that the live loop body has no branch between its reads and its MFMAs.
     const int c0_ = c, slab0_ = slab, t0_ = t, ts0_ = ts, toff0_ = toff, pend0_ = pend;
     auto run = [&](auto live_tag) {
         constexpr bool LIVE = decltype(live_tag)::value;
         int c = c0_, slab = slab0_, t = t0_, ts = ts0_, toff = toff0_, pend = pend0_;      // loop state private to this instance
-#ifdef STEM_EXPERIMENTS
-        unsigned long long t_vm_ = 0, t_bar_ = 0;
-        const unsigned long long t_loop0_ = a.stamps ? __builtin_amdgcn_s_memtime() : 0ull;
-#endif
         int ab = 0, slot = 0;
         h16x8 fa0[2][NPL], fb0[2][NPL], fa1[2][NPL], fb1[2][NPL];
         int a0 = 0, a1 = 0, b0 = 0;
@@ -388,21 +347,7 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_waitcnt(0xC07F);         // lgkmcnt(0)
             __builtin_amdgcn_sched_barrier(0);
-#ifdef STEM_EXPERIMENTS
-            const unsigned long long ts0_ = a.stamps ? __builtin_amdgcn_s_memtime() : 0ull;
-            asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            const unsigned long long ts1_ = a.stamps ? __builtin_amdgcn_s_memtime() : 0ull;
-            // ablation (round 6): what a barrier every TWO chunks could buy at most -- every second barrier left out (the weight ring
-            // is then read while it is overwritten: results are wrong, the instruction stream and its timing are the loop's)
-            if (!(a.ablate == 1 && (c & 1))) asm volatile("s_barrier" ::: "memory");
-            if (a.stamps) {
-                const unsigned long long ts2_ = __builtin_amdgcn_s_memtime();
-                t_vm_ += ts1_ - ts0_;
-                t_bar_ += ts2_ - ts1_;
-            }
-#else
             asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
-#endif
             if (pend >= 0 && pend - 2 <= (last ? slab : slab - 1)) {
                 storeA((pend - s0) & 1);
                 if (pend + 1 <= s_last) {
@@ -440,20 +385,6 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
             slot = nslot; t = nt; ts = nts; toff = ntoff; slab = nslab; ab = nab;
             a0 = na0; a1 = na1; b0 = nb0;
         }
-#ifdef STEM_EXPERIMENTS
-        if (a.stamps && lane == 0) {        // per wavefront: shader cycles in the loop, waiting for the weight DMA, waiting at the barrier
-            unsigned long long *w = a.stamps + ((size_t)(BZ * GY + BY) * GX + BX) * 8;
-            if (wave == 0) {                  // where the workgroup ran: XCC_ID [63:60], HW_ID (se / sh / cu) [59:44], shader cycles in the loop [43:0]
-                unsigned hw, xcc;
-                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-                w[7] = ((unsigned long long)(xcc & 0xF) << 60) | ((unsigned long long)(hw & 0xFFFF) << 44) | ((__builtin_amdgcn_s_memtime() - t_loop0_) & 0xFFFFFFFFFFFull);
-            }
-            atomicAdd(&g_img_waits[0], t_vm_);
-            atomicAdd(&g_img_waits[1], t_bar_);
-            atomicAdd(&g_img_waits[2], __builtin_amdgcn_s_memtime() - t_loop0_);
-        }
-#endif
     };
     if (dead)
         run(std::false_type{});
@@ -461,10 +392,6 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
         run(std::true_type{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the look-ahead DMA of the last chunks still writes LDS
     __syncthreads();            // every wavefront is done with the operand images: the epilogue tile takes their place
-    IMG_STAMP(3);
-#ifdef STEM_EXPERIMENTS
-    if (a.ablate == 2) return;  // ablation: nothing after the main loop (no partial tiles, ticket, slab read, epilogue): what the tail costs at most
-#endif
 
     // ---- sums of this workgroup -> the epilogue tile Tt (directly, or through the split-K workspace) --------------------------
     // accumulator register r of MFMA tile mi: tile row rho = (r & 3) + 8 (r >> 2) + 4 lh -> pixel (4 wm + 2 mi + (rho >> 4), rotated column)
@@ -493,18 +420,7 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
         // those the ticket overtook the data on the first launch after the workspace was (re)allocated -- the last arriver
         // summed the allocation's zeros for a few pieces (tools/debug/repro_fwd.py: 40 of 40 fresh runs; this form and a
         // plain-store + agent-release form: 0 of 40)
-        //
-        // Round 6 (STEM_IMG_LAZY_LAST): the workgroup that ARRIVES last does not write and re-read its own tile.  The counter holds two
-        // numbers: arrivals (low 16 bits: taken right behind the main loop, before anything is written) and written tiles (high 16
-        // bits: added behind the stores' acknowledgement, as the old ticket was).  The last arriver keeps its tile in LDS, waits
-        // until the nsplit - 1 others -- which arrived earlier, i.e. are already writing -- have all signalled "written", and sums
-        // the tiles IN SPLIT ORDER with its own at its place in that order: the same additions on the same values as before (a
-        // store / load round trip is exact), so results do not depend on who arrived last, nor on this switch.  What it saves is
-        // the 128-KB write-through + its acknowledgement on the one workgroup every tile waits for (17 us of a 107-us TPM.4 launch
-        // lie behind the main loop: profiles/r06_img_tail_ablation.log).  MEASURED (alternating in-step passes, same results bit for
-        // bit): 11.46 / 11.54 / 11.52 ms with it against 11.30 / 11.28 / 11.31 without -- the extra agent-scope atomic + barrier
-        // right behind the loop is paid by EVERY workgroup, and inside the step the splits of a tile arrive closer together than
-        // the 8 us a write takes, so the last arriver waits for the others' writes instead of doing its own.  Default off.
+        // (a last arriver that keeps its own tile in LDS instead was measured slower in the step: DESIGN.md 7)
         constexpr int SC1 = 16;
         const __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc(a.ws, 0, (int)((size_t)a.nsplit * Mtot * Npad * 4), 0x00020000);
         const int sstep = Mtot * Npad * 4;
@@ -513,67 +429,23 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
         for (int k = 0; k < ER; ++k) eoff[k] = em[k] >= 0 ? (em[k] * Npad + bn0 + ec4 * 4) * 4 : OOR;
         float *wsp = a.ws + (size_t)zsplit * Mtot * Npad;
         int *cn = a.cnt + BY * GX + BX;
-#if STEM_IMG_LAZY_LAST
-        if (tid == 0) flag[0] = (__hip_atomic_fetch_add(cn, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 0xFFFF) == a.nsplit - 1;
-        __syncthreads();
-        const bool lazy = flag[0] != 0;
-#else
-        const bool lazy = false;
-#endif
-        if (!lazy) {
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
+        for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = MOF(PIXL(mi, r));
-                    if (m >= 0) {
+            for (int r = 0; r < 16; ++r) {
+                const int m = MOF(PIXL(mi, r));
+                if (m >= 0) {
 #pragma unroll
-                        for (int nj = 0; nj < 2; ++nj)
-                        {
-#ifdef STEM_EXPERIMENTS
-                            if (a.ablate == 3) {
-                                wsp[(size_t)m * Npad + bn0 + wn * 64 + nj * 32 + lr] = acc[mi][nj][r];
-                                continue;
-                            }
-#endif
-                            __hip_atomic_store(&wsp[(size_t)m * Npad + bn0 + wn * 64 + nj * 32 + lr], acc[mi][nj][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
-                    }
+                    for (int nj = 0; nj < 2; ++nj)
+                        __hip_atomic_store(&wsp[(size_t)m * Npad + bn0 + wn * 64 + nj * 32 + lr], acc[mi][nj][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-#if STEM_IMG_LAZY_LAST
-            if (tid == 0) __hip_atomic_fetch_add(cn, 0x10000, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);        // "written"
-            IMG_STAMP(4);
-            return;
-#else
-            if (tid == 0) flag[0] = splitk_last_arriver(cn, a.nsplit);
-            __syncthreads();
-            IMG_STAMP(4);
-            if (!flag[0]) return;
-#endif
-        } else {
-            // own tile -> LDS (the layout of the unsplit path); the others' tiles are complete once "written" has reached nsplit - 1.
-            // They arrived before this workgroup and need nothing from it: the wait cannot deadlock; it is bounded all the same
-            // (~1 s: a launch is over in 100 us) so that a lost workgroup shows up as a wrong result in a test, not as a hung GPU
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int pix = PIXL(mi, r);
-#pragma unroll
-                    for (int nj = 0; nj < 2; ++nj) Tt[pix * ITP + wn * 64 + nj * 32 + lr] = acc[mi][nj][r];
-                }
-            if (tid == 0) {
-                long spins = 0;
-                while ((__hip_atomic_load(cn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 16) != a.nsplit - 1 && ++spins < (1L << 22)) __builtin_amdgcn_s_sleep(8);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                __hip_atomic_store(cn, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            __syncthreads();
-            IMG_STAMP(4);
-        }
-        // the owner sums the slabs in split order (own tile included at its place: one fixed order whoever arrives last), 8 rows x 4
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid == 0) flag[0] = splitk_last_arriver(cn, a.nsplit);
+        __syncthreads();
+        if (!flag[0]) return;
+        // the owner sums the slabs in split order (its own included: one fixed order whoever arrives last), 8 rows x 4
         // splits = 32 sc1 loads in flight per thread: the read is latency-bound (cross-XCD, ~1 us per dependent round)
 #pragma unroll
         for (int k = 0; k < ER; ++k) ev[k] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -585,28 +457,16 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
                 for (int k = 0; k < 8; ++k)
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
-                        const bool other = sp + u < a.nsplit && !(lazy && sp + u == zsplit);
+                        const bool other = sp + u < a.nsplit;
                         const int so = (other ? sp + u : 0) * sstep;
-#ifdef STEM_EXPERIMENTS
-                        if (a.ablate == 3) {
-                            tt[k][u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rws, other ? eoff[kb + k] : OOR, so, 1));      // sc0: past the L1, from this XCD's L2
-                            continue;
-                        }
-#endif
                         tt[k][u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rws, other ? eoff[kb + k] : OOR, so, SC1));
                     }
 #pragma unroll
                 for (int k = 0; k < 8; ++k)
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        if (lazy && sp + u == zsplit)      // this workgroup's own tile, from LDS, at its place in the order
-                            ev[kb + k] += *reinterpret_cast<const f32x4 *>(&Tt[(er0 + 16 * (kb + k)) * ITP + ec4 * 4]);
-                        else
-                            ev[kb + k] += tt[k][u];          // beyond nsplit: zeros (out-of-range loads)
-                    }
+                    for (int u = 0; u < 4; ++u) ev[kb + k] += tt[k][u];          // beyond nsplit: zeros (out-of-range loads)
             }
         }
-        IMG_STAMP(5);
     } else {
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
@@ -681,22 +541,9 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
             }
         }
     }
-    IMG_STAMP(6);
 }
 
 }   // namespace
-
-#ifdef STEM_EXPERIMENTS
-// tools/debug/f16x3_img_phases.py: a device buffer of 8 x uint64 per workgroup receives s_memrealtime (100 MHz) at the phase borders
-STEM_EXPORT void stem_exper_img_stamps(void *p) { g_img_stamps = static_cast<unsigned long long *>(p); }
-STEM_EXPORT void stem_exper_img_ablate(int mode) { g_img_ablate = mode; }
-STEM_EXPORT void stem_exper_img_waits(unsigned long long *out4, int reset)
-{
-    unsigned long long z[4] = {0, 0, 0, 0};
-    if (out4) (void)hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_img_waits), sizeof(z));
-    if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_img_waits), z, sizeof(z));
-}
-#endif
 
 // ---- host side: called from stem_conv2d_f16x3_gen_fwd (conv_f16x3.hip) -------------------------------------------------------------
 bool stem_fx3_img_eligible(int B, int H, int W, int N, int R, int S, int stride, int pad)
@@ -755,10 +602,6 @@ int stem_fx3_img_launch(const void *xp, const float *xq, int xpix, int xbytes, c
     a.B = B; a.H = H; a.W = W; a.C = C; a.N = N; a.ntaps = T;
     a.xbytes = xbytes; a.wbytes = wbytes; a.z = z; a.ldz = ldz; a.epi = epi; a.slope = slope;
     a.xpix = xpix;
-#ifdef STEM_EXPERIMENTS
-    a.stamps = g_img_stamps;
-    a.ablate = g_img_ablate;
-#endif
     a.tiles_x = cdiv(W, TS); a.tiles_y = cdiv(H, TS);
     const int nchunks = (C / 32) * T;
     a.cps = cdiv(nchunks, split);
@@ -774,12 +617,7 @@ int stem_fx3_img_launch(const void *xp, const float *xq, int xpix, int xbytes, c
         (void)hipFuncSetAttribute((const void *)conv_f16x3_img_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, ILDS);
         attr_done = true;
     }
-    a.ny = cdiv(N, IBN);
-    dim3 grid(B * a.tiles_x * a.tiles_y, cdiv(N, IBN), a.nsplit);
-#ifdef STEM_EXPERIMENTS
-    if (a.ablate == 3 && a.nsplit > 1) grid = dim3(cdiv(B * a.tiles_x * a.tiles_y * a.ny, 8) * 8 * a.nsplit);
-    else if (a.ablate == 3) a.ablate = 0;
-#endif
+    const dim3 grid(B * a.tiles_x * a.tiles_y, cdiv(N, IBN), a.nsplit);
     hipStream_t st = (hipStream_t)stream;
     if (KS == 1)
         hipLaunchKernelGGL((conv_f16x3_img_kernel<1>), grid, dim3(NTHR), ILDS, st, a);

@@ -55,7 +55,6 @@ struct IgemmArgs {
     int xbytes, wbytes;      // extents of the x / w views for the range-checked buffer loads
     const float *gamma;      // fused conv + GDN/IGDN (FUSE kernels): stored gamma [N][N], beta in `beta`
     int fuse, gmbytes;       // 0 none, 1 GDN, 2 IGDN
-    int exper;               // tuning experiments (STEM_IGEMM_EXPER), 0 in production
     int ident;               // output pixel index == m (stride-1, single phase): no div/mod in the epilogue
     TapPhase ph[4];
 };
@@ -965,8 +964,6 @@ int launch(IgemmArgs &g, bool c4, void *ws, size_t ws_bytes, hipStream_t st)
         g.xbytes = (int)xb;
         g.wbytes = (int)wb;
     }
-    static const int exper = STEM_EXPER_ENV("STEM_IGEMM_EXPER") ? atoi(STEM_EXPER_ENV("STEM_IGEMM_EXPER")) : 0;     // ablations: -DSTEM_EXPERIMENTS builds only
-    g.exper = exper;
     g.ident = (g.nphase == 1 && g.osy == 1 && g.osx == 1 && g.ph[0].ooy == 0 && g.ph[0].oox == 0 &&
                g.ph[0].qh == g.OH && g.ph[0].qw == g.OW) ? 1 : 0;
     static const bool autotune = getenv("STEM_IGEMM_AUTOTUNE") && atoi(getenv("STEM_IGEMM_AUTOTUNE")) != 0;

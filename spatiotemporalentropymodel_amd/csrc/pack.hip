@@ -15,14 +15,6 @@ void stem_set_error(const char *fmt, ...)
 }
 STEM_EXPORT const char *stem_last_error(void) { return g_err; }
 STEM_EXPORT int stem_abi_version(void) { return 5; }      // 5 (round 5): + stem_tconv2d_f16x3_*, stem_conv2d_wgrad_f16x3_strided, stem_f16x2_pack_conv_weights_pair_multi, stem_tape_set_farg, stem_tape_entry_recordable, stem_zero_bytes, stem_stream_flag_*; stem_f16x2_pack_desc.flip = 2
-STEM_EXPORT int stem_built_with_experiments(void)
-{
-#ifdef STEM_EXPERIMENTS
-    return 1;
-#else
-    return 0;
-#endif
-}
 
 static int g_tuning[STEM_TUNE_COUNT] = {0};
 static const char *const kTuningNames[STEM_TUNE_COUNT] = {"fx3_tile", "fx3_split", "wg3_split", "arp_workers", "fx3_depth", "fx3_gen_tile", "fx3_mfma", "fx3_gen_mfma", "fx3_gen_img", "fx3_img_w", "wg3_row", "wg3_minch", "tconv_cps", "arp_giveup_at", "unpack_mb"};

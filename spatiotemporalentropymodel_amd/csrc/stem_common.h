@@ -48,15 +48,6 @@ int stem_fx3_img_split(int tiles, int nchunks);
 int stem_fx3_img_launch(const void *xp, const float *xq, int xpix, int xbytes, const void *wp, const float *wq, int wbytes, const float *bias, int epi,
                         float slope, const float *z, int ldz, float *y, int ldy, void *yp, float *yq, int B, int H, int W, int C, int N, int KS,
                         int T, int split, float *ws, int *cnt, void *stream);
-// Switches that CHANGE RESULTS (ablated kernel stages, instrumentation) exist only in a library built with
-// -DSTEM_EXPERIMENTS (`make experiments` -> libstem_hip_exper.so, for tools/debug): in the shipped library the macro below is
-// a constant null pointer.
-#ifdef STEM_EXPERIMENTS
-#include <stdlib.h>
-#define STEM_EXPER_ENV(name) getenv(name)
-#else
-#define STEM_EXPER_ENV(name) (static_cast<const char *>(nullptr))
-#endif
 
 // parameters per workgroup of the optimiser pass that leaves per-chunk maxima for the fp16 weight packing (optim.hip, conv_f16x3.hip)
 #define STEM_ADAM_CHUNK 4096
@@ -143,8 +134,8 @@ __device__ inline void record_block_max(float *q, float m)
 // device-coherent level, not from this XCD's L2) and has re-armed the counter for the next launch.
 //
 // Memory order of the ticket.  In the terms of the HIP memory model the protocol wants a RELEASE before and an ACQUIRE after the
-// ticket; -DSTEM_SPLITK_ORDER=__ATOMIC_ACQ_REL builds exactly that (`buffer_wbl2 sc1` + atomic + `buffer_inv sc1` by the one
-// thread).  Measured in the training step (round 5, profiles/r05_ab_splitk_order.log, alternating passes on one box):
+// ticket; an acquire-release ticket builds exactly that (`buffer_wbl2 sc1` + atomic + `buffer_inv sc1` by the one
+// thread).  Measured in the training step (round 5, alternating passes on one box; profiles/README.md):
 // 14.36 / 14.44 ms per bench step against 13.83 / 13.85 ms with the relaxed ticket -- +4 %: the write-back / invalidate act on the
 // XCD's whole L2, i.e. on the working sets of the kernels running next to this one.  The shipped form therefore stays RELAXED and
 // rests on what the ISA guarantees for the accesses involved rather than on a fence: an sc1 store is acknowledged (vmcnt) only
@@ -154,24 +145,16 @@ __device__ inline void record_block_max(float *q, float m)
 // test_first_launch_on_fresh_workspaces_is_reproducible (the case a wider store form failed in round 4) and the bit-reproducibility
 // tests of the training step.
 //
-// STEM_SPLITK_ACQUIRE_LAST (round 6): the reader's half of that pair where it is needed and nowhere else -- an agent-scope ACQUIRE
-// fence (`buffer_inv sc1`) executed by the one thread of the ONE workgroup per tile whose ticket says "last", relaxed tickets for
-// everybody else, stores as they are.  nsplit times fewer cache operations than the acquire-release ticket and no write-back at
-// all; A/B in the step: profiles/r06_ab_splitk_acquire_last.log.
-#ifndef STEM_SPLITK_ORDER
-#define STEM_SPLITK_ORDER __ATOMIC_RELAXED
-#endif
-#ifndef STEM_SPLITK_ACQUIRE_LAST
-#define STEM_SPLITK_ACQUIRE_LAST 1
-#endif
+// Round 6: the reader's half of that pair where it is needed and nowhere else -- an agent-scope ACQUIRE fence (`buffer_inv sc1`)
+// executed by the one thread of the ONE workgroup per tile whose ticket says "last", relaxed tickets for everybody else, stores
+// as they are.  nsplit times fewer cache operations than the acquire-release ticket and no write-back at all; measured free in the
+// step.
 __device__ inline bool splitk_last_arriver(int *counter, int nsplit)
 {
-    const int ticket = __hip_atomic_fetch_add(counter, 1, STEM_SPLITK_ORDER, __HIP_MEMORY_SCOPE_AGENT);
+    const int ticket = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const bool last = ticket == nsplit - 1;
     if (last) {
-#if STEM_SPLITK_ACQUIRE_LAST
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
         __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     return last;

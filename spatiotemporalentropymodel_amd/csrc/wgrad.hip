@@ -17,9 +17,6 @@
 namespace {
 
 constexpr int KP = 32;   // pixels per chunk
-#ifndef WGRAD_PAD
-#define WGRAD_PAD 0
-#endif
 
 struct WgradArgs {
     const float *p, *g;
@@ -70,7 +67,7 @@ void wgrad_kernel(const WgradArgs a)
     // LDS pitches = tile widths, no padding: the operand fetch is ds_read_b32 (lane groups are the two 32-lane halves, which
     // read different rows and never share a cycle) and the staging writes are 16-byte runs of 8 consecutive lanes, so both
     // are conflict-free at any pitch; unpadded, the 64x64 tile takes exactly 32 KiB = five workgroups per CU.
-    constexpr int PA = BM + WGRAD_PAD, PB = BN + WGRAD_PAD;
+    constexpr int PA = BM, PB = BN;
     constexpr int F4A = BM / 4, F4B = BN / 4;               // float4 per pixel row
     constexpr int RPA = NT / F4A, RPB = NT / F4B;           // pixel rows per pass
     constexpr int NPA = KP / RPA, NPB = KP / RPB;           // passes
@@ -349,7 +346,7 @@ template <int BM, int BN, int WM, int WN>
 int launch_cfg(const WgradArgs &a, bool vec, hipStream_t st)
 {
     dim3 grid(cdiv(a.CP, BM) * cdiv(a.CG, BN), a.R * a.S, a.splits), block((BM / WM) * (BN / WN) * 64);
-    const size_t lds = (size_t)2 * KP * (BM + BN + 2 * WGRAD_PAD) * sizeof(float);
+    const size_t lds = (size_t)2 * KP * (BM + BN) * sizeof(float);
     static bool attr_done = false;
     if (!attr_done) {
         (void)hipFuncSetAttribute((const void *)wgrad_kernel<BM, BN, WM, WN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -368,7 +365,7 @@ int launch_c4(const WgradArgs &a, hipStream_t st)
 {
     constexpr int BM = 64, BN = 64;
     dim3 grid(cdiv(a.CP, BM) * cdiv(a.R * a.S, BN / 4), 1, a.splits), block(256);
-    const size_t lds = (size_t)2 * KP * (BM + BN + 2 * WGRAD_PAD) * sizeof(float);
+    const size_t lds = (size_t)2 * KP * (BM + BN) * sizeof(float);
     hipLaunchKernelGGL((wgrad_kernel<BM, BN, 32, 32, true, true>), grid, block, lds, st, a);
     STEM_LAUNCH_CHECK("wgrad_c4");
     return 0;

@@ -34,17 +34,6 @@ class _Switch:
         return getattr(_config._RUNTIME or _config.runtime(), self.field)
 
 
-class _RangePlanes:
-    """the planes of a tensor that was produced range by range (one F16Planes per channel range, each with its own scale record):
-    `channels(c0, c1)` hands out the part that covers exactly that range"""
-
-    def __init__(self, parts):
-        self.parts = dict(parts)            # (c0, c1) -> F16Planes
-
-    def channels(self, c0, c1):
-        return self.parts[(c0, c1)]
-
-
 class _Layer:
     """One convolution of the schedule: parameters, persistent packed-weight buffers and wgrad slabs."""
 
@@ -230,11 +219,7 @@ class _Layer:
                                      bias_part=bpart if (conv and gb is not None) else None)
         self.pending_bias = None
         if gb is not None and conv:                      # column sums of dy came out of the kernel: second stage
-            desc = _lib.BiasFinalDesc(bpart.data_ptr(), gb.data_ptr(), self.K, splits, int(self.eng.accumulate_grads), 0)
-            if self.eng.defer_bias_final:
-                self.pending_bias = desc
-            else:
-                F.bias_grad_final_multi([desc])
+            self.pending_bias = _lib.BiasFinalDesc(bpart.data_ptr(), gb.data_ptr(), self.K, splits, int(self.eng.accumulate_grads), 0)
         elif gb is not None:                             # the transposed layer's bias sees the FINE tensor: its own column sums
             F.bias_grad(dy, gb, accumulate=self.eng.accumulate_grads)
         self.pending = (dwp, splits)
@@ -269,7 +254,7 @@ class _Layer:
         dwp, splits, bpart = self._slabs[key]
         gb = _grad_of(self.mod.bias) if self.mod.bias is not None else None
         self.pending_bias = F.conv2d_wgrad_f16x3(xp, dyp, self.K, self.R, self.R, self.pad, dwp, splits, db=gb, bias_part=bpart,
-                                                 accumulate_db=self.eng.accumulate_grads, defer_bias=self.eng.defer_bias_final)
+                                                 accumulate_db=self.eng.accumulate_grads, defer_bias=True)
         self.pending = (dwp, splits)
 
     def _desc32(self, role):
@@ -286,7 +271,6 @@ class _Layer:
 
     def fwd(self, x, act=F.ACT_NONE, out=None):
         self.eng.ensure_packed()
-        self.eng._wait_fwd_rest()
         if self.fx3 or (self.fx3s and self.kind == "conv"):          # callers outside the training schedule (codec.py) hand over fp32 tensors
             return self.fwd6(F.F16Planes.split(x), act, out=out)[0]
         if self.fx3t and self.kind == "deconv":
@@ -330,7 +314,7 @@ class _Layer:
             splits, elems = F.wgrad_plan(x.shape, self.K, self.R, self.R, self.stride, self.pad, deconv=deconv)
             self._slabs[key] = (torch.empty(elems, device=x.device, dtype=torch.float32), splits)
         dwp, splits = self._slabs[key]
-        defer = self.eng.defer_bias_final and gb is not None
+        defer = gb is not None
         if deconv:
             _, b = F.deconv2d_wgrad(x, dy, self.K, self.R, self.R, self.stride, self.pad, self.opad, db_out=gb, dwp=dwp, unpack=False,
                                     table_valid=not fresh, accumulate_db=self.eng.accumulate_grads, defer_bias=defer)
@@ -395,7 +379,6 @@ class StemEngine:
         self._checked = False
         self._dgrad_pack_event = None
         self._fwd32_pack_event = None
-        self._fwd_rest_event = None
         #: backward ADDS into .grad (autograd's semantics; several backward passes between two zero_grad() calls accumulate).  An explicit
         #: schedule that produces every gradient exactly once per step sets it False for its backward: the producers then OVERWRITE
         #: (no clearing pass, no read of the old value: 144 MB less HBM traffic per P-frame step of the big model)
@@ -468,18 +451,6 @@ class StemEngine:
     #: input-gradient copies on a weight-gradient stream (only backward waits): 22.48-22.62 ms against 22.67-22.82 ms per bench
     #: step; STEM_ENGINE_SPLIT_PACK=0: one launch each as before
     split_pack = _Switch("engine_split_pack")
-    #: ... and of the forward-role images only those of the layers that open the forward are packed on the compute stream, the others
-    #: on the weight-gradient stream under the opening kernels.  Shortens the P-frame step's critical path by ~60 us when the step
-    #: runs alone; inside the bench step (chip shared with the latent prefetch) it measured 12.39 against 12.32 ms
-    #: (profiles/r05_ab_pack_first.log): off by default, STEM_ENGINE_PACK_FIRST=1 enables it
-    pack_first = _Switch("engine_pack_first")
-
-    #: the temporal-prior chain's weight gradients (three filter-row launches + slab sums, ~300 us of the ~900 us the
-    #: weight-gradient stream carries per P-frame step) are issued on the COMPUTE stream, behind the chain's own input gradients:
-    #: that stream has nothing else to do once the TPM input gradients are out (the hyper chain runs on its branch stream), while the
-    #: weight-gradient stream was the last to finish by ~250 us (profiles/r05_gantt_palone.txt).  Scheduling only: lane -1 = "the
-    #: stream the backward runs on".  STEM_ENGINE_TPM_WGRAD_INLINE=0: every weight gradient on the side stream, as in round 4
-    tpm_wgrad_inline = _Switch("engine_tpm_wgrad_inline")
 
     def side_stream(self, device, lane=0):
         if not self.overlap_wgrad or device.type != "cuda" or lane < 0:
@@ -493,20 +464,6 @@ class StemEngine:
     #: network joins them: the hyper path runs on its own stream in forward and backward so that the ramp-up / drain of its
     #: small launches overlaps the other branch's kernels (30.90 -> 30.75 ms per bench step; STEM_ENGINE_BRANCH=0 disables)
     branch_streams = _Switch("engine_branch")
-    #: the temporal-prior chain is enqueued before the hyper branch (scheduling only)
-    tpm_first = _Switch("engine_tpm_first")
-    tpm_first_bwd = _Switch("engine_tpm_first_bwd")
-    #: the context model's forward on the weight-gradient stream (opt-in experiment, STEM_ENGINE_CTX_ON_SIDE=1)
-    ctx_on_side = _Switch("engine_ctx_on_side")
-    ctx_split_on_side = _Switch("engine_ctx_split_on_side")
-    #: one planes tensor for he_in = [y_cur | y_cond] and the TPM chain's input (its second half): a split launch less per step
-    share_in_planes = _Switch("engine_share_in_planes")
-    #: EPM.0's input gradient as one launch per prior range, the hyper chain's range first, so that the chain that ends the backward
-    #: starts a third of the launch earlier.  Three 128-row-tile launches instead of one: 11.80 against 11.61 ms per bench step
-    #: (profiles/r05_ab_epm_by_prior.log) -- three smaller launches cost more than the earlier start returns.  Off; STEM_ENGINE_EPM_DGRAD_BY_PRIOR=1
-    epm_dgrad_by_prior = _Switch("engine_epm_dgrad_by_prior")
-    #: the GaussianConditional's backward computed by the fused forward glue (one launch less per P-frame step)
-    fuse_gc_backward = _Switch("engine_fuse_gc_backward")
 
     def _branch(self, device, which=0):
         if not self.branch_streams or device.type != "cuda":
@@ -554,30 +511,7 @@ class StemEngine:
                 descs6 = [d for _, b in both for d in b]
                 if descs6 and block_max is not None:
                     _attach_block_maxima(descs6, *block_max)
-                first6 = []
-                if descs6 and side is not None and not on_side and self.pack_first:
-                    # The forward cannot start before its first kernels' images exist, and the optimiser pass cannot overlap anything:
-                    # only the images of the layers that OPEN the forward (TPM.0, HE.0, the context model: 3.9 of 17 M weights) are
-                    # packed on the compute stream; the others follow on the weight-gradient stream, in front of its input-gradient
-                    # images, while the opening kernels run.  Their consumers wait for `fwd_rest` (_wait_fwd_rest).
-                    opening = {id(l) for l in ([self.HE[0]] + ([self.TPM[0]] if self.has_tpm else []) + ([self.CTX] if self.has_spm else []))}
-                    fwd_pairs = [(l, d) for l in self.layers for d in l.role_descs(0)[1]]
-                    first6 = [d for l, d in fwd_pairs if id(l) in opening]
-                    rest6 = [d for l, d in fwd_pairs if id(l) not in opening]
-                    if first6 and rest6:
-                        if block_max is not None:
-                            _attach_block_maxima(first6 + rest6, *block_max)
-                        F.pack_weights_f16x2_multi((_lib.F16PackDesc * len(first6))(*first6))
-                        F.stream_wait(side, F.cur_stream(dev))
-                        with F.on_stream(side):
-                            F.pack_weights_f16x2_multi((_lib.F16PackDesc * len(rest6))(*rest6))
-                            self._fwd_rest_event = self._events.setdefault("fwd_rest", torch.cuda.Event())
-                            F.event_record(self._fwd_rest_event, side)
-                    else:
-                        first6 = []
-                if descs6 and not first6:          # the forward's first kernels (HE.0, TPM.0, the context model) wait for these
-                    if not on_side:
-                        self._fwd_rest_event = None
+                if descs6:                        # the forward's first kernels (HE.0, TPM.0, the context model) wait for these
                     F.pack_weights_f16x2_multi((_lib.F16PackDesc * len(descs6))(*descs6))
                 # the fp32 copies of the forward role (the transposed hyper-decoder layers: consumed on the hyper branch, half a
                 # forward later) are packed on that branch's stream, off the compute stream's optimiser -> forward chain
@@ -620,7 +554,7 @@ class StemEngine:
             d.bmax, d.b0 = maxima.data_ptr(), off // ch
             d.nb = (off + numel - 1) // ch - d.b0 + 1
         F.pack_weights_f16x2_pair_multi((_lib.F16PairDesc * len(descs))(*descs))
-        self._dgrad_pack_event = self._fwd_rest_event = None
+        self._dgrad_pack_event = None
         return True
 
     def unpack_all(self):
@@ -631,9 +565,6 @@ class StemEngine:
     #: (EPM, context_prediction, TPM, HD + entropy_bottleneck, HE -- the order backward produces them) are final,
     #: so a data-parallel reducer can start exchanging that slice while the rest of backward still runs
     grad_ready_hook = None
-
-    #: one launch for a group's bias-gradient second stages (stem_bias_grad_final_multi); STEM_ENGINE_BIAS_MULTI=0: one per layer
-    defer_bias_final = _Switch("engine_bias_multi")
 
     def _group_ready(self, layers, extra_params):
         dev = layers[0].mod.weight.device
@@ -671,12 +602,6 @@ class StemEngine:
         if self._fwd32_pack_event is not None:
             F.event_wait(F.cur_stream(), self._fwd32_pack_event)
 
-    def _wait_fwd_rest(self):
-        """a consumer of a forward-role image that was packed on the weight-gradient stream (every layer but the ones that open
-        the forward): order the current stream behind that packing"""
-        if self._fwd_rest_event is not None:
-            F.event_wait(F.cur_stream(), self._fwd_rest_event)
-
     def _wait_dgrad_packs(self):
         """backward's first consumer of an input-gradient weight copy: order it after the side-stream packing"""
         if self._dgrad_pack_event is not None:
@@ -705,16 +630,12 @@ class StemEngine:
         assert not fused or training, "the fused glue is the TRAINING forward"
         k = {}
         target = t_hat = y_hat = None
-        ctx_go = None
         rec = self._rec = {}    # scale records left by the producers of fp32 tensors that are split for the fp16 kernels below
         if fused:
             # one kernel: he_in = [y_cur | y_cond], target, t_hat = target + noise, y_hat = t_hat (+ y_cond); it also records
             # max |y_cur|, |y_cond| and max |t_hat| per workgroup: the splits of he_in, y_cond and t_hat need no maximum pass
             slot = gc._noise_slot(yc) if self.has_spm else {}
             he_in, target, t_hat, y_hat = F.prior_prologue(yc, yd, self.residual, True, self.has_spm, records=rec if self.use_fx3 and self.use_records else None, **slot)
-            if self.has_spm and self.ctx_on_side and self.side_stream(dev) is not None and self._branch(dev) is not None:
-                ctx_go = self._events.setdefault("ctx_go", torch.cuda.Event())       # t_hat exists from here on
-                F.event_record(ctx_go, F.cur_stream(dev))
         else:
             # hyper encoder on cat(y_cur, y_cond): the two halves are written into one buffer
             he_in = F.empty_nhwc(B, 2 * Cin, H, W, dev)
@@ -732,8 +653,7 @@ class StemEngine:
         split = F.F16Planes.split
         tp0 = tp2 = None
         ctx_split_done = None
-        if (fused and self.has_spm and self.CTX.fx3 and self.ctx_split_on_side and ctx_go is None and rec.get("t_hat") is not None
-                and self.side_stream(dev) is not None):
+        if fused and self.has_spm and self.CTX.fx3 and rec.get("t_hat") is not None and self.side_stream(dev) is not None:
             # t_hat exists since the prologue and the context model runs behind the TPM chain: its planes are made meanwhile on the
             # weight-gradient stream, which has nothing to do during the forward (one launch less between TPM.4 and the context model)
             side = self.side_stream(dev)
@@ -744,7 +664,7 @@ class StemEngine:
                 F.event_record(ctx_split_done, side)
             t_hat.record_stream(side)
 
-        if self.share_in_planes and fused and self.HE[0].fx3 and self.has_tpm and self.TPM[0].fx3 and Cin % 32 == 0 and rec.get("in") is not None:
+        if fused and self.HE[0].fx3 and self.has_tpm and self.TPM[0].fx3 and Cin % 32 == 0 and rec.get("in") is not None:
             # he_in = [y_cur | y_cond] and the TPM chain's input y_cond share ONE planes tensor (same record: max(|y_cur|, |y_cond|)):
             # one split on the compute stream, the TPM chain reads its second half as a channel view, the hyper branch (which waits
             # for this stream anyway) the whole -- a launch less, the same values
@@ -753,24 +673,18 @@ class StemEngine:
             if bs is not None:
                 F.stream_wait(bs, main)
 
-        def tpm_chain():
-            nonlocal tp0, tp2
-            if self.has_tpm and self.TPM[0].fx3:
-                # planes travel from layer to layer (written by the producing epilogue next to the fp32 copy backward needs)
-                if "yd" not in pl:
-                    pl["yd"] = split(yd, src_q=_qp(rec.get("in")))       # max(|y_cur|, |y_cond|) bounds y_cond
-                tp0, pl["tp0"] = self.TPM[0].fwd6(pl["yd"], F.ACT_LRELU, planes=True)
-                self._wait_fwd_rest()
-                tp2, pl["tp2"] = self.TPM[1].fwd6(pl["tp0"], F.ACT_LRELU, planes=True)
-                self.TPM[2].fwd6(pl["tp2"], out=epm_in[:, o_tp:o_tp + P])
-            elif self.has_tpm:
-                self._wait_fwd_rest()
-                tp0 = self.TPM[0].fwd(yd, F.ACT_LRELU)
-                tp2 = self.TPM[1].fwd(tp0, F.ACT_LRELU)
-                self.TPM[2].fwd(tp2, out=epm_in[:, o_tp:o_tp + P])
-
-        if self.tpm_first:           # enqueued ahead of the hyper branch's ~14 launches: the TPM chain is the forward's critical path
-            tpm_chain()
+        # the TPM chain is enqueued ahead of the hyper branch's ~14 launches: it is the forward's critical path
+        if self.has_tpm and self.TPM[0].fx3:
+            # planes travel from layer to layer (written by the producing epilogue next to the fp32 copy backward needs)
+            if "yd" not in pl:
+                pl["yd"] = split(yd, src_q=_qp(rec.get("in")))       # max(|y_cur|, |y_cond|) bounds y_cond
+            tp0, pl["tp0"] = self.TPM[0].fwd6(pl["yd"], F.ACT_LRELU, planes=True)
+            tp2, pl["tp2"] = self.TPM[1].fwd6(pl["tp0"], F.ACT_LRELU, planes=True)
+            self.TPM[2].fwd6(pl["tp2"], out=epm_in[:, o_tp:o_tp + P])
+        elif self.has_tpm:
+            tp0 = self.TPM[0].fwd(yd, F.ACT_LRELU)
+            tp2 = self.TPM[1].fwd(tp0, F.ACT_LRELU)
+            self.TPM[2].fwd(tp2, out=epm_in[:, o_tp:o_tp + P])
         with F.on_stream(bs):
             if self.HE[0].fx3:
                 if "he_in" not in pl:
@@ -778,7 +692,6 @@ class StemEngine:
                 he0, he0p = self.HE[0].fwd6(pl["he_in"], F.ACT_LRELU, planes=self.HE[1].fx3s)
             else:
                 he0 = self.HE[0].fwd(he_in, F.ACT_LRELU)
-            self._wait_fwd_rest()
             if self.HE[1].fx3s:           # the strided forwards on the general fp16 kernel, planes handed down
                 he2, he2p = self.HE[1].fwd6(he0p, F.ACT_LRELU, planes=self.HE[2].fx3s)
                 z = self.HE[2].fwd6(he2p)[0] if self.HE[2].fx3s else self.HE[2].fwd(he2)
@@ -814,31 +727,17 @@ class StemEngine:
                 self.HD[2].fwd6(pl["hd2"], out=epm_in[:, o_hp:o_hp + P])
             else:
                 self.HD[2].fwd(hd2, out=epm_in[:, o_hp:o_hp + P])
-        if not self.tpm_first:
-            tpm_chain()
         if not fused:
             target = F.sub(yc, yd) if self.residual else (yc if F.nhwc_ld(yc) == Cin else F.copy_channels(yc, F.empty_nhwc(B, Cin, H, W, dev)))
         if self.has_spm:
             # gaussian_conditional.quantize(target, "noise" | "dequantize") with no means (:570-572, :853-855)
             if not fused:
                 t_hat = F.add(target, gc._noise_like(target)) if training else F.round_(target)
-            if ctx_go is not None:
-                # the context model only needs t_hat: on the weight-gradient stream (idle during the forward) next to the TPM chain
-                # and the hyper branch, instead of behind the TPM chain
-                side = self.side_stream(dev)
-                F.event_wait(side, ctx_go)
-                with F.on_stream(side):
-                    self._ctx_forward(t_hat, epm_in[:, o_ctx:o_ctx + P], pl)
-                t_hat.record_stream(side)
-                epm_in.record_stream(side)
-                F.stream_wait(main, side)
-            else:
-                if ctx_split_done is not None:
-                    F.event_wait(F.cur_stream(dev), ctx_split_done)
-                self._ctx_forward(t_hat, epm_in[:, o_ctx:o_ctx + P], pl)
+            if ctx_split_done is not None:
+                F.event_wait(F.cur_stream(dev), ctx_split_done)
+            self._ctx_forward(t_hat, epm_in[:, o_ctx:o_ctx + P], pl)
         if bs is not None:
             F.stream_wait(main, bs)
-        self._wait_fwd_rest()
         if self.EPM[0].fx3:
             pl["epm_in"] = split(epm_in)
             e0, pl["e0"] = self.EPM[0].fwd6(pl["epm_in"], F.ACT_LRELU, planes=True)
@@ -852,15 +751,11 @@ class StemEngine:
         if fused:
             # the GaussianConditional's backward in the same launch (d loss / d likelihood = coef / lik is known here): backward()
             # uses it when it is handed this very dlik_y
-            if self.fuse_gc_backward:
-                dgp = F.empty_nhwc(B, 2 * Cin, H, W, dev)
-                gc_out, lik_y, k["dlik_y"], part_y, k["qg"] = F.gc_forward_train(
-                    target, scales, means, rate_coef[0], scale_bound=gc._scale_bound, lik_bound=gc._lik_bound,
-                    backward=(dgp[:, :Cin], dgp[:, Cin:]), record=self.EPM[0].fx3 and self.use_records, **gc._noise_slot(target))
-                k["dgp"] = dgp
-            else:
-                gc_out, lik_y, k["dlik_y"], part_y = F.gc_forward_train(target, scales, means, rate_coef[0], scale_bound=gc._scale_bound,
-                                                                        lik_bound=gc._lik_bound, **gc._noise_slot(target))
+            dgp = F.empty_nhwc(B, 2 * Cin, H, W, dev)
+            gc_out, lik_y, k["dlik_y"], part_y, k["qg"] = F.gc_forward_train(
+                target, scales, means, rate_coef[0], scale_bound=gc._scale_bound, lik_bound=gc._lik_bound,
+                backward=(dgp[:, :Cin], dgp[:, Cin:]), record=self.EPM[0].fx3 and self.use_records, **gc._noise_slot(target))
+            k["dgp"] = dgp
             k["loss3"] = F.em_loss_finalize(part_y, part_z, rate_coef[1])
             if not self.has_spm:
                 y_hat = gc_out
@@ -904,23 +799,7 @@ class StemEngine:
             self.EPM[1].wgrad_any(k["e0"], de2, pl.get("e0"), de2p)
             de0, de0p = self.EPM[1].dgrad6(de2p, xact=k["e0"], planes=True)
             self.EPM[0].wgrad_any(k["epm_in"], de0, pl.get("epm_in"), de0p)
-            if self.epm_dgrad_by_prior and P % 128 == 0 and self.branch_streams and self._branch(gp.device) is not None:
-                # EPM.0's input gradient feeds three independent consumers (hyper chain, TPM chain, context weight gradient): computed
-                # range by range, the hyper chain's first -- the chain that ends the backward -- which then starts a third of the
-                # launch earlier (rows [n0, n0 + P) of the flipped weight image = whole 128-row tiles)
-                l0 = self.EPM[0]
-                dpri = F.empty_nhwc(B, self.nprior * P, H, W, gp.device)
-                order = [o_hp] + ([o_tp] if self.has_tpm else []) + ([o_ctx] if self.has_spm else [])
-                parts = {}
-                for j, o in enumerate(order):
-                    _, parts[(o, o + P)] = F.conv2d_f16x3_gen(de0p, l0.wp6_dgrad, None, P, l0.R, l0.R, 1, l0.pad, out=dpri[:, o:o + P],
-                                                              want_planes=True, rows=(self.nprior * P, o))
-                    if j == 0:
-                        hp_done = self._events.setdefault("bwd_epm", torch.cuda.Event())
-                        F.event_record(hp_done, F.cur_stream(gp.device))
-                dprip = _RangePlanes(parts)
-            else:
-                dpri, dprip = self.EPM[0].dgrad6(de0p, planes=True)    # the prior branches read 32-aligned channel views of the planes
+            dpri, dprip = self.EPM[0].dgrad6(de0p, planes=True)        # the prior branches read 32-aligned channel views of the planes
         else:
             self.EPM[2].wgrad(k["e2"], dgp)
             de2 = self.EPM[2].dgrad(dgp, k["e2"].shape, xact=k["e2"])
@@ -934,16 +813,7 @@ class StemEngine:
 
         if bs is not None:                 # the hyper chain depends on the EPM input gradient only: its point on the compute stream
             epm_done = self._events.setdefault("bwd_epm", torch.cuda.Event())
-            if not isinstance(dprip, _RangePlanes):          # (range by range: recorded right behind the hyper chain's range)
-                F.event_record(epm_done, main)
-
-        def hyper_branch():                # hyper chain (HD -> bottleneck -> HE) on its own stream, next to the TPM chain
-            F.event_wait(bs, epm_done)
-            with F.on_stream(bs):
-                self._backward_hyper(k, dpri, dlik_z, dprip)
-
-        if bs is not None and not self.tpm_first_bwd:
-            hyper_branch()
+            F.event_record(epm_done, main)
         # spatial prior: weight gradient of all 25 taps, no input gradient (its input is data + noise)
         if self.has_spm:
             if self.CTX.wg3 and dprip is not None:
@@ -953,8 +823,11 @@ class StemEngine:
                 self.CTX.wgrad(k["t_hat"], dpri[:, o_ctx:o_ctx + P])
             self._group_ready([self.CTX], [])
         if self.has_tpm:
+            # with a hyper branch stream, the chain's weight gradients (~300 us of the ~900 us the weight-gradient stream carries per
+            # P-frame step) go on the compute stream, behind its own input gradients: that stream is otherwise idle by then, while the
+            # weight-gradient stream finished last by ~250 us (profiles/r05_gantt_palone.txt).  lane -1 = "the stream backward runs on"
             for l in self.TPM:
-                l.lane = -1 if (self.tpm_wgrad_inline and bs is not None) else 0
+                l.lane = -1 if bs is not None else 0
             dtp = dpri[:, o_tp:o_tp + P]
             if self.TPM[2].fx3:
                 dtpp = dprip.channels(o_tp, o_tp + P) if dprip is not None else F.F16Planes.split(dtp)
@@ -970,11 +843,12 @@ class StemEngine:
                 d = self.TPM[1].dgrad(d, k["tp0"].shape, xact=k["tp0"])
                 self.TPM[0].wgrad(k["yd"], d)
             self._group_ready(self.TPM, [])
-        if bs is not None and self.tpm_first_bwd:
-            hyper_branch()
         if bs is None:
             self._backward_hyper(k, dpri, dlik_z, dprip)
-        else:
+        else:                              # hyper chain (HD -> bottleneck -> HE) on its own stream, enqueued behind the TPM chain
+            F.event_wait(bs, epm_done)
+            with F.on_stream(bs):
+                self._backward_hyper(k, dpri, dlik_z, dprip)
             F.stream_wait(main, bs)
         self.join_side_stream()          # gradients are complete for whatever the compute stream does next
 

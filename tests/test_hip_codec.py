@@ -145,13 +145,13 @@ def test_lockstep_batch_decode_equals_per_image_decode(monkeypatch):
         monkeypatch.delenv("STEM_AR_NO_BATCH")
         assert torch.equal(a, ref) and torch.equal(a0, ref)
         monkeypatch.setenv("STEM_AR_FORCE_BATCH", "1")     # the lockstep loop also for one image
-        monkeypatch.setenv("STEM_AR_PIPELINE", "1")        # flag-polling variant: no stream synchronisation per position
         c = m.decompress(enc["strings"], enc["shape"], y_cond)["y_hat"].clone()
         c1 = m.decompress([enc["strings"][0][:1], enc["strings"][1][:1]], enc["shape"], y_cond[:1])["y_hat"].clone()
-        monkeypatch.delenv("STEM_AR_PIPELINE")
-        c1s = m.decompress([enc["strings"][0][:1], enc["strings"][1][:1]], enc["shape"], y_cond[:1])["y_hat"].clone()
         monkeypatch.delenv("STEM_AR_FORCE_BATCH")
+        monkeypatch.setenv("STEM_AR_PERSISTENT", "0")
         monkeypatch.setenv("STEM_AR_NO_BATCH", "1")
+        c1s = m.decompress([enc["strings"][0][:1], enc["strings"][1][:1]], enc["shape"], y_cond[:1])["y_hat"].clone()   # per-position loop
+        monkeypatch.delenv("STEM_AR_PERSISTENT")
         b = m.decompress(enc["strings"], enc["shape"], y_cond)["y_hat"].clone()
         # and one image on its own equals its slot in the batch
         one = m.decompress([enc["strings"][0][3:4], enc["strings"][1][3:4]], enc["shape"], y_cond[3:4])["y_hat"]

@@ -500,9 +500,8 @@ def test_taped_step_at_the_bench_geometry_is_bit_identical(monkeypatch):
 
 
 # the switches of config.StemRuntimeConfig that stay supported next to the defaults (round 4: the others were deleted)
-_SCHEDULE_SWITCHES = [("overlap_wgrad", False), ("branch_streams", False), ("split_pack", False), ("defer_bias_final", False),
-                      ("tpm_first", False), ("tpm_first_bwd", False), ("tpm_wgrad_inline", False), ("pack_first", True), ("pack_pair", False), ("share_in_planes", False), ("ctx_split_on_side", False)]
-_ROUTE_SWITCHES = [("epm_dgrad_by_prior", True), ("fuse_gc_backward", False), ("use_wg3", False), ("use_fx3t", False), ("use_fx3s", False), ("use_ctx3", False), ("use_records", False), ("use_fx3", False)]
+_SCHEDULE_SWITCHES = [("overlap_wgrad", False), ("branch_streams", False), ("split_pack", False), ("pack_pair", False)]
+_ROUTE_SWITCHES = [("use_wg3", False), ("use_fx3t", False), ("use_fx3s", False), ("use_ctx3", False), ("use_records", False), ("use_fx3", False)]
 
 
 def _two_steps(monkeypatch, switch):
@@ -534,7 +533,7 @@ def _two_steps(monkeypatch, switch):
 
 def test_schedule_switches_change_no_bit(monkeypatch):
     """every scheduling switch that is still supported (weight gradients on the compute stream, no hyper branch, one packing
-    launch per role, bias second stages per layer, hyper branch enqueued first) gives the default's bits"""
+    launch per role, no pair pack) gives the default's bits"""
     ref = _two_steps(monkeypatch, None)
     for sw in _SCHEDULE_SWITCHES:
         got = _two_steps(monkeypatch, sw)

@@ -574,14 +574,14 @@ def test_runtime_config_is_the_one_reader_of_the_stem_switches(monkeypatch):
     monkeypatch.setenv("STEM_STREAM_PRIO", "side=-1")
     c = config.runtime()
     assert not c.engine_f16x3 and c.dp_min_bytes == 4096 and c.stream_prio == "side=-1" and c.engine_wgrad_f16x3
-    with config.override(engine_f16x3=True, ar_pipeline=True):
-        assert config.runtime().engine_f16x3 and config.runtime().ar_pipeline
+    with config.override(engine_f16x3=True, ar_force_batch=True):
+        assert config.runtime().engine_f16x3 and config.runtime().ar_force_batch
         monkeypatch.setenv("STEM_AR_STEPWISE", "1")                  # an environment change inside the block keeps the block's fields
         assert config.runtime().engine_f16x3 and config.runtime().ar_stepwise
         with config.override(engine_f16x3=False):
             assert not config.runtime().engine_f16x3
         assert config.runtime().engine_f16x3
-    assert not config.runtime().engine_f16x3 and not config.runtime().ar_pipeline
+    assert not config.runtime().engine_f16x3 and not config.runtime().ar_force_batch
     with pytest.raises(AttributeError):
         with config.override(no_such_field=1):
             pass
