@@ -13,6 +13,8 @@ producing convolution (forward) and into the consuming dgrad's epilogue (backwar
 """
 from __future__ import annotations
 
+import collections
+
 import torch
 
 from . import _lib
@@ -32,6 +34,30 @@ class _Switch:
 
     def __get__(self, obj, owner=None):
         return getattr(_config._RUNTIME or _config.runtime(), self.field)
+
+
+class _Act:
+    """One activation of the schedule: the fp32 NHWC tensor `x`, its fp16 planes `p` (None until an epilogue wrote them or planes()
+    split them) and `rec`, the scale record the producer of `x` left (None: a split measures x itself)."""
+    __slots__ = ("x", "p", "rec")
+
+    def __init__(self, x, p=None, rec=None):
+        self.x, self.p, self.rec = x, p, rec
+
+    def planes(self, record=True):
+        """the planes, split on the current stream at the first request"""
+        if self.p is None:
+            self.p = F.F16Planes.split(self.x, src_q=self.rec.data_ptr() if record and self.rec is not None else None)
+        return self.p
+
+    def channels(self, c0, c1):
+        """a channel range of both members (planes views are 32-channel aligned)"""
+        return _Act(self.x[:, c0:c1], None if self.p is None else self.p.channels(c0, c1))
+
+
+#: one face (forward / input gradient) of a layer: kind "gen" (general fp16 kernel), "phases" (the same kernel over the four sub-pixel
+#: phases of a transposed face) or "f32" (igemm.hip), and the (outputs, contraction channels, flip, taps) of its packed weight image
+_Face = collections.namedtuple("_Face", "kind N C flip taps")
 
 
 class _Layer:
@@ -85,61 +111,50 @@ class _Layer:
         return (self.fx3s and self.R % 2 == 1 and self.R >= 3 and self.pad == self.R // 2 and self.C % 32 == 0 and self.K % 32 == 0
                 and (self.kind == "conv" or self.opad == 1))
 
-    def alloc_packs(self, device):
-        if self.fx3s and self.fx3t:
-            conv = self.kind == "conv"
-            # (zeros: the pair pack never writes the padding rows of a 128-row tile)
-            strided = torch.zeros(F.f16x2_gen_weight_bytes(*((self.K, self.C) if conv else (self.C, self.K)), self.R, self.R), device=device, dtype=torch.uint8)
-            phases = torch.zeros(F.f16x2_gen_weight_bytes(*((self.C, self.K) if conv else (self.K, self.C)), self.R, self.R), device=device, dtype=torch.uint8)
-            self.wp_fwd = torch.empty(0, device=device)              # never read: marks the layer as allocated
-            self.wp_dgrad = None
+    def wg3_eligible(self):
+        """weight gradient on csrc/wgrad_f16x3.hip: stride-1 convolutions (all taps are produced, as autograd does for the
+        masked context convolution too)"""
+        return (self.kind == "conv" and self.stride == 1 and self.C % 32 == 0 and self.K % 32 == 0 and self.R % 2 == 1
+                and self.R * self.R <= 25 and self.pad == self.R // 2)
+
+    def set_faces(self):
+        """The ONE description of which kernel serves the layer's two faces, derived from the route flags when the engine has
+        chosen them (StemEngine._select_fx3): packing, allocation and the three compute methods below all read it."""
+        K, C, conv = self.K, self.C, self.kind == "conv"
+        fwd = dgrad = _Face("f32", K, C, 0, 0)
+        if self.fx3:              # the input gradient of a stride-1 convolution is a convolution with the mirrored, transposed weight
+            fwd, dgrad = _Face("gen", K, C, 0, self.taps), _Face("gen", C, K, 1, 0)
+        elif self.fx3s:
+            # strided face: the torch weight read as a Conv2d weight [outputs][contraction]; transposed face: read as w[c][n] (flip = 2)
             if conv:
-                self.wp6_fwd, self.wp6_dgrad = strided, (phases if self.need_dgrad else None)
+                fwd, dgrad = _Face("gen", K, C, 0, 0), (_Face("phases", C, K, 2, 0) if self.fx3t else dgrad)
             else:
-                self.wp6_fwd, self.wp6_dgrad = phases, (strided if self.need_dgrad else None)
-            return
-        if self.fx3s:
-            n = self.K * self.C * self.R * self.R
-            nb = F.f16x2_gen_weight_bytes(*((self.K, self.C) if self.kind == "conv" else (self.C, self.K)), self.R, self.R)
-            img = torch.empty(nb, device=device, dtype=torch.uint8)
-            if self.kind == "conv":      # forward on the fp16 kernel, input gradient on igemm.hip
-                self.wp6_fwd, self.wp6_dgrad = img, None
-                self.wp_fwd = torch.empty(0, device=device)          # never read: marks the layer as allocated
-                self.wp_dgrad = torch.empty(n, device=device, dtype=torch.float32) if self.need_dgrad else None
-            else:                        # forward on igemm.hip, input gradient on the fp16 kernel
-                self.wp6_fwd, self.wp6_dgrad = None, img
-                self.wp_fwd = torch.empty(n, device=device, dtype=torch.float32)
-                self.wp_dgrad = None
-            return
-        if self.fx3:
-            self.wp6_fwd = torch.zeros(F.f16x2_gen_weight_bytes(self.K, self.C, self.R, self.R), device=device, dtype=torch.uint8)
-            self.wp6_dgrad = torch.zeros(F.f16x2_gen_weight_bytes(self.C, self.K, self.R, self.R), device=device,
-                                         dtype=torch.uint8) if self.need_dgrad else None
-            return
-        n = self.K * self.C * self.R * self.R
-        self.wp_fwd = torch.empty(n, device=device, dtype=torch.float32)
-        self.wp_dgrad = torch.empty(n, device=device, dtype=torch.float32) if self.need_dgrad else None
+                fwd, dgrad = (_Face("phases", K, C, 2, 0) if self.fx3t else fwd), _Face("gen", C, K, 0, 0)
+        self.faces = (fwd, dgrad if self.need_dgrad else None)
+
+    def alloc_packs(self, device):
+        """exactly the packed weight copies the two faces read: fp32 (wp_*) for igemm.hip, an fp16 image (wp6_*) otherwise"""
+        bufs = []
+        for face in self.faces:
+            if face is None:
+                bufs += [None, None]
+            elif face.kind == "f32":
+                bufs += [torch.empty(self.K * self.C * self.R * self.R, device=device, dtype=torch.float32), None]
+            else:                 # (zeros: the pair pack never writes the padding rows of a 128-row tile)
+                bufs += [None, torch.zeros(F.f16x2_gen_weight_bytes(face.N, face.C, self.R, self.R), device=device, dtype=torch.uint8)]
+        self.wp_fwd, self.wp6_fwd, self.wp_dgrad, self.wp6_dgrad = bufs
+        if self.fx3s and self.wp_fwd is None:
+            self.wp_fwd = torch.empty(0, device=device)              # never read: a stride-2 layer without an fp32 forward copy
 
     def role_descs(self, role):
         """(fp32 descriptors, fp16 descriptors) of this layer's packed copies for role 0 (forward) / 1 (input gradient)"""
-        if self.fx3s and self.fx3t:
-            w, conv = self.mod.weight, self.kind == "conv"
-            # strided face: the torch weight read as a Conv2d weight [outputs][contraction]; transposed face: read as w[c][n] (flip = 2)
-            if role == 0:
-                return [], [_lib.F16PackDesc(w.data_ptr(), self.wp6_fwd.data_ptr(), self.K, self.C, self.R, self.R, 0 if conv else 2, 0)]
-            if not self.need_dgrad:
-                return [], []
-            return [], [_lib.F16PackDesc(w.data_ptr(), self.wp6_dgrad.data_ptr(), self.C, self.K, self.R, self.R, 2 if conv else 0, 0)]
-        if self.fx3s:
-            w, conv = self.mod.weight, self.kind == "conv"
-            if role == 0:
-                return ([], [_lib.F16PackDesc(w.data_ptr(), self.wp6_fwd.data_ptr(), self.K, self.C, self.R, self.R, 0, 0)]) if conv \
-                    else ([self._desc32(0)], [])
-            if not self.need_dgrad:
-                return [], []
-            return ([self._desc32(1)], []) if conv \
-                else ([], [_lib.F16PackDesc(w.data_ptr(), self.wp6_dgrad.data_ptr(), self.C, self.K, self.R, self.R, 0, 0)])
-        return ([], self.pack_descs6()[role:role + 1]) if self.fx3 else (self.pack_descs()[role:role + 1], [])
+        face = self.faces[role]
+        if face is None:
+            return [], []
+        if face.kind == "f32":
+            return [self._desc32(role)], []
+        wp = self.wp6_dgrad if role else self.wp6_fwd
+        return [], [_lib.F16PackDesc(self.mod.weight.data_ptr(), wp.data_ptr(), face.N, face.C, self.R, self.R, face.flip, face.taps)]
 
     def pair_desc(self):
         """both fp16 images of this layer as ONE descriptor of the pair pack (F.pack_weights_f16x2_pair_multi), or None when the
@@ -159,53 +174,85 @@ class _Layer:
             roles += [d.wp, rows_b | (int(d.flip) << 1), int(d.taps)]
         return _lib.F16PairDesc(w.data_ptr(), A, Bd, self.R, self.R, roles[0], roles[1], roles[2], roles[3], roles[4], roles[5], None, 0, 0)
 
-    def pack_descs6(self):
+    def _desc32(self, role):
         w = self.mod.weight
-        out = [_lib.F16PackDesc(w.data_ptr(), self.wp6_fwd.data_ptr(), self.K, self.C, self.R, self.R, 0, self.taps)]
-        if self.need_dgrad:       # the input-gradient of a stride-1 convolution is a convolution with the mirrored, transposed weight
-            out.append(_lib.F16PackDesc(w.data_ptr(), self.wp6_dgrad.data_ptr(), self.C, self.K, self.R, self.R, 1, 0))
-        return out
+        conv = self.kind == "conv"
+        if role == 0:
+            return _lib.PackDesc(w.data_ptr(), self.wp_fwd.data_ptr(), self.K, self.C, self.R, self.R,
+                                 F.PACK_CONV_FWD if conv else F.PACK_DECONV_FWD, self.masked)
+        return _lib.PackDesc(w.data_ptr(), self.wp_dgrad.data_ptr(), self.K, self.C, self.R, self.R,
+                             F.PACK_CONV_DGRAD if conv else F.PACK_DECONV_DGRAD, (1 | (self.masked & 4)) if self.masked else 0)
 
-    def fwd6(self, xp, act=F.ACT_NONE, out=None, planes=False):
-        """-> (fp32 output, planes output or None); `xp` a F16Planes (possibly a channel view)"""
-        return F.conv2d_f16x3_gen(xp, self.wp6_fwd, self.mod.bias, self.K, self.R, self.R, self.stride, self.pad,
-                                   epi=F.GEN_EPI_LRELU if act == F.ACT_LRELU else F.GEN_EPI_BIAS, out=out, want_planes=planes, taps=self.taps)
+    # ---- the three operations of the schedule; each picks its kernel from `faces` / the route flags and nothing else -----------------
+    def forward(self, a, act=F.ACT_NONE, out=None, planes=False):
+        """a: _Act -> _Act of the (activated) output; `out` may be a channel slice of a wider NHWC buffer; planes: the fp16
+        kernels write the output's planes next to the fp32 copy (the fp32 kernels cannot: the consumer splits)"""
+        self.eng.ensure_packed()
+        face, m = self.faces[0], self.mod
+        epi = F.GEN_EPI_LRELU if act == F.ACT_LRELU else F.GEN_EPI_BIAS
+        if face.kind == "gen":
+            return _Act(*F.conv2d_f16x3_gen(a.planes(), self.wp6_fwd, m.bias, self.K, self.R, self.R, self.stride, self.pad,
+                                            epi=epi, out=out, want_planes=planes, taps=self.taps))
+        if face.kind == "phases":         # a ConvTranspose2d over its four sub-pixel phases, one launch
+            return _Act(*F.tconv2d_f16x3(a.planes(), self.wp6_fwd, m.bias, self.K, self.R, epi=epi, out=out, want_planes=planes))
+        self.eng._wait_fwd32_packs()
+        if self.kind == "conv":
+            if self.masked and not self.masked & 4:
+                act |= F.CONV_MASKED_A            # the masked taps (type A) are zeros: skip them
+            return _Act(F.conv2d_fwd(a.x, self.wp_fwd, m.bias, self.K, self.R, self.R, self.stride, self.pad, act, out=out))
+        return _Act(F.deconv2d_fwd(a.x, self.wp_fwd, m.bias, self.K, self.R, self.R, self.stride, self.pad, self.opad, act, out=out))
 
-    def dgrad6(self, dyp, xact=None, planes=False):
-        """-> (dx fp32, dx planes or None); xact: the activated input of this layer (leaky-ReLU derivative folded in)"""
-        return F.conv2d_f16x3_gen(dyp, self.wp6_dgrad, None, self.C, self.R, self.R, 1, self.pad,
-                                   epi=F.GEN_EPI_DACT if xact is not None else F.GEN_EPI_BIAS, z=xact, want_planes=planes)
+    def fwd(self, x, act=F.ACT_NONE, out=None):
+        """fp32 tensor in, fp32 tensor out: callers outside the training schedule (codec.py)"""
+        return self.forward(_Act(x), act, out=out).x
 
-    def dgrad6s(self, dyp, xact=None, planes=False):
-        """input gradient of a ConvTranspose2d = the strided convolution of dy with the stored weight (fx3s)"""
-        return F.conv2d_f16x3_gen(dyp, self.wp6_dgrad, None, self.C, self.R, self.R, self.stride, self.pad,
-                                   epi=F.GEN_EPI_DACT if xact is not None else F.GEN_EPI_BIAS, z=xact, want_planes=planes)
+    def input_grad(self, dy, xact=None, planes=False, x_shape=None):
+        """dy: _Act -> _Act of the gradient of the layer's input; xact: the activated input (its leaky-ReLU derivative is folded
+        in); x_shape: the input's shape where there is no xact (only the fp32 kernels ask)"""
+        face = self.faces[1]
+        epi = F.GEN_EPI_DACT if xact is not None else F.GEN_EPI_BIAS
+        if face.kind == "gen":            # stride 1: the mirrored weight; a ConvTranspose2d: the strided convolution of dy with the stored weight
+            return _Act(*F.conv2d_f16x3_gen(dy.planes(), self.wp6_dgrad, None, self.C, self.R, self.R, self.stride, self.pad,
+                                            epi=epi, z=xact, want_planes=planes))
+        if face.kind == "phases":         # a strided Conv2d: the transposed face
+            return _Act(*F.tconv2d_f16x3(dy.planes(), self.wp6_dgrad, None, self.C, self.R, epi=epi, z=xact, want_planes=planes,
+                                         fine_hw=tuple(xact.shape[2:]) if xact is not None else None))
+        x_shape = xact.shape if xact is not None else x_shape
+        if self.kind == "conv":
+            return _Act(F.conv2d_dgrad(dy.x, self.wp_dgrad, x_shape, self.K, self.R, self.R, self.stride, self.pad, xact=xact))
+        return _Act(F.deconv2d_dgrad(dy.x, self.wp_dgrad, x_shape, self.K, self.R, self.R, self.stride, self.pad, self.opad, xact=xact))
 
-    def fwd6t(self, xp, act=F.ACT_NONE, planes=False):
-        """forward of a ConvTranspose2d on the fp16 kernel (four sub-pixel phases, one launch) -> (fp32, planes or None)"""
-        return F.tconv2d_f16x3(xp, self.wp6_fwd, self.mod.bias, self.K, self.R,
-                               epi=F.GEN_EPI_LRELU if act == F.ACT_LRELU else F.GEN_EPI_BIAS, want_planes=planes)
+    def reads_dy_planes(self, x):
+        """whether the gradient of this layer's output is wanted as planes too: the input gradient reads them, or the weight gradient
+        of a chain's first layer does next to the planes of its input `x`"""
+        return self.faces[1].kind != "f32" if self.faces[1] is not None else (self.wg3 and x.p is not None)
 
-    def dgrad6t(self, dyp, xact=None, planes=False):
-        """input gradient of a strided Conv2d = the transposed face, leaky-ReLU derivative of the layer's input folded in"""
-        return F.tconv2d_f16x3(dyp, self.wp6_dgrad, None, self.C, self.R, epi=F.GEN_EPI_DACT if xact is not None else F.GEN_EPI_BIAS,
-                               z=xact, want_planes=planes, fine_hw=tuple(xact.shape[2:]) if xact is not None else None)
-
-    def wgrad_t(self, fine_p, coarse_p, dy):
-        """weight + bias gradient of a stride-2 layer from planes: `fine_p` the fine-grid operand (a Conv2d's input, a
-        ConvTranspose2d's output gradient), `coarse_p` the coarse-grid one; dy: the fp32 output gradient (bias column sums of
-        the transposed layer).  On the weight-gradient stream like every other weight gradient."""
-        side = self.eng.side_stream(dy.device, self.lane)
-        if side is not None:
-            F.stream_wait(side, F.cur_stream(dy.device))
-            with F.on_stream(side):
-                self._wgrad_t(fine_p, coarse_p, dy)
-            for t in (fine_p.data, coarse_p.data, dy):
-                t.record_stream(side)
+    def weight_grad(self, x, dy):
+        """Weight + bias gradient from the layer's input `x` and output gradient `dy` (_Act): packed slabs now, StemEngine.unpack_all()
+        / _group_ready turn every layer's slabs into .grad tensors with one launch.  A stride-1 layer with `wg3` takes the fp16 kernel
+        when both operands have planes already -- they do whenever its two faces run on the fp16 kernels -- and a chain's first layer
+        (no input gradient) when one has: the other is split here, on the compute stream, measuring its own maximum.  Runs on the
+        engine's weight-gradient stream (nothing on the dgrad chain consumes it), ordered after everything the compute stream has
+        queued so far."""
+        at_hand = (x.p is not None) + (dy.p is not None)
+        if self.fx3t:                     # fine-grid operand first: a Conv2d's input, a ConvTranspose2d's output gradient
+            fn, args = self._wgrad_t, ((x.planes(), dy.planes()) if self.kind == "conv" else (dy.planes(), x.planes())) + (dy.x,)
+        elif self.wg3 and at_hand >= (2 if self.need_dgrad else 1):
+            fn, args = self._wgrad3, (x.planes(record=False), dy.planes(record=False), dy.x)
         else:
-            self._wgrad_t(fine_p, coarse_p, dy)
+            fn, args = self._wgrad, (x.x, dy.x)
+        side = self.eng.side_stream(dy.x.device, self.lane)
+        if side is None:
+            return fn(*args)
+        F.stream_wait(side, F.cur_stream(dy.x.device))
+        with F.on_stream(side):
+            fn(*args)
+        for t in args:
+            (t.data if isinstance(t, F.F16Planes) else t).record_stream(side)
 
     def _wgrad_t(self, fine_p, coarse_p, dy):
+        """a stride-2 layer from planes: `fine_p` the fine-grid operand, `coarse_p` the coarse-grid one; dy: the fp32 output
+        gradient (bias column sums of the transposed layer)"""
         conv = self.kind == "conv"
         Kk = self.K if conv else self.C                  # rows of the slabs = channels of the coarse operand
         key = ("fp16t",) + tuple(fine_p.shape)
@@ -224,27 +271,6 @@ class _Layer:
             F.bias_grad(dy, gb, accumulate=self.eng.accumulate_grads)
         self.pending = (dwp, splits)
 
-    def wg3_eligible(self):
-        """weight gradient on csrc/wgrad_f16x3.hip: stride-1 convolutions (all taps are produced, as autograd does for the
-        masked context convolution too)"""
-        return (self.kind == "conv" and self.stride == 1 and self.C % 32 == 0 and self.K % 32 == 0 and self.R % 2 == 1
-                and self.R * self.R <= 25 and self.pad == self.R // 2)
-
-    def wgrad_any(self, x, dy, xp=None, dyp=None):
-        """weight + bias gradient from the planes operands when this layer runs its weight gradient on the fp16 kernel and both
-        are at hand, else from the fp32 tensors"""
-        if not (self.wg3 and xp is not None and dyp is not None):
-            return self.wgrad(x, dy)
-        side = self.eng.side_stream(dy.device, self.lane)
-        if side is not None:
-            F.stream_wait(side, F.cur_stream(dy.device))
-            with F.on_stream(side):
-                self._wgrad3(xp, dyp, dy)
-            for t in (xp.data, dyp.data, dy):
-                t.record_stream(side)
-        else:
-            self._wgrad3(xp, dyp, dy)
-
     def _wgrad3(self, xp, dyp, dy):
         key = ("fp16",) + tuple(xp.shape)
         if key not in self._slabs:
@@ -256,52 +282,6 @@ class _Layer:
         self.pending_bias = F.conv2d_wgrad_f16x3(xp, dyp, self.K, self.R, self.R, self.pad, dwp, splits, db=gb, bias_part=bpart,
                                                  accumulate_db=self.eng.accumulate_grads, defer_bias=True)
         self.pending = (dwp, splits)
-
-    def _desc32(self, role):
-        w = self.mod.weight
-        conv = self.kind == "conv"
-        if role == 0:
-            return _lib.PackDesc(w.data_ptr(), self.wp_fwd.data_ptr(), self.K, self.C, self.R, self.R,
-                                 F.PACK_CONV_FWD if conv else F.PACK_DECONV_FWD, self.masked)
-        return _lib.PackDesc(w.data_ptr(), self.wp_dgrad.data_ptr(), self.K, self.C, self.R, self.R,
-                             F.PACK_CONV_DGRAD if conv else F.PACK_DECONV_DGRAD, (1 | (self.masked & 4)) if self.masked else 0)
-
-    def pack_descs(self):
-        return [self._desc32(0)] + ([self._desc32(1)] if self.need_dgrad else [])
-
-    def fwd(self, x, act=F.ACT_NONE, out=None):
-        self.eng.ensure_packed()
-        if self.fx3 or (self.fx3s and self.kind == "conv"):          # callers outside the training schedule (codec.py) hand over fp32 tensors
-            return self.fwd6(F.F16Planes.split(x), act, out=out)[0]
-        if self.fx3t and self.kind == "deconv":
-            y = self.fwd6t(F.F16Planes.split(x), act)[0]
-            return y if out is None else F.copy_channels(y, out)
-        m = self.mod
-        self.eng._wait_fwd32_packs()
-        if self.kind == "conv":
-            if self.masked and not self.masked & 4:
-                act |= F.CONV_MASKED_A            # the masked taps (type A) are zeros: skip them
-            return F.conv2d_fwd(x, self.wp_fwd, m.bias, self.K, self.R, self.R, self.stride, self.pad, act, out=out)
-        return F.deconv2d_fwd(x, self.wp_fwd, m.bias, self.K, self.R, self.R, self.stride, self.pad, self.opad, act, out=out)
-
-    def dgrad(self, dy, x_shape, xact=None):
-        if self.kind == "conv":
-            return F.conv2d_dgrad(dy, self.wp_dgrad, x_shape, self.K, self.R, self.R, self.stride, self.pad, xact=xact)
-        return F.deconv2d_dgrad(dy, self.wp_dgrad, x_shape, self.K, self.R, self.R, self.stride, self.pad, self.opad, xact=xact)
-
-    def wgrad(self, x, dy):
-        """packed slabs now, bias gradient straight into .grad; StemEngine.unpack_all() turns every layer's
-        slabs into .grad tensors with one launch.  Runs on the engine's weight-gradient stream (nothing on the dgrad
-        chain consumes it), ordered after everything the compute stream has queued so far."""
-        side = self.eng.side_stream(x.device, self.lane)
-        if side is not None:
-            F.stream_wait(side, F.cur_stream(x.device))
-            with F.on_stream(side):
-                self._wgrad(x, dy)
-            x.record_stream(side)
-            dy.record_stream(side)
-        else:
-            self._wgrad(x, dy)
 
     def _wgrad(self, x, dy):
         m = self.mod
@@ -331,21 +311,16 @@ class _Layer:
                                (F.UNPACK_DECONV if self.kind == "deconv" else 0) | (F.UNPACK_ACCUMULATE if self.eng.accumulate_grads else 0))
 
 
-def _attach_block_maxima(descs, maxima, flat):
-    """point every fp16 pack descriptor whose weight lies inside the flat parameter buffer at the optimiser's chunk maxima"""
-    ch = F.adam_chunk()
-    base, n = flat.data_ptr(), flat.numel()
-    for d in descs:
-        off = (d.w - base) // 4
-        numel = d.N * d.C * d.R * d.S
-        if (d.w - base) % 4 == 0 and 0 <= off and off + numel <= n:
-            d.bmax, d.b0 = maxima.data_ptr(), off // ch
-            d.nb = (off + numel - 1) // ch - d.b0 + 1
-
-
-def _qp(rec):
-    """address of a scale record tensor, or None"""
-    return None if rec is None else rec.data_ptr()
+def _attach_block_maxima(d, numel, maxima, flat, ch=None):
+    """point one fp16 pack descriptor (single or pair; numel: the elements of its weight) at the optimiser's chunk maxima that cover
+    the weight inside the flat parameter buffer `flat`.  -> False, the descriptor untouched, when the weight lies outside the buffer"""
+    off = (d.w - flat.data_ptr()) // 4
+    if (d.w - flat.data_ptr()) % 4 or off < 0 or off + numel > flat.numel():
+        return False
+    ch = ch or F.adam_chunk()
+    d.bmax, d.b0 = maxima.data_ptr(), off // ch
+    d.nb = (off + numel - 1) // ch - d.b0 + 1
+    return True
 
 
 def _grad_of(p):
@@ -374,7 +349,6 @@ class StemEngine:
         for first in [self.HE[0]] + ([self.TPM[0]] if has_tpm else []) + ([self.CTX] if has_spm else []):
             first.need_dgrad = False
         self._pack_key = None
-        self._pack_descs = None
         self._side = {}
         self._checked = False
         self._dgrad_pack_event = None
@@ -420,9 +394,10 @@ class StemEngine:
                 for l in group:
                     l.fx3 = False
         for l in self.layers:
-            # weight gradients take whatever planes the forward / input-gradient route left behind (wgrad_any falls back to the
-            # fp32 kernel when there are none), so they follow the layer's own eligibility
+            # weight gradients take whatever planes the forward / input-gradient route left behind (_Layer.weight_grad falls back to
+            # the fp32 kernel when there are none), so they follow the layer's own eligibility
             l.wg3 = self.use_fx3 and self.use_wg3 and l.wg3_eligible()
+            l.set_faces()
 
     #: forward and input-gradient of the stride-1 layers (TPM, HE.0, HD.4, EPM) on the fp16 matrix cores: three fp16 products per fp32 product on operands split into two scaled fp16 planes, ~2^-21 relative per product (tests: 1e-4 gates; measured 0.4-1.6e-6 of max per layer against fp64)
     #: (three fp16 MFMAs per fp32 product, csrc/conv_f16x3.hip); STEM_ENGINE_F16X3=0 keeps every layer on the fp32-MFMA kernels
@@ -445,8 +420,6 @@ class StemEngine:
     #: and overlap the latency-bound parts of the dgrad chain; set False to keep everything on the compute stream
     overlap_wgrad = _Switch("engine_overlap")
 
-    #: (a second weight-gradient stream for the hyper path, the slab sums on a stream of their own and the context model on a third
-    #: forward stream were switches until round 4: +0.8, +0.6 and +1.6 ms per bench step -- removed)
     #: the next forward's weight packing is split: forward-role copies on the compute stream (the forward waits for them), the
     #: input-gradient copies on a weight-gradient stream (only backward waits): 22.48-22.62 ms against 22.67-22.82 ms per bench
     #: step; STEM_ENGINE_SPLIT_PACK=0: one launch each as before
@@ -484,20 +457,15 @@ class StemEngine:
         maximum launch.  Only meaningful in the call that directly follows that optimiser step."""
         if self._checked:
             return
-        key = tuple((_layers.weight_epoch(l.mod.weight), l.mod.weight._version, l.mod.weight.data_ptr()) for l in self.layers)
-        if key == self._pack_key:
+        if self._weights_key() == self._pack_key:
             return
-        stale = False
-        for l in self.layers:
-            have = l.wp_fwd if (l.fx3s or not l.fx3) else l.wp6_fwd
-            stale = stale or have is None or have.device != l.mod.weight.device
-        if stale:
+        have = [l.wp_fwd if l.faces[0].kind == "f32" else l.wp6_fwd for l in self.layers]        # the forward face's copy of each layer
+        if any(h is None or h.device != l.mod.weight.device for h, l in zip(have, self.layers)):
             for l in self.layers:
                 l.alloc_packs(l.mod.weight.device)
-            self._pack_descs = None
         dev = self.layers[0].mod.weight.device
         if block_max is not None and self.pack_pair and self._pack_pairs(*block_max):
-            self._pack_key = tuple((_layers.weight_epoch(l.mod.weight), l.mod.weight._version, l.mod.weight.data_ptr()) for l in self.layers)
+            self._pack_key = self._weights_key()
             return
         side = self.side_stream(dev) if self.split_pack and not torch.cuda.is_current_stream_capturing() else None
         roles = ((0, 1), (1, 2)) if side is not None else ((0, 2),)
@@ -510,7 +478,9 @@ class StemEngine:
                 descs = [d for a, _ in both for d in a]
                 descs6 = [d for _, b in both for d in b]
                 if descs6 and block_max is not None:
-                    _attach_block_maxima(descs6, *block_max)
+                    ch = F.adam_chunk()
+                    for d in descs6:
+                        _attach_block_maxima(d, d.N * d.C * d.R * d.S, *block_max, ch)
                 if descs6:                        # the forward's first kernels (HE.0, TPM.0, the context model) wait for these
                     F.pack_weights_f16x2_multi((_lib.F16PackDesc * len(descs6))(*descs6))
                 # the fp32 copies of the forward role (the transposed hyper-decoder layers: consumed on the hyper branch, half a
@@ -531,7 +501,11 @@ class StemEngine:
                     self._dgrad_pack_event = self._events.setdefault("dgrad", torch.cuda.Event())
                     F.event_record(self._dgrad_pack_event, side)
         # masked == 2 zeroed taps of the context weight in place: refresh its version in the key
-        self._pack_key = tuple((_layers.weight_epoch(l.mod.weight), l.mod.weight._version, l.mod.weight.data_ptr()) for l in self.layers)
+        self._pack_key = self._weights_key()
+
+    def _weights_key(self):
+        """changes whenever a weight of the schedule was written or moved: the packed copies are then stale"""
+        return tuple((_layers.weight_epoch(l.mod.weight), l.mod.weight._version, l.mod.weight.data_ptr()) for l in self.layers)
 
     #: after an optimiser pass that left chunk maxima, both images of every layer come from ONE launch that reads each weight once
     #: (F.pack_weights_f16x2_pair_multi) on the compute stream, instead of one launch per role (the input-gradient role on the
@@ -545,14 +519,8 @@ class StemEngine:
         if any(d is None for d in descs):
             return False
         ch = F.adam_chunk()
-        base, n = flat.data_ptr(), flat.numel()
-        for d in descs:
-            off = (d.w - base) // 4
-            numel = d.A * d.B * d.R * d.S
-            if (d.w - base) % 4 or off < 0 or off + numel > n:
-                return False
-            d.bmax, d.b0 = maxima.data_ptr(), off // ch
-            d.nb = (off + numel - 1) // ch - d.b0 + 1
+        if not all(_attach_block_maxima(d, d.A * d.B * d.R * d.S, maxima, flat, ch) for d in descs):
+            return False
         F.pack_weights_f16x2_pair_multi((_lib.F16PairDesc * len(descs))(*descs))
         self._dgrad_pack_event = None
         return True
@@ -620,6 +588,34 @@ class StemEngine:
         finally:
             self._checked = False
 
+    @staticmethod
+    def _chain_forward(layers, a, out=None):
+        """a chain of convolutions with leaky ReLUs between them over the _Act `a`; the last one writes `out` (a channel slice of
+        the EPM input) if given.  -> [a, output of layer 0, ...]: an epilogue writes planes when the next layer reads them"""
+        acts = [a]
+        for i, l in enumerate(layers):
+            nxt = layers[i + 1] if i + 1 < len(layers) else None
+            acts.append(l.forward(acts[-1], F.ACT_LRELU if nxt else F.ACT_NONE, out=None if nxt else out,
+                                  planes=nxt is not None and nxt.faces[0].kind != "f32"))
+        return acts
+
+    @staticmethod
+    def _chain_backward(layers, xs, dy, planes=False):
+        """from the last layer to the first: weight gradient of layer i from its input xs[i] and `dy`, then `dy` through layer i
+        (the leaky-ReLU derivative at xs[i] folded in for i > 0).  -> the gradient of xs[0], with planes if `planes` and the route
+        can write them; None when the first layer has no input gradient.  Where the input gradient reads planes of dy they are made
+        before the weight gradient (with dy's scale record), so that both read the same ones."""
+        for i in range(len(layers) - 1, -1, -1):
+            l = layers[i]
+            if l.faces[1] is not None and l.faces[1].kind != "f32":
+                dy.planes()
+            l.weight_grad(xs[i], dy)
+            if l.faces[1] is None:
+                return None
+            dy = l.input_grad(dy, xact=xs[i].x if i else None, x_shape=xs[i].x.shape,
+                              planes=layers[i - 1].reads_dy_planes(xs[i - 1]) if i else planes)
+        return dy
+
     def _forward(self, y_cur, y_cond, training: bool, rate_coef=None):
         m = self.m
         yc, yd = F.to_nhwc(y_cur.detach()), F.to_nhwc(y_cond.detach())
@@ -630,7 +626,7 @@ class StemEngine:
         assert not fused or training, "the fused glue is the TRAINING forward"
         k = {}
         target = t_hat = y_hat = None
-        rec = self._rec = {}    # scale records left by the producers of fp32 tensors that are split for the fp16 kernels below
+        rec = {}    # scale records left by the producers of fp32 tensors that are split for the fp16 kernels below
         if fused:
             # one kernel: he_in = [y_cur | y_cond], target, t_hat = target + noise, y_hat = t_hat (+ y_cond); it also records
             # max |y_cur|, |y_cond| and max |t_hat| per workgroup: the splits of he_in, y_cond and t_hat need no maximum pass
@@ -649,57 +645,39 @@ class StemEngine:
         main = F.cur_stream(dev) if bs is not None else None
         if bs is not None:
             F.stream_wait(bs, main)
-        pl = {}             # planes copies of activations, kept for the weight gradients
-        split = F.F16Planes.split
-        tp0 = tp2 = None
+        acts = k["acts"] = {}             # every activation backward reads, with the planes the forward made of it
+        acts["he_in"] = _Act(he_in, rec=rec.get("in"))
+        acts["yd"] = _Act(yd, rec=rec.get("in"))                     # max(|y_cur|, |y_cond|) bounds y_cond
         ctx_split_done = None
-        if fused and self.has_spm and self.CTX.fx3 and rec.get("t_hat") is not None and self.side_stream(dev) is not None:
-            # t_hat exists since the prologue and the context model runs behind the TPM chain: its planes are made meanwhile on the
-            # weight-gradient stream, which has nothing to do during the forward (one launch less between TPM.4 and the context model)
-            side = self.side_stream(dev)
-            F.stream_wait(side, F.cur_stream(dev))
-            with F.on_stream(side):
-                pl["t_hat"] = split(t_hat, src_q=_qp(rec.get("t_hat")))
-                ctx_split_done = self._events.setdefault("ctx_split", torch.cuda.Event())
-                F.event_record(ctx_split_done, side)
-            t_hat.record_stream(side)
+        if self.has_spm and fused:
+            acts["t_hat"] = _Act(t_hat, rec=rec.get("t_hat"))
+            if self.CTX.fx3 and rec.get("t_hat") is not None and self.side_stream(dev) is not None:
+                # t_hat exists since the prologue and the context model runs behind the TPM chain: its planes are made meanwhile on the
+                # weight-gradient stream, which has nothing to do during the forward (one launch less between TPM.4 and the context model)
+                side = self.side_stream(dev)
+                F.stream_wait(side, F.cur_stream(dev))
+                with F.on_stream(side):
+                    acts["t_hat"].planes()
+                    ctx_split_done = self._events.setdefault("ctx_split", torch.cuda.Event())
+                    F.event_record(ctx_split_done, side)
+                t_hat.record_stream(side)
 
         if fused and self.HE[0].fx3 and self.has_tpm and self.TPM[0].fx3 and Cin % 32 == 0 and rec.get("in") is not None:
             # he_in = [y_cur | y_cond] and the TPM chain's input y_cond share ONE planes tensor (same record: max(|y_cur|, |y_cond|)):
             # one split on the compute stream, the TPM chain reads its second half as a channel view, the hyper branch (which waits
             # for this stream anyway) the whole -- a launch less, the same values
-            pl["he_in"] = split(he_in, src_q=_qp(rec.get("in")))
-            pl["yd"] = pl["he_in"].channels(Cin, 2 * Cin)
+            acts["yd"] = _Act(yd, acts["he_in"].planes().channels(Cin, 2 * Cin))
             if bs is not None:
                 F.stream_wait(bs, main)
 
         # the TPM chain is enqueued ahead of the hyper branch's ~14 launches: it is the forward's critical path
-        if self.has_tpm and self.TPM[0].fx3:
-            # planes travel from layer to layer (written by the producing epilogue next to the fp32 copy backward needs)
-            if "yd" not in pl:
-                pl["yd"] = split(yd, src_q=_qp(rec.get("in")))       # max(|y_cur|, |y_cond|) bounds y_cond
-            tp0, pl["tp0"] = self.TPM[0].fwd6(pl["yd"], F.ACT_LRELU, planes=True)
-            tp2, pl["tp2"] = self.TPM[1].fwd6(pl["tp0"], F.ACT_LRELU, planes=True)
-            self.TPM[2].fwd6(pl["tp2"], out=epm_in[:, o_tp:o_tp + P])
-        elif self.has_tpm:
-            tp0 = self.TPM[0].fwd(yd, F.ACT_LRELU)
-            tp2 = self.TPM[1].fwd(tp0, F.ACT_LRELU)
-            self.TPM[2].fwd(tp2, out=epm_in[:, o_tp:o_tp + P])
+        tp0 = tp2 = None
+        if self.has_tpm:
+            _, acts["tp0"], acts["tp2"], _ = self._chain_forward(self.TPM, acts["yd"], out=epm_in[:, o_tp:o_tp + P])
+            tp0, tp2 = acts["tp0"].x, acts["tp2"].x
         with F.on_stream(bs):
-            if self.HE[0].fx3:
-                if "he_in" not in pl:
-                    pl["he_in"] = split(he_in, src_q=_qp(rec.get("in")))
-                he0, he0p = self.HE[0].fwd6(pl["he_in"], F.ACT_LRELU, planes=self.HE[1].fx3s)
-            else:
-                he0 = self.HE[0].fwd(he_in, F.ACT_LRELU)
-            if self.HE[1].fx3s:           # the strided forwards on the general fp16 kernel, planes handed down
-                he2, he2p = self.HE[1].fwd6(he0p, F.ACT_LRELU, planes=self.HE[2].fx3s)
-                z = self.HE[2].fwd6(he2p)[0] if self.HE[2].fx3s else self.HE[2].fwd(he2)
-                if self.HE[1].fx3t:       # the weight gradients read them again
-                    pl["he0"], pl["he2"] = he0p, he2p
-            else:
-                he2 = self.HE[1].fwd(he0, F.ACT_LRELU)
-                z = self.HE[2].fwd(he2)
+            _, acts["he0"], acts["he2"], z = self._chain_forward(self.HE, acts["he_in"])
+            z = z.x
             pack = F.eb_pack(eb._tensors14())
             if fused:
                 if self.HD[0].fx3t and self.use_records:         # the kernel leaves max |z_hat| for the split below: no maximum pass
@@ -712,41 +690,23 @@ class StemEngine:
             else:
                 z_hat, lik_z = F.eb_forward(z, pack, medians=eb._medians_vec())
             # hyper decoder; its last conv writes the `hp` slice of the EPM input
-            if self.HD[0].fx3t:          # the transposed layers on the fp16 kernel: planes in, planes out, no maximum / split passes
-                pl["z_hat"] = split(z_hat, src_q=_qp(rec.get("z_hat")))
-                hd0, pl["hd0"] = self.HD[0].fwd6t(pl["z_hat"], F.ACT_LRELU, planes=True)
-                hd2, pl["hd2"] = self.HD[1].fwd6t(pl["hd0"], F.ACT_LRELU, planes=True)
-                self.HD[2].fwd6(pl["hd2"], out=epm_in[:, o_hp:o_hp + P])
-            else:
-                hd0 = self.HD[0].fwd(z_hat, F.ACT_LRELU)
-                hd2 = self.HD[1].fwd(hd0, F.ACT_LRELU)
-            if self.HD[0].fx3t:
-                pass
-            elif self.HD[2].fx3:
-                pl["hd2"] = split(hd2)
-                self.HD[2].fwd6(pl["hd2"], out=epm_in[:, o_hp:o_hp + P])
-            else:
-                self.HD[2].fwd(hd2, out=epm_in[:, o_hp:o_hp + P])
+            acts["z_hat"], acts["hd0"], acts["hd2"], _ = self._chain_forward(self.HD, _Act(z_hat, rec=rec.get("z_hat")), out=epm_in[:, o_hp:o_hp + P])
         if not fused:
             target = F.sub(yc, yd) if self.residual else (yc if F.nhwc_ld(yc) == Cin else F.copy_channels(yc, F.empty_nhwc(B, Cin, H, W, dev)))
         if self.has_spm:
             # gaussian_conditional.quantize(target, "noise" | "dequantize") with no means (:570-572, :853-855)
             if not fused:
                 t_hat = F.add(target, gc._noise_like(target)) if training else F.round_(target)
+                acts["t_hat"] = _Act(t_hat)
             if ctx_split_done is not None:
                 F.event_wait(F.cur_stream(dev), ctx_split_done)
-            self._ctx_forward(t_hat, epm_in[:, o_ctx:o_ctx + P], pl)
+            # context_prediction(t_hat) -> its channel slice of the EPM input (spatiotemporalpriors.py:857): on the fp16 kernel over
+            # the live taps of the mask (the planes of t_hat stay for the weight gradient), else on igemm.hip's masked form
+            self.CTX.forward(acts["t_hat"], out=epm_in[:, o_ctx:o_ctx + P])
         if bs is not None:
             F.stream_wait(main, bs)
-        if self.EPM[0].fx3:
-            pl["epm_in"] = split(epm_in)
-            e0, pl["e0"] = self.EPM[0].fwd6(pl["epm_in"], F.ACT_LRELU, planes=True)
-            e2, pl["e2"] = self.EPM[1].fwd6(pl["e0"], F.ACT_LRELU, planes=True)
-            gp = self.EPM[2].fwd6(pl["e2"])[0]                     # [B, 2*Cin, H, W] = scales | means
-        else:
-            e0 = self.EPM[0].fwd(epm_in, F.ACT_LRELU)
-            e2 = self.EPM[1].fwd(e0, F.ACT_LRELU)
-            gp = self.EPM[2].fwd(e2)                               # [B, 2*Cin, H, W] = scales | means
+        acts["epm_in"], acts["e0"], acts["e2"], gp = self._chain_forward(self.EPM, _Act(epm_in))
+        gp = gp.x                                                    # [B, 2*Cin, H, W] = scales | means
         scales, means = gp[:, :Cin], gp[:, Cin:]
         if fused:
             # the GaussianConditional's backward in the same launch (d loss / d likelihood = coef / lik is known here): backward()
@@ -766,8 +726,9 @@ class StemEngine:
                 y_hat = F.add(t_hat, yd if F.nhwc_ld(yd) == Cin else F.copy_channels(yd, F.empty_nhwc(B, Cin, H, W, dev))) if self.residual else t_hat
             else:
                 y_hat = gc_out
-        k.update(he_in=he_in, he0=he0, he2=he2, z_hat=z_hat, pack=pack, hd0=hd0, hd2=hd2, epm_in=epm_in, tp0=tp0, tp2=tp2,
-                 yd=yd, t_hat=t_hat, e0=e0, e2=e2, gp=gp, gc_out=gc_out, offs=(o_tp, o_hp, o_ctx), P=P, Cin=Cin, planes=pl)
+        k.update(he_in=he_in, he0=acts["he0"].x, he2=acts["he2"].x, z_hat=z_hat, pack=pack, hd0=acts["hd0"].x, hd2=acts["hd2"].x,
+                 epm_in=epm_in, tp0=tp0, tp2=tp2, yd=yd, t_hat=t_hat, e0=acts["e0"].x, e2=acts["e2"].x, gp=gp, gc_out=gc_out,
+                 offs=(o_tp, o_hp, o_ctx), P=P, Cin=Cin)
         return y_hat, lik_y, lik_z, k
 
     # -------------------------------------------------------------------------------------------
@@ -780,7 +741,7 @@ class StemEngine:
         gc = m.gaussian_conditional
         Cin, P = k["Cin"], k["P"]
         o_tp, o_hp, o_ctx = k["offs"]
-        gp = k["gp"]
+        gp, acts = k["gp"], k["acts"]
         B, _, H, W = gp.shape
         self._wait_dgrad_packs()
         if k.get("dgp") is not None and dlik_y is k.get("dlik_y"):          # computed by the fused forward glue
@@ -789,24 +750,8 @@ class StemEngine:
             dgp = F.empty_nhwc(B, 2 * Cin, H, W, gp.device)
             qg = F.gc_backward(k["gc_out"], gp[:, :Cin], gp[:, Cin:], dlik_y, dgp[:, :Cin], dgp[:, Cin:], dy=None,
                                scale_bound=gc._scale_bound, lik_bound=gc._lik_bound, record=self.EPM[0].fx3 and self.use_records)
-        # EPM (1x1 chain)
-        dprip = None
-        pl = k.get("planes", {})
-        if self.EPM[0].fx3:
-            dgpp = F.F16Planes.split(dgp, src_q=_qp(qg))
-            self.EPM[2].wgrad_any(k["e2"], dgp, pl.get("e2"), dgpp)
-            de2, de2p = self.EPM[2].dgrad6(dgpp, xact=k["e2"], planes=True)
-            self.EPM[1].wgrad_any(k["e0"], de2, pl.get("e0"), de2p)
-            de0, de0p = self.EPM[1].dgrad6(de2p, xact=k["e0"], planes=True)
-            self.EPM[0].wgrad_any(k["epm_in"], de0, pl.get("epm_in"), de0p)
-            dpri, dprip = self.EPM[0].dgrad6(de0p, planes=True)        # the prior branches read 32-aligned channel views of the planes
-        else:
-            self.EPM[2].wgrad(k["e2"], dgp)
-            de2 = self.EPM[2].dgrad(dgp, k["e2"].shape, xact=k["e2"])
-            self.EPM[1].wgrad(k["e0"], de2)
-            de0 = self.EPM[1].dgrad(de2, k["e0"].shape, xact=k["e0"])
-            self.EPM[0].wgrad(k["epm_in"], de0)
-            dpri = self.EPM[0].dgrad(de0, k["epm_in"].shape)
+        # EPM (1x1 chain); the prior branches read 32-aligned channel views of its input gradient (and of its planes)
+        dpri = self._chain_backward(self.EPM, [acts["epm_in"], acts["e0"], acts["e2"]], _Act(dgp, rec=qg), planes=True)
         self._group_ready(self.EPM, [])
         bs = self._branch(gp.device)
         main = F.cur_stream(gp.device)
@@ -816,11 +761,7 @@ class StemEngine:
             F.event_record(epm_done, main)
         # spatial prior: weight gradient of all 25 taps, no input gradient (its input is data + noise)
         if self.has_spm:
-            if self.CTX.wg3 and dprip is not None:
-                thp = pl.get("t_hat") or F.F16Planes.split(k["t_hat"])         # left by the forward when it ran on the fp16 kernel
-                self.CTX.wgrad_any(k["t_hat"], dpri[:, o_ctx:o_ctx + P], thp, dprip.channels(o_ctx, o_ctx + P))
-            else:
-                self.CTX.wgrad(k["t_hat"], dpri[:, o_ctx:o_ctx + P])
+            self._chain_backward([self.CTX], [acts["t_hat"]], dpri.channels(o_ctx, o_ctx + P))
             self._group_ready([self.CTX], [])
         if self.has_tpm:
             # with a hyper branch stream, the chain's weight gradients (~300 us of the ~900 us the weight-gradient stream carries per
@@ -828,90 +769,33 @@ class StemEngine:
             # weight-gradient stream finished last by ~250 us (profiles/r05_gantt_palone.txt).  lane -1 = "the stream backward runs on"
             for l in self.TPM:
                 l.lane = -1 if bs is not None else 0
-            dtp = dpri[:, o_tp:o_tp + P]
-            if self.TPM[2].fx3:
-                dtpp = dprip.channels(o_tp, o_tp + P) if dprip is not None else F.F16Planes.split(dtp)
-                self.TPM[2].wgrad_any(k["tp2"], dtp, pl.get("tp2"), dtpp)
-                d, dp = self.TPM[2].dgrad6(dtpp, xact=k["tp2"], planes=True)
-                self.TPM[1].wgrad_any(k["tp0"], d, pl.get("tp0"), dp)
-                d, dp = self.TPM[1].dgrad6(dp, xact=k["tp0"], planes=self.TPM[0].wg3)
-                self.TPM[0].wgrad_any(k["yd"], d, pl.get("yd"), dp)
-            else:
-                self.TPM[2].wgrad(k["tp2"], dtp)
-                d = self.TPM[2].dgrad(dtp, k["tp2"].shape, xact=k["tp2"])
-                self.TPM[1].wgrad(k["tp0"], d)
-                d = self.TPM[1].dgrad(d, k["tp0"].shape, xact=k["tp0"])
-                self.TPM[0].wgrad(k["yd"], d)
+            self._chain_backward(self.TPM, [acts["yd"], acts["tp0"], acts["tp2"]], dpri.channels(o_tp, o_tp + P))
             self._group_ready(self.TPM, [])
         if bs is None:
-            self._backward_hyper(k, dpri, dlik_z, dprip)
+            self._backward_hyper(k, dpri.channels(o_hp, o_hp + P), dlik_z)
         else:                              # hyper chain (HD -> bottleneck -> HE) on its own stream, enqueued behind the TPM chain
             F.event_wait(bs, epm_done)
             with F.on_stream(bs):
-                self._backward_hyper(k, dpri, dlik_z, dprip)
+                self._backward_hyper(k, dpri.channels(o_hp, o_hp + P), dlik_z)
             F.stream_wait(main, bs)
         self.join_side_stream()          # gradients are complete for whatever the compute stream does next
 
-    def _ctx_forward(self, t_hat, out, pl):
-        """context_prediction(t_hat) -> its channel slice of the EPM input (spatiotemporalpriors.py:857): on the fp16 kernel over
-        the live taps of the mask (the planes of t_hat stay for the weight gradient), else on igemm.hip's masked form"""
-        if self.CTX.fx3:
-            if "t_hat" not in pl:
-                pl["t_hat"] = F.F16Planes.split(t_hat, src_q=_qp(self._rec.get("t_hat")))
-            self.CTX.fwd6(pl["t_hat"], out=out)
-        else:
-            self.CTX.fwd(t_hat, out=out)
-
-    def _backward_hyper(self, k, dpri, dlik_z, dprip=None):
-        m = self.m
-        P = k["P"]
-        o_tp, o_hp, o_ctx = k["offs"]
+    def _backward_hyper(self, k, dhp, dlik_z):
+        """dhp: the gradient of the hyper decoder's slice of the EPM input (_Act)"""
+        acts = k["acts"]
         # hyper decoder
-        dhp = dpri[:, o_hp:o_hp + P]
-        pl = k.get("planes", {})
-        if self.HD[2].fx3:
-            dhpp = dprip.channels(o_hp, o_hp + P) if dprip is not None else F.F16Planes.split(dhp)
-            self.HD[2].wgrad_any(k["hd2"], dhp, pl.get("hd2"), dhpp)
-            d, dp = self.HD[2].dgrad6(dhpp, xact=k["hd2"], planes=self.HD[1].fx3s)
-        else:
-            self.HD[2].wgrad(k["hd2"], dhp)
-            d = self.HD[2].dgrad(dhp, k["hd2"].shape, xact=k["hd2"])
-        if self.HD[1].fx3t:
-            self.HD[1].wgrad_t(dp, pl["hd0"], d)
-        else:
-            self.HD[1].wgrad(k["hd0"], d)
-        if self.HD[1].fx3s:               # input gradients of the transposed layers = strided convolutions of dy, planes handed down
-            d, dp = self.HD[1].dgrad6s(dp, xact=k["hd0"], planes=self.HD[0].fx3s)
-        else:
-            d = self.HD[1].dgrad(d, k["hd0"].shape, xact=k["hd0"])
-        if self.HD[0].fx3t:
-            self.HD[0].wgrad_t(dp, pl["z_hat"], d)
-        else:
-            self.HD[0].wgrad(k["z_hat"], d)
-        dz_hat = self.HD[0].dgrad6s(dp)[0] if self.HD[0].fx3s else self.HD[0].dgrad(d, k["z_hat"].shape)
+        dz_hat = self._chain_backward(self.HD, [acts["z_hat"], acts["hd0"], acts["hd2"]], dhp).x
         # entropy bottleneck: d/dz = dz_hat + likelihood path; 58 parameter gradients per channel
-        eb = m.entropy_bottleneck
+        eb = self.m.entropy_bottleneck
         qdz = None
-        if self.HE[2].fx3t and self.use_records:
+        if self.HE[2].fx3t and self.use_records:       # the kernel leaves max |dz| for the split in front of the hyper encoder's backward
             dz, dpack, qdz = F.eb_backward(k["z_hat"], k["pack"], dlik_z, dzhat_in=dz_hat, bound=eb._lik_bound, record=True)
         else:
             dz, dpack = F.eb_backward(k["z_hat"], k["pack"], dlik_z, dzhat_in=dz_hat, bound=eb._lik_bound)
         F.eb_unpack_grads(dpack, [_grad_of(p) for p in eb._tensors14()], accumulate=self.accumulate_grads)
         self._group_ready(self.HD, eb._tensors14())
         # hyper encoder
-        if self.HE[2].fx3t:               # transposed faces (input gradients of the strided convolutions) and weight gradients on the fp16 kernels
-            dzp = F.F16Planes.split(dz, src_q=_qp(qdz))
-            self.HE[2].wgrad_t(pl["he2"], dzp, dz)
-            d, dp = self.HE[2].dgrad6t(dzp, xact=k["he2"], planes=True)
-            self.HE[1].wgrad_t(pl["he0"], dp, d)
-            d, dp = self.HE[1].dgrad6t(dp, xact=k["he0"], planes=self.HE[0].wg3 and "he_in" in pl)
-            self.HE[0].wgrad_any(k["he_in"], d, pl.get("he_in"), dp)
-        else:
-            self.HE[2].wgrad(k["he2"], dz)
-            d = self.HE[2].dgrad(dz, k["he2"].shape, xact=k["he2"])
-            self.HE[1].wgrad(k["he0"], d)
-            d = self.HE[1].dgrad(d, k["he0"].shape, xact=k["he0"])
-            self.HE[0].wgrad_any(k["he_in"], d, pl.get("he_in"), F.F16Planes.split(d) if self.HE[0].wg3 and "he_in" in pl else None)
+        self._chain_backward(self.HE, [acts["he_in"], acts["he0"], acts["he2"]], _Act(dz, rec=qdz))
         self._group_ready(self.HE, [])
 
 

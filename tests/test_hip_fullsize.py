@@ -513,7 +513,7 @@ def test_first_launch_on_fresh_workspaces_is_reproducible():
         eng = stem.engine()
         y_hat, lik_y, lik_z, k = eng.forward(y_cur, y_cond, True)
         torch.cuda.synchronize()
-        again, _ = eng.TPM[0].fwd6(k["planes"]["yd"], F.ACT_LRELU, planes=True)
+        again = eng.TPM[0].forward(k["acts"]["yd"], F.ACT_LRELU, planes=True).x      # from the very planes the forward read
         torch.cuda.synchronize()
         assert torch.equal(again, k["tp0"]), f"run {r}: TPM.0 inside the forward differs from its recomputation"
         runs.append({n: k[n].clone() for n in ("he0", "he2", "hd0", "hd2", "tp0", "tp2", "e0", "e2", "gp") if isinstance(k.get(n), torch.Tensor)}

@@ -25,13 +25,14 @@ for r in range(int(sys.argv[1]) if len(sys.argv) > 1 else 6):
     y_hat, lik_y, lik_z, k = eng.forward(y_cur, y_cond, True)
     torch.cuda.synchronize()
     snap = {n: k[n].clone() for n in ("he_in", "he0", "he2", "z_hat", "hd0", "hd2", "tp0", "tp2", "epm_in", "e0", "e2", "gp") if isinstance(k.get(n), torch.Tensor)}
-    for n, p in k["planes"].items():
-        snap["planes:" + n] = p.merge().clone()
-        snap["record:" + n] = torch.tensor(p.record())
+    for n, a in k["acts"].items():
+        if a.p is not None and a.p.dense:
+            snap["planes:" + n] = a.p.merge().clone()
+            snap["record:" + n] = torch.tensor(a.p.record())
     snap["lik_y"] = lik_y.clone()
     snap["wp:TPM.0"] = eng.TPM[0].wp6_fwd.clone()
     snap["bias:TPM.0"] = eng.TPM[0].mod.bias.detach().clone()
-    again, againp = eng.TPM[0].fwd6(k["planes"]["yd"], F.ACT_LRELU, planes=True)
+    again = eng.TPM[0].forward(k["acts"]["yd"], F.ACT_LRELU, planes=True).x
     torch.cuda.synchronize()
     snap["tp0:recomputed"] = again.clone()
     print(f"run {r}: tp0 in the flow == tp0 recomputed afterwards: {torch.equal(again, k['tp0'])}", flush=True)
