@@ -91,14 +91,13 @@ class _Layer:
         self.lane = 0             # which weight-gradient stream this layer's wgrad / unpack runs on (StemEngine.side_stream)
 
     def fx3_eligible(self):
-        return (self.kind == "conv" and self.stride == 1 and not self.masked and self.C % 32 == 0 and self.K % 32 == 0
-                and self.R % 2 == 1 and self.R * self.R <= 25 and self.pad == self.R // 2)     # odd windows: 'same' shapes both ways
+        return self.kind == "conv" and not self.masked and _layers.f16x3_same_shape(self.stride, self.R, self.pad, self.C, self.K)
 
     def fx3_masked_eligible(self):
         """the context model's masked convolution, forward only (its input is data + noise: no input gradient): the general
         kernel runs over the live taps alone -- 12 of 25 for the 5x5 type-A mask (layers.py:21-47)"""
-        return (self.kind == "conv" and self.stride == 1 and bool(self.masked) and not self.need_dgrad and self.C % 32 == 0
-                and self.K % 4 == 0 and self.R % 2 == 1 and self.R * self.R <= 25 and self.pad == self.R // 2)
+        return (self.kind == "conv" and bool(self.masked) and not self.need_dgrad
+                and _layers.f16x3_same_shape(self.stride, self.R, self.pad, self.C, self.K, k_multiple=4))
 
     def fx3s_eligible(self):
         n_out, n_red = (self.K, self.C) if self.kind == "conv" else (self.C, self.K)       # outputs / contraction channels of that face
@@ -114,8 +113,7 @@ class _Layer:
     def wg3_eligible(self):
         """weight gradient on csrc/wgrad_f16x3.hip: stride-1 convolutions (all taps are produced, as autograd does for the
         masked context convolution too)"""
-        return (self.kind == "conv" and self.stride == 1 and self.C % 32 == 0 and self.K % 32 == 0 and self.R % 2 == 1
-                and self.R * self.R <= 25 and self.pad == self.R // 2)
+        return self.kind == "conv" and _layers.f16x3_same_shape(self.stride, self.R, self.pad, self.C, self.K)
 
     def set_faces(self):
         """The ONE description of which kernel serves the layer's two faces, derived from the route flags when the engine has

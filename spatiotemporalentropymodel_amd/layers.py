@@ -1,13 +1,16 @@
-"""Layer modules with the reference's names, constructor arguments and state-dict keys, whose
-forward/backward run the HIP kernels through the C ABI.
+"""Layer modules with the reference's names, constructor arguments and state-dict keys, whose forward/backward run the HIP
+kernels through the C ABI -- and the one place that decides which kernel family serves a convolution (`route`).
 
-  Conv2d / ConvTranspose2d   torch.nn.Conv2d / ConvTranspose2d as built by compressai/models/utils.py:112-130
-  MaskedConv2d               compressai/layers/layers.py:21-47
-  GDN                        compressai/layers/gdn.py:22-67
-  FusedSequential            nn.Sequential that fuses Conv -> LeakyReLU pairs into the conv epilogue
+  Conv2d / ConvTranspose2d   torch.nn.Conv2d / ConvTranspose2d as built by compressai/models/utils.py:112-130 (conv / deconv)
+  MaskedConv2d, GDN          compressai/layers/layers.py:21-47, gdn.py:22-67;  LeakyReLU: index-keeping placeholder
+  FusedSequential            nn.Sequential that plans its children into steps (conv, conv+GDN, conv+LeakyReLU), then runs them
+  route / Route / Step       the kernel family of a convolution as a value; f16x3_same_shape: the shape rule engine.py shares
+  cat / to_nchw / adaptive_avg_pool2d, the *Function classes      glue operations of the layer-wise models (stem_utils.py, stem_roi.py)
+  bump_weight_epoch / weight_epoch / wgrad_side_stream / join_wgrad_stream      what optimisers and trainers synchronise with
 """
 from __future__ import annotations
 
+import collections
 import math
 
 import torch
@@ -42,6 +45,15 @@ PACK_F16X2_GEN_FLIP = -6 # ... of the mirrored, transposed weight: the input-gra
 PACK_C4GDN = -5           # A-operand stream of csrc/c4gdn_f16x3.hip: first-layer weight AND the following GDN's gamma
 PACK_GDN_GAMMA = -8       # reparametrised gamma of the GDN fused into conv_f16x3_kernel, packed as a 1x1 weight image
 
+#: role -> packer, for the roles above (every other role is a stem_pack_* role: F.pack_weight(w, role, masked))
+_PACKERS = {
+    PACK_F16X2: F.pack_weight_f16x2,
+    PACK_F16X2_FLIP: lambda w: F.pack_weight_f16x2(w, flip=True),
+    PACK_F16X2_GEN: F.pack_weight_f16x2_gen,
+    PACK_F16X2_GEN_FLIP: lambda w: F.pack_weight_f16x2_gen(w, flip=True),
+    PACK_GDN_GAMMA: F.pack_gdn_gamma_f16x2,
+}
+
 
 class _PackCache:
     """Packed weight copies, rebuilt only when the parameter changed."""
@@ -49,37 +61,23 @@ class _PackCache:
     def __init__(self):
         self._c = {}
 
-    def get(self, w: torch.Tensor, role: int, masked: int = 0):
-        key = (w._version, w.data_ptr(), weight_epoch(w), tuple(w.shape))
+    def _cached(self, role, tensors, build):
+        def key():
+            return tuple((t._version, t.data_ptr(), weight_epoch(t), tuple(t.shape)) for t in tensors)
         hit = self._c.get(role)
-        if hit is not None and hit[0] == key:
+        if hit is not None and hit[0] == key():
             return hit[1]
-        if role == PACK_F16X2:
-            wp = F.pack_weight_f16x2(w)
-        elif role == PACK_F16X2_FLIP:
-            wp = F.pack_weight_f16x2(w, flip=True)
-        elif role == PACK_F16X2_GEN:
-            wp = F.pack_weight_f16x2_gen(w)
-        elif role == PACK_F16X2_GEN_FLIP:
-            wp = F.pack_weight_f16x2_gen(w, flip=True)
-        elif role == PACK_GDN_GAMMA:
-            wp = F.pack_gdn_gamma_f16x2(w)
-        else:
-            wp = F.pack_weight(w, role, masked)
-        if (masked & 3) == 2:                    # the kernel zeroed taps of w in place
-            key = (w._version, w.data_ptr(), weight_epoch(w), tuple(w.shape))
-        self._c[role] = (key, wp)
+        wp = build()
+        self._c[role] = (key(), wp)              # taken after packing: pack mode 2 zeroes the masked taps of w in place
         return wp
+
+    def get(self, w: torch.Tensor, role: int, masked: int = 0):
+        pack = _PACKERS.get(role)
+        return self._cached(role, (w,), lambda: pack(w) if pack is not None else F.pack_weight(w, role, masked))
 
     def get_c4gdn(self, w: torch.Tensor, gamma: torch.Tensor, K: int, R: int):
         """the combined (first-layer weight, GDN gamma) stream of F.conv2d_c4_gdn_f16x3, rebuilt when either parameter changed"""
-        key = tuple((t._version, t.data_ptr(), weight_epoch(t), tuple(t.shape)) for t in (w, gamma))
-        hit = self._c.get(PACK_C4GDN)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        st = F.c4gdn_stream(self.get(w, F.PACK_CONV_FWD_C4), gamma, K, R, R)
-        self._c[PACK_C4GDN] = (key, st)
-        return st
+        return self._cached(PACK_C4GDN, (w, gamma), lambda: F.c4gdn_stream(self.get(w, F.PACK_CONV_FWD_C4), gamma, K, R, R))
 
 
 def _flat_grad(p):
@@ -136,140 +134,212 @@ def _on_side_stream(fn, *tensors):
         torch.autograd.Variable._execution_engine.queue_callback(join_wgrad_stream)
 
 
-# ----------------------------------------------------------------------------- autograd functions
-def _layers_f16x3_enabled():
-    """stride-1 convolutions of the layer-wise (autograd) models -- the variable-rate family of models/stem_roi.py -- on the fp16
-    matrix cores (three fp16 products per fp32 product on two-plane operands, ~2^-21 per product: csrc/conv_f16x3.hip / wgrad_f16x3.hip); STEM_LAYERS_F16X3=0: fp32 MFMA"""
-    return _config.runtime().layers_f16x3
+def _weight_grads(ctx, wgrad, *operands, flat=True):
+    """(dw, db) of a convolution Function's backward.  `wgrad(gw, gb, need_db)` runs the kernels, accumulating into the tensors it
+    is given or filling new ones (gw None), and returns them.  When the parameters' `.grad` are slots of a flat gradient buffer
+    (_flat_grad) it accumulates straight into them on the side stream, `operands` (what it reads) held until the streams join."""
+    if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+        return None, None
+    need_db = bool(ctx.needs_input_grad[2])
+    gw, gb = _flat_grad(ctx.params[0]), (_flat_grad(ctx.params[1]) if need_db else None)
+    if not (flat and gw is not None and (gb is not None or not need_db)):
+        return wgrad(None, None, need_db)
+
+    def run():
+        wgrad(gw, gb, need_db)
+    _on_side_stream(run, *operands) if _WGRAD_SIDE["enabled"] else run()
+    return None, None
 
 
-def _conv_f16x3_route(weight, stride, pad, masked, x_shape):
-    """forward, input gradient and weight gradient of this convolution on the fp16 kernels: stride 1, 'same' padding, channel
-    counts that are multiples of 32, operands within the kernels' 2 GiB buffer views"""
-    K, Cc, R, S = weight.shape
-    B, _, H, W = x_shape
-    # odd windows only: with an even R the output is (H + 1) x (W + 1) and the input gradient needs pad R - 1 - pad, which the
-    # planes hand-over between layers ('same' shapes) does not carry
-    return (stride == 1 and R == S and R % 2 == 1 and pad == R // 2 and not masked and Cc % 32 == 0 and K % 32 == 0 and R * S <= 25
-            and B * H * W <= _config.runtime().layers_f16x3_maxpix
-            and _planes_fit(B * H * W, max(Cc, K)) and B * H * W * ((max(K, Cc) + 127) // 128) * 512 < 0x7FFFFF00)
+# ----------------------------------------------------------------------------- which kernel serves a convolution
+#: fewest output pixels for which the fp16 kernel beats the fp32-MFMA one (64-pixel tiles, no split-K: below ~3/4 of the CUs
+#: the split-K fp32 kernel wins; measured on g_a.6 at B=16: 4096 pixels)
+_F16X3_MIN_PIXELS = 12288
+FP16 = ("wide", "gen")        # Route kinds of the split-operand fp16 kernels
 
 
-#: The general fp16 kernel streams its weight tile once per 64-pixel workgroup and the fp16 weight-gradient kernel re-reads both
-#: operands once per tap: at full-resolution feature maps (a million pixels per batch) both are bound by L2 -> LDS traffic and
-#: lose to the 128x128-tile fp32-MFMA kernels; `config.layers_f16x3_maxpix` caps the fp16 route's pixel count (sweep: DESIGN.md section 9)
+def _planes_fit(npix, channels):
+    """does a planes tensor of this size (4 bytes per element) stay inside one 2 GiB buffer view?"""
+    return npix * ((channels + 31) // 32) * F.PLANES_SLAB_BYTES < 0x7FFFFF00
 
 
-def _wide_kernel(n_out, x_shape):
-    """large pixel counts with at most 192 output channels: the 192-column kernel (128-pixel workgroups, one weight stream per
-    128 pixels) instead of the general one (64-pixel workgroups x 128-column tiles, built for the 16x16 latents)"""
-    B, _, H, W = x_shape
-    return n_out <= 192 and B * H * W >= _config.runtime().layers_wide_minpix
+def f16x3_same_shape(stride, R, pad, C, K, k_multiple=32):
+    """The shape rule of the stride-1 convolutions whose forward, input gradient and weight gradient run on the fp16 kernels
+    (engine._Layer shares it): 'same' padding, an odd window of at most 25 taps, channel counts in whole 32-channel slabs.
+    Odd windows only: with an even R the output is (H + 1) x (W + 1) and the input gradient needs pad R - 1 - pad, which the
+    planes hand-over between layers ('same' shapes) does not carry."""
+    return stride == 1 and R % 2 == 1 and R * R <= 25 and pad == R // 2 and C % 32 == 0 and K % k_multiple == 0
 
+
+class Route(collections.namedtuple("Route", "kind gdn planes_out infer dgrad")):
+    """Which kernels serve one convolution:
+      kind        "c4"   the 4-channel-input fp32-MFMA kernel of igemm.hip (the image, or image + quality map);
+                  "c4h"  first layer + GDN on the fp16 kernel of c4gdn_f16x3.hip
+                  "wide" the 192-column fp16 kernel of conv_f16x3.hip (128-pixel workgroups, one weight stream per 128 pixels)
+                  "gen"  the general fp16 kernel (64-pixel workgroups x 128-column tiles, split-K: built for the 16x16 latents)
+                  "f32"  the fp32-MFMA kernels of igemm.hip / wgrad.hip
+      gdn         the GDN / IGDN that follows runs in the same kernel
+      planes_out  the output is written as fp16 planes for the next convolution (`infer`: INSTEAD of the fp32 tensor)
+      infer       inference-only entry points (no autograd graph); otherwise the layer-wise autograd Functions, whose input
+                  gradient runs on kernel family `dgrad`"""
+    __slots__ = ()
+
+    def __str__(self):
+        return self.kind + ("+gdn" if self.gdn else "") + (" -> planes" if self.planes_out else "")
+
+
+def _runtime(cfg):
+    return cfg if cfg is not None else _config.runtime()
+
+
+def _out_shape(m, in_shape):
+    hw, R = in_shape[2:], m.kernel_size
+    hw = F.deconv_out_hw(*hw, R, R, m.stride, m.padding, m.output_padding) if isinstance(m, ConvTranspose2d) else F.conv_out_hw(*hw, R, R, m.stride, m.padding)
+    return (in_shape[0], m.out_channels) + tuple(hw)
+
+
+def route(m, in_shape, src, *, grad, on_device, cfg=None, gdn=None, act=False, consumer=None, c4gdn=None):
+    """The one decision of which kernel family serves convolution `m` (Conv2d / MaskedConv2d / ConvTranspose2d).  Pure: it reads
+    the module's static facts and its arguments and touches no tensor.  in_shape: logical (B, C, H, W) of the input
+      src        "nchw" | "nhwc": an fp32 tensor in that layout; "planes": fp16 planes alone (left by an `infer` producer)
+      grad       autograd is on;  on_device: input and weights live on the GPU;  cfg: the runtime configuration (default: current)
+      gdn        None | "gdn" | "igdn": what follows;  act: a (leaky) ReLU follows, folded into the layer-wise kernels' epilogue
+      consumer   Route of the convolution that reads this one's output and could take planes from it, else None;  c4gdn: a
+                 (K, R, S, inverse) -> bool in place of F.c4gdn_supported (the library's answer), for callers without the library"""
+    cfg = _runtime(cfg)
+    K, Cin, R = m.out_channels, m.in_channels, m.kernel_size
+    npix = in_shape[0] * in_shape[2] * in_shape[3]
+    hands = consumer is not None and consumer.kind in FP16 and K % 32 == 0
+
+    def first_layer(inverse):
+        return "c4h" if cfg.first_layer_f16x3 and (c4gdn or F.c4gdn_supported)(K, R, R, inverse) else "c4"
+    if not grad and cfg.analysis_f16x3 and type(m) is Conv2d:
+        # frozen / inference chain of convolutions (the analysis transform): operands pre-split into fp16 planes, the following
+        # GDN fused, the output written as planes again when the next convolution takes them.  A chain starts where the next
+        # convolution is eligible too -- either at the 3-channel first layer, whose kernel then writes planes, or with a split
+        # pass over an fp32 tensor -- and runs until one is not eligible.
+        chain = hands and consumer.infer
+        if chain and gdn == "gdn" and Cin == 3 and src == "nchw" and K <= 192:
+            return Route(first_layer(False), True, True, True, None)
+        # the kernels address their operands through 2 GiB buffer views: a batch whose planes exceed one stays on the fp32 kernels
+        fp16 = not m._masked and on_device and R * R <= 25 and Cin % 32 == 0 and _planes_fit(npix, Cin)
+        nout = in_shape[0] * math.prod(_out_shape(m, in_shape)[2:])
+        if fp16 and K <= 192 and _planes_fit(nout, K) and nout >= _F16X3_MIN_PIXELS and (src == "planes" or chain):
+            return Route("wide", gdn == "gdn", chain, True, None)
+        # small layers that end a planes chain (the last convolution of the analysis transform: 4096 output pixels at the bench
+        # size) go to the general split-K kernel, which has no fused GDN
+        if fp16 and src == "planes" and gdn is None and K % 4 == 0:
+            return Route("gen", False, chain, True, None)
+    if gdn is not None and not grad and K <= 192 and K % 4 == 0 and Cin % 4 in (0, 3):
+        # Conv2d / ConvTranspose2d followed by GDN / IGDN in ONE kernel (inference only: no autograd graph)
+        image = type(m) is not ConvTranspose2d and Cin == 3 and src == "nchw"
+        return Route(first_layer(gdn == "igdn") if image else "f32", True, False, True, None)
+    if isinstance(m, ConvTranspose2d):
+        return Route("f32", False, False, False, "f32")
+    # the layer-wise (autograd) Functions.  <= 4 input channels: the image (NCHW, fused layout change) or image + quality map
+    if (Cin == 3 and src == "nchw") or (Cin == 4 and R * R <= 32):
+        return Route("c4", False, False, False, "f32")
+    # Stride-1 convolutions of the layer-wise models (the variable-rate family of models/stem_roi.py) on the fp16 matrix cores:
+    # three fp16 products per fp32 product on two-plane operands, ~2^-21 per product (csrc/conv_f16x3.hip / wgrad_f16x3.hip);
+    # STEM_LAYERS_F16X3=0: fp32 MFMA.  The general fp16 kernel streams its weight tile once per 64-pixel workgroup and the fp16
+    # weight-gradient kernel re-reads both operands once per tap: at full-resolution feature maps (a million pixels per batch) both
+    # are bound by L2 -> LDS traffic and lose to the 128x128-tile fp32-MFMA kernels: `layers_f16x3_maxpix` (sweep: DESIGN.md 9)
+    if (on_device and cfg.layers_f16x3 and not m._masked and f16x3_same_shape(m.stride, R, m.padding, Cin, K)
+            and npix <= cfg.layers_f16x3_maxpix and _planes_fit(npix, max(Cin, K)) and npix * ((max(K, Cin) + 127) // 128) * 512 < 0x7FFFFF00):
+        def family(n_out):      # large pixel counts with at most 192 output channels: the 192-column kernel
+            return "wide" if n_out <= 192 and npix >= cfg.layers_wide_minpix else "gen"
+        # planes for the next convolution when both run on the fp16 kernels (a conv -> LeakyReLU -> conv chain)
+        return Route(family(K), False, bool(act and hands and not consumer.infer), False, family(Cin))
+    return Route("f32", False, False, False, "f32")
 
 
 def planes_of(t):
-    """the fp16 planes copy a producing kernel left next to an activation tensor (same values), if any"""
+    """the fp16 planes copy a producing kernel left next to an activation tensor (same values), if any.  An autograd Function
+    returns tensors only: this attribute is how planes leave Conv2dFunction (_attach_planes) and reach the next convolution."""
     return getattr(t, "_stem_planes", None)
 
 
+def _attach_planes(t, planes):
+    if planes is not None:
+        t._stem_planes = planes
+    return t
+
+
+def _src(x):
+    return "nchw" if F.nhwc_ld(x) is None else "nhwc"
+
+
+# ----------------------------------------------------------------------------- autograd functions
 class Conv2dFunction(torch.autograd.Function):
+    """Conv2d (+ leaky ReLU) on the layer-wise route `r`; `xp`: the input as planes where its producer left them"""
+
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, pad, act, masked, cache, slope=F.LRELU_SLOPE, want_planes=False):
+    def forward(ctx, x, weight, bias, r, xp, stride, pad, act, masked, cache, slope=F.LRELU_SLOPE):
         K, Cc, R, S = weight.shape
-        # <=4 input channels: the image (NCHW, fused layout change: g_a.0) or image+quality map (stem_roi.py:529)
-        first = (Cc == 3 and F.nhwc_ld(x) is None) or (Cc == 4 and R * S <= 32)
-        if not first and x.is_cuda and _layers_f16x3_enabled() and _conv_f16x3_route(weight, stride, pad, masked, x.shape):
-            # fp16 route: the input as planes (left by the producer, or split here), kept for the weight gradient instead
-            # of the fp32 input; the activation is the kernel's epilogue
-            xp = planes_of(x)
+        yp = None
+        if r.kind in FP16:
+            # the input as planes (the producer's, or split here), kept for the weight gradient; the activation is the epilogue
             if xp is None or tuple(xp.shape) != tuple(x.shape):
                 xp = F.F16Planes.split(x)
-            if _wide_kernel(K, x.shape) and xp.dense:
-                y, yp = F.conv2d_f16x3_act(xp, cache.get(weight, PACK_F16X2), bias, K, R, S, 1, pad, bool(act), slope, want_planes)
+            if r.kind == "wide":
+                y, yp = F.conv2d_f16x3_act(xp, cache.get(weight, PACK_F16X2), bias, K, R, S, 1, pad, bool(act), slope, r.planes_out)
             else:
                 y, yp = F.conv2d_f16x3_gen(xp, cache.get(weight, PACK_F16X2_GEN), bias, K, R, S, 1, pad,
-                                            epi=F.GEN_EPI_LRELU if act else F.GEN_EPI_BIAS, slope=slope, want_planes=want_planes)
-            if yp is not None:
-                y._stem_planes = yp
-            ctx.cfg = (stride, pad, act, masked, cache, False, tuple(x.shape), slope)
-            ctx.params = (weight, bias)
-            ctx.fx3 = (xp.q_offset, xp.pix_bytes, xp.byte_offset)
-            ctx.save_for_backward(xp.data, weight, y if act else None)
-            return y
-        ctx.fx3 = None
-        if first:
-            xin = F.nchw3_to_nhwc4(x) if Cc == 3 else F.dense_nhwc(x).permute(0, 2, 3, 1)
-            y = F.conv2d_fwd_c4(xin, cache.get(weight, F.PACK_CONV_FWD_C4), bias, K, R, S, stride, pad)
-            xin = xin.permute(0, 3, 1, 2)               # [B,4,H,W] NHWC view for the weight gradient
+                                            epi=F.GEN_EPI_LRELU if act else F.GEN_EPI_BIAS, slope=slope, want_planes=r.planes_out)
+            xin, ctx.planes = xp.data, (xp.q_offset, xp.pix_bytes, xp.byte_offset)
+        elif r.kind == "c4":
+            x4 = F.nchw3_to_nhwc4(x) if Cc == 3 else F.dense_nhwc(x).permute(0, 2, 3, 1)
+            y = F.conv2d_fwd_c4(x4, cache.get(weight, F.PACK_CONV_FWD_C4), bias, K, R, S, stride, pad)
+            if act:
+                y = F.lrelu_fwd(y, slope)
+            xin = x4.permute(0, 3, 1, 2)                # [B,4,H,W] NHWC view for the weight gradient
         else:
             xin = F.to_nhwc(x)
             y = F.conv2d_fwd(xin, cache.get(weight, F.PACK_CONV_FWD, masked), bias, K, R, S, stride, pad,
                              act | (F.CONV_MASKED_A if masked and not masked & 4 else 0), slope=slope)
-        if first and act:
-            y = F.lrelu_fwd(y, slope)
-        ctx.cfg = (stride, pad, act, masked, cache, first, tuple(x.shape), slope)
-        ctx.params = (weight, bias)
+        ctx.route, ctx.stride, ctx.pad, ctx.act, ctx.masked, ctx.cache, ctx.slope = r, stride, pad, act, masked, cache, slope
+        ctx.xshape, ctx.params = tuple(x.shape), (weight, bias)
         ctx.save_for_backward(xin, weight, y if act else None)
-        return y
-
-    @staticmethod
-    def _backward_fx3(ctx, dy):
-        stride, pad, act, masked, cache, first, xshape, slope = ctx.cfg
-        xdata, weight, y = ctx.saved_tensors
-        K, Cc, R, S = weight.shape
-        xp = F.F16Planes(xdata, xshape, *ctx.fx3)
-        dy = F.to_nhwc(dy)
-        # the gradient as planes, with this layer's leaky-ReLU derivative applied in the splitting pass
-        dyp = F.F16Planes.split_dact(dy, y, slope) if act else F.F16Planes.split(dy)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if _wide_kernel(Cc, xshape):
-                dx = F.conv2d_f16x3_act(dyp, cache.get(weight, PACK_F16X2_FLIP), None, Cc, R, S, 1, pad)[0]
-            else:
-                dx = F.conv2d_f16x3_gen(dyp, cache.get(weight, PACK_F16X2_GEN_FLIP), None, Cc, R, S, 1, pad, epi=F.GEN_EPI_BIAS)[0]
-        dw = db = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            need_db = bool(ctx.needs_input_grad[2])
-            gw, gb = _flat_grad(ctx.params[0]), (_flat_grad(ctx.params[1]) if need_db else None)
-            if gw is not None and (gb is not None or not need_db):
-                def run():
-                    F.conv2d_wgrad_f16x3_into(xp, dyp, K, R, S, pad, gw, gb if need_db else None, accumulate=True)
-                _on_side_stream(run, dyp.data, xdata) if _WGRAD_SIDE["enabled"] else run()
-            else:
-                dw = torch.zeros((K, Cc, R, S), device=dy.device, dtype=torch.float32)
-                db = torch.zeros(K, device=dy.device, dtype=torch.float32) if need_db else None
-                F.conv2d_wgrad_f16x3_into(xp, dyp, K, R, S, pad, dw, db, accumulate=True)
-        return dx, dw, db, None, None, None, None, None, None, None
+        return _attach_planes(y, yp)
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.fx3 is not None:
-            return Conv2dFunction._backward_fx3(ctx, dy)
-        stride, pad, act, masked, cache, first, xshape, slope = ctx.cfg
+        r, stride, pad, masked, cache, slope = ctx.route, ctx.stride, ctx.pad, ctx.masked, ctx.cache, ctx.slope
         xin, weight, y = ctx.saved_tensors
         K, Cc, R, S = weight.shape
         dy = F.to_nhwc(dy)
-        if F.nhwc_ld(dy) != K:
-            dy = F.copy_channels(dy, F.empty_nhwc(*dy.shape, dy.device))
-        if act:
-            dy = F.lrelu_bwd(y, dy, slope)
+        if r.kind in FP16:
+            xp = F.F16Planes(xin, ctx.xshape, *ctx.planes)
+            # the gradient as planes, with this layer's leaky-ReLU derivative applied in the splitting pass
+            dy = F.F16Planes.split_dact(dy, y, slope) if ctx.act else F.F16Planes.split(dy)
+        else:
+            if F.nhwc_ld(dy) != K:
+                dy = F.copy_channels(dy, F.empty_nhwc(*dy.shape, dy.device))
+            if ctx.act:
+                dy = F.lrelu_bwd(y, dy, slope)
         dx = None
-        if ctx.needs_input_grad[0]:
-            dx = F.conv2d_dgrad(dy, cache.get(weight, F.PACK_CONV_DGRAD, (1 | (masked & 4)) if masked else 0), xshape, K, R, S, stride, pad)
-        dw = db = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            need_db = bool(ctx.needs_input_grad[2])
-            gw, gb = _flat_grad(ctx.params[0]), (_flat_grad(ctx.params[1]) if need_db else None)
-            if gw is not None and (gb is not None or not need_db) and not (first and Cc == 3):
-                def run():
-                    F.conv2d_wgrad(xin, dy, K, R, S, stride, pad, dw_out=gw, db_out=gb, need_db=need_db, accumulate=True)
-                _on_side_stream(run, dy, xin) if _WGRAD_SIDE["enabled"] else run()
-            else:
-                dw, db = F.conv2d_wgrad(xin, dy, K, R, S, stride, pad, need_db=need_db)
-                if first and Cc == 3:
-                    dw = dw[:, :3].contiguous()
-        return dx, dw, db, None, None, None, None, None, None, None
+        if ctx.needs_input_grad[0] and r.dgrad == "wide":
+            dx = F.conv2d_f16x3_act(dy, cache.get(weight, PACK_F16X2_FLIP), None, Cc, R, S, 1, pad)[0]
+        elif ctx.needs_input_grad[0] and r.dgrad == "gen":
+            dx = F.conv2d_f16x3_gen(dy, cache.get(weight, PACK_F16X2_GEN_FLIP), None, Cc, R, S, 1, pad, epi=F.GEN_EPI_BIAS)[0]
+        elif ctx.needs_input_grad[0]:
+            dx = F.conv2d_dgrad(dy, cache.get(weight, F.PACK_CONV_DGRAD, (1 | (masked & 4)) if masked else 0), ctx.xshape, K, R, S, stride, pad)
+        if r.kind in FP16:
+            def wgrad(gw, gb, need_db):
+                if gw is None:
+                    gw = torch.zeros((K, Cc, R, S), device=xin.device, dtype=torch.float32)
+                    gb = torch.zeros(K, device=xin.device, dtype=torch.float32) if need_db else None
+                F.conv2d_wgrad_f16x3_into(xp, dy, K, R, S, pad, gw, gb, accumulate=True)
+                return gw, gb
+            dw, db = _weight_grads(ctx, wgrad, dy.data, xin)
+        else:
+            def wgrad(gw, gb, need_db):
+                return F.conv2d_wgrad(xin, dy, K, R, S, stride, pad, dw_out=gw, db_out=gb, need_db=need_db, accumulate=gw is not None)
+            image = r.kind == "c4" and Cc == 3          # its weight gradient has the 4 channels of the padded image
+            dw, db = _weight_grads(ctx, wgrad, dy, xin, flat=not image)
+            if image and dw is not None:
+                dw = dw[:, :3].contiguous()
+        return dx, dw, db, None, None, None, None, None, None, None, None
 
 
 class ConvTranspose2dFunction(torch.autograd.Function):
@@ -278,59 +348,44 @@ class ConvTranspose2dFunction(torch.autograd.Function):
         Cc, K, R, S = weight.shape
         xin = F.to_nhwc(x)
         y = F.deconv2d_fwd(xin, cache.get(weight, F.PACK_DECONV_FWD), bias, K, R, S, stride, pad, opad, act, slope=slope)
-        ctx.cfg = (stride, pad, opad, act, cache, tuple(x.shape), slope)
-        ctx.params = (weight, bias)
+        ctx.stride, ctx.pad, ctx.opad, ctx.act, ctx.cache, ctx.slope = stride, pad, opad, act, cache, slope
+        ctx.xshape, ctx.params = tuple(x.shape), (weight, bias)
         ctx.save_for_backward(xin, weight, y if act else None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        stride, pad, opad, act, cache, xshape, slope = ctx.cfg
+        stride, pad, opad, act, cache = ctx.stride, ctx.pad, ctx.opad, ctx.act, ctx.cache
         xin, weight, y = ctx.saved_tensors
         Cc, K, R, S = weight.shape
         dy = F.to_nhwc(dy)
-        if K == 3 and not act and R * S <= 32:
-            return ConvTranspose2dFunction._backward_rgb(ctx, dy)
-        if F.nhwc_ld(dy) != K:
-            dy = F.copy_channels(dy, F.empty_nhwc(*dy.shape, dy.device))
-        if act:
-            dy = F.lrelu_bwd(y, dy, slope)
+        # The synthesis transform's last layer (-> 3 image channels): the image gradient is padded to 4 channels so that
+        # the input gradient is the 4-channel-input convolution kernel (it IS Conv2d(weight [C,3,R,S], stride, pad) applied
+        # to dY) and the weight gradient uses the folded-tap mode, instead of 3-wide operands in 64-wide MFMA tiles.
+        rgb = K == 3 and not act and R * S <= 32
+        if rgb:
+            B, _, Ho, Wo = dy.shape
+            dy4 = torch.zeros((B, Ho, Wo, 4), device=dy.device, dtype=torch.float32)
+            F.copy_channels(dy, dy4.permute(0, 3, 1, 2)[:, :3])
+            dy = dy4.permute(0, 3, 1, 2)
+        else:
+            if F.nhwc_ld(dy) != K:
+                dy = F.copy_channels(dy, F.empty_nhwc(*dy.shape, dy.device))
+            if act:
+                dy = F.lrelu_bwd(y, dy, ctx.slope)
         dx = None
-        if ctx.needs_input_grad[0]:
-            dx = F.deconv2d_dgrad(dy, cache.get(weight, F.PACK_DECONV_DGRAD), xshape, K, R, S, stride, pad, opad)
-        dw = db = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            need_db = bool(ctx.needs_input_grad[2])
-            gw, gb = _flat_grad(ctx.params[0]), (_flat_grad(ctx.params[1]) if need_db else None)
-            if gw is not None and (gb is not None or not need_db):
-                def run():
-                    F.deconv2d_wgrad(xin, dy, K, R, S, stride, pad, opad, dw_out=gw, db_out=gb, need_db=need_db, accumulate=True)
-                _on_side_stream(run, dy, xin) if _WGRAD_SIDE["enabled"] else run()
-            else:
-                dw, db = F.deconv2d_wgrad(xin, dy, K, R, S, stride, pad, opad, need_db=need_db)
-        return dx, dw, db, None, None, None, None, None, None
-
-    @staticmethod
-    def _backward_rgb(ctx, dy):
-        """The synthesis transform's last layer (-> 3 image channels): the image gradient is padded to 4 channels so that
-        the input gradient is the 4-channel-input convolution kernel (it IS Conv2d(weight [C,3,R,S], stride, pad) applied
-        to dY) and the weight gradient uses the folded-tap mode, instead of 3-wide operands in 64-wide MFMA tiles."""
-        stride, pad, opad, act, cache, xshape, slope = ctx.cfg
-        xin, weight, _ = ctx.saved_tensors
-        Cc, K, R, S = weight.shape
-        B, _, Ho, Wo = dy.shape
-        dy4 = torch.zeros((B, Ho, Wo, 4), device=dy.device, dtype=torch.float32)
-        F.copy_channels(dy, dy4.permute(0, 3, 1, 2)[:, :3])
-        dx = None
-        if ctx.needs_input_grad[0]:
+        if ctx.needs_input_grad[0] and rgb:
             dx = F.conv2d_fwd_c4(dy4, cache.get(weight, F.PACK_CONV_FWD_C4), None, Cc, R, S, stride, pad)
-            assert tuple(dx.shape) == tuple(xshape), (dx.shape, xshape)
-        dw = db = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            need_db = bool(ctx.needs_input_grad[2])
-            dw4, db4 = F.deconv2d_wgrad(xin, dy4.permute(0, 3, 1, 2), 4, R, S, stride, pad, opad, need_db=need_db)
-            dw = dw4[:, :3].contiguous()
-            db = db4[:3].contiguous() if need_db else None
+            assert tuple(dx.shape) == tuple(ctx.xshape), (dx.shape, ctx.xshape)
+        elif ctx.needs_input_grad[0]:
+            dx = F.deconv2d_dgrad(dy, cache.get(weight, F.PACK_DECONV_DGRAD), ctx.xshape, K, R, S, stride, pad, opad)
+
+        def wgrad(gw, gb, need_db):
+            return F.deconv2d_wgrad(xin, dy, 4 if rgb else K, R, S, stride, pad, opad, dw_out=gw, db_out=gb, need_db=need_db,
+                                    accumulate=gw is not None)
+        dw, db = _weight_grads(ctx, wgrad, dy, xin, flat=not rgb)
+        if rgb and dw is not None:
+            dw, db = dw[:, :3].contiguous(), (db[:3].contiguous() if db is not None else None)
         return dx, dw, db, None, None, None, None, None, None
 
 
@@ -470,12 +525,37 @@ class Conv2d(nn.Module):
             bound = 1 / math.sqrt(self.weight[0].numel())
             nn.init.uniform_(self.bias, -bound, bound)
 
-    def forward(self, x, act=F.ACT_NONE, slope=F.LRELU_SLOPE, planes=False):
-        """planes=True: the consumer is another fp16-routed convolution -- leave the pre-split copy next to the output"""
-        return Conv2dFunction.apply(x, self.weight, self.bias, self.stride, self.padding, act, self._masked, self._packs, slope, planes)
+    def forward(self, x, act=F.ACT_NONE, slope=F.LRELU_SLOPE, r=None):
+        """r: the layer-wise Route a FusedSequential has planned for this call"""
+        r = r or route(self, x.shape, _src(x), grad=torch.is_grad_enabled(), on_device=x.is_cuda)
+        return Conv2dFunction.apply(x, self.weight, self.bias, r, planes_of(x), self.stride, self.padding, act, self._masked, self._packs, slope)
 
-    def f16x3_route(self, x_shape):
-        return _layers_f16x3_enabled() and _conv_f16x3_route(self.weight, self.stride, self.padding, self._masked, x_shape)
+    def _launch(self, r, x, xp, gdn, act, slope):
+        """the kernels of route `r` on (fp32 tensor or None, planes or None) -> the same pair for the next step"""
+        K, R, w, b, packs = self.out_channels, self.kernel_size, self.weight, self.bias, self._packs
+        if not r.infer:
+            y = self(x, act, slope, r)
+            return y, planes_of(y)
+        beta, gamma, beta_min = (gdn.beta, gdn.gamma, gdn.beta_min) if r.gdn else (None, None, 1e-6)
+        if r.kind in ("c4", "c4h"):
+            wp = packs.get(w, F.PACK_CONV_FWD_C4) if r.planes_out else None
+            ast = packs.get_c4gdn(w, gamma, K, R) if r.kind == "c4h" else None
+            x4 = F.nchw3_to_nhwc4(x)
+            if r.planes_out:
+                return None, F.conv2d_fwd_c4_gdn_planes(x4, wp, b, beta, gamma, K, R, R, self.stride, self.padding, beta_min, astream=ast)
+            return F.conv2d_fwd_c4_gdn(x4, packs.get(w, F.PACK_CONV_FWD_C4), b, beta, gamma, K, R, R, self.stride, self.padding,
+                                       gdn.inverse, beta_min, astream=ast), None
+        if r.kind == "wide":
+            xin = xp if x is None else F.F16Planes.split(x)
+            wp = packs.get(w, PACK_F16X2)
+            gp = packs.get(gamma, PACK_GDN_GAMMA) if r.gdn else None          # kept in the convolution's cache
+            out = F.conv2d_f16x3_fwd(xin, wp, b, K, R, R, self.stride, self.padding, beta, gamma, beta_min, planes_out=r.planes_out, gp=gp)
+            return (None, out) if r.planes_out else (out, None)
+        if r.kind == "gen":
+            return F.conv2d_f16x3_gen(xp, packs.get(w, PACK_F16X2_GEN), b, K, R, R, self.stride, self.padding,
+                                      want_fp32=not r.planes_out, want_planes=r.planes_out)
+        return F.conv2d_gdn_fwd(F.to_nhwc(x), packs.get(w, F.PACK_CONV_FWD, self._masked), b, beta, gamma, K, R, R, self.stride,
+                                self.padding, gdn.inverse, beta_min), None
 
     def extra_repr(self):
         return f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}"
@@ -501,6 +581,13 @@ class ConvTranspose2d(nn.Module):
     def forward(self, x, act=F.ACT_NONE, slope=F.LRELU_SLOPE):
         return ConvTranspose2dFunction.apply(x, self.weight, self.bias, self.stride, self.padding, self.output_padding,
                                              act, self._packs, slope)
+
+    def _launch(self, r, x, xp, gdn, act, slope):
+        if not r.gdn:
+            return self(x, act, slope), None
+        R = self.kernel_size
+        return F.deconv2d_gdn_fwd(F.to_nhwc(x), self._packs.get(self.weight, F.PACK_DECONV_FWD), self.bias, gdn.beta, gdn.gamma,
+                                  self.out_channels, R, R, self.stride, self.padding, self.output_padding, gdn.inverse, gdn.beta_min), None
 
 
 class MaskedConv2d(Conv2d):
@@ -539,80 +626,19 @@ class LeakyReLU(nn.LeakyReLU):
     FusedSequential folds it into the preceding convolution's epilogue."""
 
 
-def _conv_gdn_fused(conv_mod, gdn, x):
-    """Conv2d / ConvTranspose2d followed by GDN / IGDN in ONE kernel (inference only: no autograd graph)."""
-    K = conv_mod.out_channels
-    R = conv_mod.kernel_size
-    w, b = conv_mod.weight, conv_mod.bias
-    if isinstance(conv_mod, ConvTranspose2d):
-        return F.deconv2d_gdn_fwd(F.to_nhwc(x), conv_mod._packs.get(w, F.PACK_DECONV_FWD), b, gdn.beta, gdn.gamma, K, R, R,
-                                  conv_mod.stride, conv_mod.padding, conv_mod.output_padding, gdn.inverse, gdn.beta_min)
-    if conv_mod.in_channels == 3 and F.nhwc_ld(x) is None:
-        ast = conv_mod._packs.get_c4gdn(w, gdn.gamma, K, R) if F.c4gdn_supported(K, R, R, gdn.inverse) else None
-        return F.conv2d_fwd_c4_gdn(F.nchw3_to_nhwc4(x), conv_mod._packs.get(w, F.PACK_CONV_FWD_C4), b, gdn.beta, gdn.gamma, K, R, R,
-                                   conv_mod.stride, conv_mod.padding, gdn.inverse, gdn.beta_min, astream=ast)
-    return F.conv2d_gdn_fwd(F.to_nhwc(x), conv_mod._packs.get(w, F.PACK_CONV_FWD, conv_mod._masked), b, gdn.beta, gdn.gamma, K, R, R,
-                            conv_mod.stride, conv_mod.padding, gdn.inverse, gdn.beta_min)
-
-
-def _f16x3_enabled():
-    """fp32-accurate convolutions on the fp16 matrix cores for inference-only chains (csrc/conv_f16x3.hip).  STEM_F16X3=0
-    selects the fp32-MFMA kernels everywhere."""
-    return _config.runtime().analysis_f16x3
-
-
-#: fewest output pixels for which the fp16 kernel beats the fp32-MFMA one (64-pixel tiles, no split-K: below ~3/4 of the CUs
-#: the split-K fp32 kernel wins; measured on g_a.6 at B=16: 4096 pixels)
-_F16X3_MIN_PIXELS = 12288
-
-
-def _f16x3_eligible(m, in_shape):
-    """Can conv `m`, applied to an input of logical shape `in_shape` = (B, C, H, W), run on csrc/conv_f16x3.hip?"""
-    if not (type(m) is Conv2d and not m._masked and m.in_channels % 32 == 0 and m.out_channels <= 192
-            and m.kernel_size * m.kernel_size <= 25 and m.weight.is_cuda):
-        return False
-    return _f16x3_shape_ok(m, in_shape)
-
-
-def _f16x3_shape_ok(m, in_shape):
-    B, _, H, W = in_shape
-    Ho, Wo = F.conv_out_hw(H, W, m.kernel_size, m.kernel_size, m.stride, m.padding)
-    if not (_planes_fit(B * H * W, m.in_channels) and _planes_fit(B * Ho * Wo, m.out_channels)):
-        return False          # the kernels address their operands through 2 GiB buffer views: such a batch stays on the fp32 kernels
-    return B * Ho * Wo >= _F16X3_MIN_PIXELS
-
-
-def _planes_fit(npix, channels):
-    """does a planes tensor of this size (4 bytes per element) stay inside one 2 GiB buffer view?"""
-    return npix * ((channels + 31) // 32) * F.PLANES_SLAB_BYTES < 0x7FFFFF00
-
-
-def _f16x3_gen_eligible(m, follows_gdn, in_shape=None):
-    """Small layers that end a planes chain (the last convolution of the analysis transform: 4096 output pixels at the bench
-    size) go to the general split-K kernel, which has no fused GDN."""
-    if in_shape is not None and not _planes_fit(in_shape[0] * in_shape[2] * in_shape[3], m.in_channels):
-        return False
-    return (type(m) is Conv2d and not m._masked and not follows_gdn and m.in_channels % 32 == 0 and m.out_channels % 4 == 0
-            and m.kernel_size * m.kernel_size <= 25 and m.weight.is_cuda)
-
-
-def _conv_out_shape(m, in_shape):
-    B, _, H, W = in_shape
-    Ho, Wo = F.conv_out_hw(H, W, m.kernel_size, m.kernel_size, m.stride, m.padding)
-    return (B, m.out_channels, Ho, Wo)
+#: One step of a plan: the children it covers (conv [+ GDN | + activation]; a lone GDN / activation: route None), the input's shape
+Step = collections.namedtuple("Step", "children route in_shape act slope")
+_ACTIVATIONS = (nn.LeakyReLU, nn.ReLU)
 
 
 class FusedSequential(nn.Sequential):
     #: optional (index, list) pair -- or a dict {index: list} -- set by bench.py: HIP events are recorded on the launching stream
-    #: around the kernel(s) of child `index`
+    #: around the kernel(s) of the step whose first child is `index`
     probe = None
 
     def _timed(self, i, fn):
-        sink = None
-        if isinstance(self.probe, dict):
-            sink = self.probe.get(i)
-        elif self.probe is not None and self.probe[0] == i:
-            sink = self.probe[1]
+        probe = self.probe
+        sink = probe.get(i) if isinstance(probe, dict) else probe[1] if probe is not None and probe[0] == i else None
         if sink is None:
             return fn()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -622,71 +648,52 @@ class FusedSequential(nn.Sequential):
         sink.append((e0, e1))
         return out
 
-    def forward(self, x):
-        mods = list(self)
-        nograd = not torch.is_grad_enabled()
-        fx3 = nograd and _f16x3_enabled()
-        i = 0
+    def plan(self, in_shape, src, grad, on_device, cfg=None, c4gdn=None):
+        """The children as a list of Steps for an input of logical shape `in_shape` (other arguments: see `route`).  Pure and cheap:
+        planned at every call.  A GDN behind a convolution is fused where the route has a kernel for it; a LeakyReLU (slope) or
+        ReLU (= slope 0) is folded into the layer-wise kernels' epilogue; planes travel between convolutions on the fp16 kernels."""
+        mods, steps, shape, i = list(self), [], tuple(in_shape), 0
+        kw = dict(grad=grad, on_device=on_device, cfg=_runtime(cfg), c4gdn=c4gdn)
+
+        def routed(j, shape, src, consumer=None):
+            nxt = mods[j + 1] if j + 1 < len(mods) else None
+            gdn = ("igdn" if nxt.inverse else "gdn") if isinstance(nxt, GDN) else None
+            return route(mods[j], shape, src, gdn=gdn, act=isinstance(nxt, _ACTIVATIONS), consumer=consumer, **kw)
+
         while i < len(mods):
             m = mods[i]
-            nxt = mods[i + 1] if i + 1 < len(mods) else None
-            if fx3 and type(m) is Conv2d:
-                # frozen / inference chain of convolutions (the analysis transform): operands pre-split into fp16 planes, the
-                # following GDN fused, the output written as planes again when the next convolution takes them.  A chain
-                # starts where the next convolution is eligible too -- either at the 3-channel first layer, whose fp32 kernel
-                # then writes planes, or with a split pass over an fp32 tensor -- and runs until one is not eligible.
-                gdn = nxt if isinstance(nxt, GDN) and not nxt.inverse else None
-                j = i + (2 if gdn is not None else 1)
-                K, R = m.out_channels, m.kernel_size
-                out_shape = _conv_out_shape(m, x.shape)
-                chain = False
-                if K % 32 == 0 and j < len(mods) and mods[j].__class__ is Conv2d and mods[j].in_channels == K:
-                    nxt_gdn = j + 1 < len(mods) and isinstance(mods[j + 1], GDN)
-                    chain = _f16x3_eligible(mods[j], out_shape) or _f16x3_gen_eligible(mods[j], nxt_gdn, out_shape)
-                if (chain and gdn is not None and m.in_channels == 3 and not isinstance(x, F.F16Planes) and F.nhwc_ld(x) is None
-                        and K <= 192):
-                    wp = m._packs.get(m.weight, F.PACK_CONV_FWD_C4)
-                    ast = m._packs.get_c4gdn(m.weight, gdn.gamma, K, R) if F.c4gdn_supported(K, R, R) else None
-                    x = self._timed(i, lambda: F.conv2d_fwd_c4_gdn_planes(F.nchw3_to_nhwc4(x), wp, m.bias, gdn.beta, gdn.gamma, K, R, R,
-                                                                          m.stride, m.padding, gdn.beta_min, astream=ast))
-                    i = j
-                    continue
-                if _f16x3_eligible(m, x.shape) and (isinstance(x, F.F16Planes) or (chain and x.is_cuda)):
-                    xin = x if isinstance(x, F.F16Planes) else F.F16Planes.split(x)
-                    wp = m._packs.get(m.weight, PACK_F16X2)
-                    gp = m._packs.get(gdn.gamma, PACK_GDN_GAMMA) if gdn is not None else None     # kept in the convolution's cache
-                    x = self._timed(i, lambda: F.conv2d_f16x3_fwd(xin, wp, m.bias, K, R, R, m.stride, m.padding,
-                                                                   gdn.beta if gdn is not None else None,
-                                                                   gdn.gamma if gdn is not None else None,
-                                                                   gdn.beta_min if gdn is not None else 1e-6, planes_out=chain, gp=gp))
-                    i = j
-                    continue
-                if isinstance(x, F.F16Planes) and _f16x3_gen_eligible(m, gdn is not None):
-                    wp = m._packs.get(m.weight, PACK_F16X2_GEN)
-                    x = self._timed(i, lambda: F.conv2d_f16x3_gen(x, wp, m.bias, K, R, R, m.stride, m.padding, want_fp32=not chain,
-                                                                   want_planes=chain)[1 if chain else 0])
-                    i = j
-                    continue
-            if (isinstance(m, (Conv2d, ConvTranspose2d)) and isinstance(nxt, GDN) and nograd and m.out_channels <= 192
-                    and m.out_channels % 4 == 0 and m.in_channels % 4 in (0, 3)):
-                x = self._timed(i, lambda: _conv_gdn_fused(m, nxt, x))
-                i += 2
+            if isinstance(m, (GDN,) + _ACTIVATIONS):
+                steps.append(Step((i,), None, shape, F.ACT_NONE, F.LRELU_SLOPE))
+                src, i = "nhwc" if isinstance(m, GDN) else src, i + 1
                 continue
-            if isinstance(m, (Conv2d, ConvTranspose2d)) and isinstance(nxt, (nn.LeakyReLU, nn.ReLU)):
-                # LeakyReLU(slope) or ReLU (= slope 0) folded into the conv epilogue
-                slope = float(nxt.negative_slope) if isinstance(nxt, nn.LeakyReLU) else 0.0
-                if type(m) is Conv2d and x.is_cuda:
-                    # hand planes to the next convolution when both run on the fp16 kernels (a conv -> LeakyReLU -> conv chain)
-                    after = mods[i + 2] if i + 2 < len(mods) else None
-                    out_shape = _conv_out_shape(m, x.shape)
-                    hand = type(after) is Conv2d and m.f16x3_route(x.shape) and after.f16x3_route(out_shape)
-                    x = self._timed(i, lambda: m(x, act=F.ACT_LRELU, slope=slope, planes=hand))
-                else:
-                    x = self._timed(i, lambda: m(x, act=F.ACT_LRELU, slope=slope))
-                i += 2
-            else:
-                x = m(x)
-                i += 1
+            if not isinstance(m, (Conv2d, ConvTranspose2d)):
+                raise TypeError(f"FusedSequential plans convolutions, GDNs and (leaky) ReLUs; child {i} is a {type(m).__name__}")
+            # who reads the output: the convolution behind a fusable GDN / a folded activation, or the very next child
+            nxt = mods[i + 1] if i + 1 < len(mods) else None
+            folded = isinstance(nxt, _ACTIVATIONS)
+            j = i + (2 if folded or (isinstance(nxt, GDN) and not nxt.inverse) else 1)
+            out_shape, consumer = _out_shape(m, shape), None
+            if j < len(mods) and type(mods[j]) is Conv2d and mods[j].in_channels == m.out_channels:
+                consumer = routed(j, out_shape, "nhwc" if folded else "planes")
+            r = routed(i, shape, src, consumer)
+            assert src != "planes" or (r.infer and r.kind in FP16), f"child {i} was handed planes and has no kernel that reads them ({r})"
+            act, slope = F.ACT_NONE, F.LRELU_SLOPE
+            if folded and not r.infer:
+                act, slope = F.ACT_LRELU, (float(nxt.negative_slope) if isinstance(nxt, nn.LeakyReLU) else 0.0)
+            n = 2 if r.gdn or act else 1
+            steps.append(Step(tuple(range(i, i + n)), r, shape, act, slope))
+            shape, src, i = out_shape, "planes" if r.infer and r.planes_out else "nhwc", i + n
+        return steps
+
+    def forward(self, x):
+        mods, xp = list(self), planes_of(x)
+        for st in self.plan(x.shape, _src(x), torch.is_grad_enabled(), x.is_cuda):
+            m = mods[st.children[0]]
+            if st.route is None:
+                x, xp = m(x), None
+                continue
+            gdn = mods[st.children[1]] if st.route.gdn else None
+            x, xp = self._timed(st.children[0], lambda: m._launch(st.route, x, xp, gdn, st.act, st.slope))
         return x
 
 

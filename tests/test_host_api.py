@@ -478,16 +478,96 @@ def test_bf16_planes_views_and_engine_routing_table():
     assert all(l.fx3 for l in e64.EPM + e64.TPM)
 
 
+def _plan(seq, shape, src="nchw", grad=False, **kw):
+    """a FusedSequential's plan as strings: route, input shape of the fp16 kernels, planes hand-over (CPU: no library is asked)"""
+    def text(s):
+        r = s.route
+        return "-" if r is None else (r.kind + ("+gdn" if r.gdn else "") + (f" {s.in_shape}" if r.kind in ("wide", "gen") else "")
+                                      + (" -> planes" if r.planes_out else ""))
+    return [text(s) for s in seq.plan(shape, src, grad, True, c4gdn=lambda K, R, S, inverse=False: not inverse and K in (64, 128, 192), **kw)]
+
+
 def test_bf16_chain_is_not_selected_when_planes_exceed_a_buffer_view():
     """6 full-HD frames per call: their planes (two fp16 numbers per value, 2.4 GB) exceed the 2 GiB views the kernels address
     operands through: the chain must not start; 5 frames fit."""
     from spatiotemporalentropymodel_amd import layers as L
     from spatiotemporalentropymodel_amd.zoo import models
     conv1 = models["mbt2018"](quality=4).g_a[2]
-    assert L._f16x3_shape_ok(conv1, (5, 192, 544, 960))
-    assert not L._f16x3_shape_ok(conv1, (6, 192, 544, 960))
+
+    def wide(shape):        # g_a.2 fed with planes of `shape` by g_a.0: on the 192-column fp16 kernel?
+        r = L.route(conv1, shape, "planes", grad=False, on_device=True, gdn="gdn")
+        return r.infer and r.kind == "wide"
+    assert wide((5, 192, 544, 960))
+    assert not wide((6, 192, 544, 960))
     assert L._planes_fit(5 * 544 * 960, 192) and not L._planes_fit(6 * 544 * 960, 192)
-    assert not L._f16x3_shape_ok(conv1, (1, 192, 32, 32))          # too few output pixels for the 192-wide kernel
+    assert not wide((1, 192, 32, 32))          # too few output pixels for the 192-wide kernel
+
+
+def test_analysis_transform_plan_at_the_bench_size_and_under_autograd():
+    """B=16 x 256x256 (the bench workload): g_a.0 hands planes to g_a.2, g_a.2 to g_a.4, g_a.4 to the small last layer, which runs
+    on the general split-K kernel -- the sequence tests/test_hip_f16x3.py sees launched; with autograd enabled (trainable
+    transform) nothing is routed to the inference-only kernels; below _F16X3_MIN_PIXELS the fused fp32 conv+GDN kernels."""
+    from spatiotemporalentropymodel_amd import config
+    from spatiotemporalentropymodel_amd.zoo import models
+    g_a = models["mbt2018"](quality=4).g_a
+    bench = (16, 3, 256, 256)
+    with config.override(analysis_f16x3=True, first_layer_f16x3=True, layers_f16x3=True):
+        assert _plan(g_a, bench) == ["c4h+gdn -> planes", "wide+gdn (16, 192, 128, 128) -> planes", "wide+gdn (16, 192, 64, 64) -> planes",
+                                     "gen (16, 192, 32, 32)"]
+        assert [s.children for s in g_a.plan(bench, "nchw", False, True, c4gdn=lambda *a: True)] == [(0, 1), (2, 3), (4, 5), (6,)]
+        steps = g_a.plan(bench, "nchw", True, True)
+        assert [s.children for s in steps] == [(i,) for i in range(7)]
+        assert not any(s.route.infer for s in steps if s.route is not None)
+        assert [str(s.route) for s in steps] == ["c4", "None", "f32", "None", "f32", "None", "f32"]     # stride 2: no layer-wise fp16 kernel
+        assert _plan(g_a, (2, 3, 256, 256)) == ["c4h+gdn", "f32+gdn", "f32+gdn", "f32"]
+        # the chain does not start at 6 full-HD frames (2 GiB views) and does at 5
+        assert _plan(g_a, (5, 3, 1088, 1920))[:2] == ["c4h+gdn -> planes", "wide+gdn (5, 192, 544, 960) -> planes"]
+        assert _plan(g_a, (6, 3, 1088, 1920)) == ["c4h+gdn", "f32+gdn", "wide+gdn (6, 192, 272, 480) -> planes", "wide (6, 192, 136, 240)"]
+        # an NHWC image is not the first-layer kernel's input; a CPU model has no kernels at all to choose from
+        assert _plan(g_a, bench, src="nhwc")[0] == "f32+gdn"
+        assert [str(s.route) for s in g_a.plan(bench, "nchw", False, False, c4gdn=lambda *a: True)] == ["c4h+gdn", "f32+gdn", "f32+gdn", "f32"]
+    with config.override(analysis_f16x3=False):
+        assert _plan(g_a, bench) == ["c4h+gdn", "f32+gdn", "f32+gdn", "f32"]
+    with config.override(first_layer_f16x3=False):
+        assert _plan(g_a, bench)[0] == "c4+gdn -> planes"
+        assert _plan(g_a, (2, 3, 256, 256))[0] == "c4+gdn"
+
+
+def test_layerwise_plan_hands_planes_between_fp16_convolutions():
+    """conv -> LeakyReLU -> conv: planes go from one to the next exactly when both ends take the fp16 route; `wide` / `gen` flips at
+    layers_wide_minpix (output channels <= 192); STEM_LAYERS_F16X3=0 and layers_f16x3_maxpix give the fp32 route."""
+    from spatiotemporalentropymodel_amd import config
+    from spatiotemporalentropymodel_amd.layers import Conv2d, ConvTranspose2d, FusedSequential, LeakyReLU
+    seq = FusedSequential(Conv2d(192, 256, 5, 1, 2), LeakyReLU(), Conv2d(256, 320, 5, 1, 2), LeakyReLU(),      # TPM-like ...
+                          Conv2d(320, 128, 5, 2, 2), LeakyReLU(), ConvTranspose2d(128, 64, 5, 2, 2, 1), torch.nn.ReLU(),
+                          Conv2d(64, 64, 3, 1, 1))                                                              # ... and a strided tail
+    shape = (8, 192, 16, 16)
+    for grad in (True, False):
+        steps = seq.plan(shape, "nhwc", grad, True)
+        assert [s.children for s in steps] == [(0, 1), (2, 3), (4, 5), (6, 7), (8,)]
+        assert [str(s.route) for s in steps] == ["gen -> planes", "gen", "f32", "f32", "gen"], grad
+        assert [s.route.dgrad for s in steps] == ["gen", "gen", "f32", "f32", "gen"]
+        assert not any(s.route.infer for s in steps)
+        assert [(s.act, s.slope) for s in steps] == [(1, 0.01), (1, 0.01), (1, 0.01), (1, 0.0), (0, 0.01)]
+    with config.override(layers_f16x3=False):
+        assert [str(s.route) for s in seq.plan(shape, "nhwc", True, True)] == ["f32"] * 5
+    with config.override(layers_f16x3_maxpix=8 * 16 * 16 - 1):
+        assert [str(s.route) for s in seq.plan(shape, "nhwc", True, True)] == ["f32"] * 5
+    with config.override(layers_f16x3_maxpix=8 * 16 * 16):
+        assert [str(s.route) for s in seq.plan(shape, "nhwc", True, True)] == ["gen -> planes", "gen", "f32", "f32", "gen"]
+    pair = FusedSequential(Conv2d(64, 128, 3, 1, 1), LeakyReLU(), Conv2d(128, 96, 3, 1, 1))
+    minpix = config.runtime().layers_wide_minpix
+    B = minpix // (64 * 64)
+    assert [str(s.route) for s in pair.plan((B, 64, 64, 64), "nhwc", True, True)] == ["wide -> planes", "wide"]
+    assert [str(s.route) for s in pair.plan((B, 64, 64, 63), "nhwc", True, True)] == ["gen -> planes", "gen"]
+    with config.override(layers_wide_minpix=0):
+        assert [str(s.route) for s in pair.plan((1, 64, 4, 4), "nhwc", True, True)] == ["wide -> planes", "wide"]
+    # one end off the fp16 route (33 channels: not whole slabs; a 4x4 window): no planes are written
+    for other in (Conv2d(128, 33, 3, 1, 1), Conv2d(128, 96, 4, 1, 2)):
+        assert [str(s.route) for s in FusedSequential(pair[0], LeakyReLU(), other).plan((4, 64, 16, 16), "nhwc", True, True)] == ["gen", "f32"]
+    assert [str(s.route) for s in FusedSequential(Conv2d(33, 128, 3, 1, 1), LeakyReLU(), pair[2]).plan((4, 33, 16, 16), "nhwc", True, True)] == ["f32", "gen"]
+    with pytest.raises(TypeError):
+        FusedSequential(pair[0], torch.nn.Sigmoid()).plan((4, 64, 16, 16), "nhwc", True, True)
 
 
 def test_planes_byte_count_matches_the_library():
