@@ -604,6 +604,20 @@ int stem_adam_step_dev(float *p, const float *g, float *m, float *v, size_t n, c
 /* ctr[0] += inc on the device (epoch counters of captured graphs) */
 int stem_counter_add(long long *ctr, long long inc, void *stream);
 
+/* ---- evaluation metrics ------------------------------------------------- */
+/* stem/evalSTEM.py:81,147 (pytorch_msssim.ms_ssim(x, x_hat, data_range=1.0)) and :29-31 (PSNR's mean squared error) of two fp32
+ * NCHW-contiguous batches [B,C,H,W]: five scales, 11-tap Gaussian window (sigma 1.5), K = (0.01, 0.03), 2x2 average pooling with
+ * padding s % 2 between scales; window means accumulated in fp64, sums without atomics (bit-reproducible, and independent of the
+ * batch around an image).  ms_ssim[b]: mean over channels of the product of the clamped, exponentiated per-scale means; mse[b]:
+ * mean of (x - y)^2 over the image; terms[b][c][s]: the five clamped per-scale means BEFORE exponentiation (cs for s < 4, ssim for
+ * s = 4).  min(H, W) must exceed 160 (a fifth scale exists); `workspace`: stem_ms_ssim_workspace() bytes of device memory,
+ * 8-byte aligned, nothing to initialise.  No host synchronisation; outputs stay on the device. */
+int stem_ms_ssim_workspace(int B, int C, int H, int W, size_t *bytes);
+int stem_ms_ssim(const float *x, const float *y, int B, int C, int H, int W, float data_range,
+                 void *workspace, size_t workspace_bytes,
+                 float *ms_ssim /* [B] */, float *mse /* [B], may be NULL */, float *terms /* [B][C][5], may be NULL */,
+                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,8 @@ _HIP_SIG = {
                              vp, vp, vp, vp, vp, ci, ci, vp, vp, vp],
     "stem_ar_encode_image": [vp, ci, vp, vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, cf, cf,
                              vp, vp, vp],
+    "stem_ms_ssim_workspace": [ci, ci, ci, ci, vp],
+    "stem_ms_ssim": [vp, vp, ci, ci, ci, ci, cf, vp, sz, vp, vp, vp, vp],
     "stem_sumsq": [vp, sz, vp, vp],
     "stem_sumsq_set": [vp, sz, vp, vp],
     "stem_clip_scale": [vp, sz, vp, cf, vp],

@@ -10,8 +10,9 @@ Same order of operations, same returned keys, same arithmetic for bpp / PSNR as 
 `pytorch_msssim.ms_ssim(x, x_hat, data_range=1.0)` (:81, :147), a third-party package that is not in the reference tree (nor in this
 image; unpinned in the reference's requirements): `ms_ssim` below restates the published algorithm (Wang, Simoncelli, Bovik 2003)
 with that package's conventions.  PARITY UNPINNED for this one number -- no golden vector exists; tests/test_host_api.py checks it
-against an independent scipy formulation and its defining properties.  It is a reporting metric computed on the HOST, outside the
-timed encode / decode regions; frames smaller than 161 pixels on a side have no five-scale MS-SSIM and report None.  One deliberate difference: the script's I frame runs
+against an independent scipy formulation and its defining properties.  It is a reporting metric outside the timed encode / decode
+regions, computed on the host by default and by the HIP kernel on request: `with_msssim="device"` takes "ms-ssim" and "psnr" of a frame
+from one stem_ms_ssim call (functional.ms_ssim, `ms_ssim_device` below; tests/test_hip_msssim.py holds it against float64); frames smaller than 161 pixels on a side have no five-scale MS-SSIM and report None.  One deliberate difference: the script's I frame runs
 on the CPU and moves `y_conditioned` to the GPU for the P frames (:196-207); here everything stays on the models' device.
 The script's last line reads out_dec["entropy_params"], a key the reference model's decompress() does not return
 (spatiotemporalpriors.py:1012 -> KeyError at :152 as shipped); the key is returned holding None.
@@ -81,6 +82,30 @@ def ms_ssim(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0):
     return float(torch.prod(torch.stack(terms) ** w, dim=0).mean())
 
 
+def ms_ssim_device(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0):
+    """`ms_ssim` of two device batches by the HIP kernel (functional.ms_ssim): same contract -- a float, the mean over channels
+    and batch, or None when the smaller side is <= 160 pixels.  One host read of the result."""
+    from . import functional
+    if min(x.shape[-2:]) <= (11 - 1) * 2 ** 4:
+        return None
+    return float(functional.ms_ssim(x.float(), y.float(), data_range)[0].double().mean())
+
+
+def _metrics(x, x_hat, with_msssim):
+    """("psnr", "ms-ssim") of one frame.  with_msssim: True = host `ms_ssim`, False = none, "device" = both numbers from one
+    stem_ms_ssim call (its mean squared error is PSNR's), read back together; frames without a fifth scale fall to `psnr`."""
+    if isinstance(with_msssim, str):
+        if with_msssim != "device":
+            raise ValueError(f'with_msssim is True, False or "device", got {with_msssim!r}')
+        if min(x.shape[-2:]) > (11 - 1) * 2 ** 4:
+            from . import functional
+            ms, mse = functional.ms_ssim(x.float(), x_hat.float(), 1.0)
+            ms, mse = torch.stack((ms.double().mean(), mse.double().mean())).tolist()
+            return -10 * math.log10(mse), ms
+        return psnr(x, x_hat), None
+    return psnr(x, x_hat), (ms_ssim(x, x_hat, data_range=1.0) if with_msssim else None)
+
+
 def _sync(t):
     if t.is_cuda:
         torch.cuda.synchronize(t.device)
@@ -112,7 +137,8 @@ def inference_iframe(model, x, with_msssim=True):
     x_hat = bitstream.crop(out_dec["x_hat"], (h, w))
     num_pixels = x.size(0) * h * w
     bpp, est = _bpp_terms(out_enc, out_forward, num_pixels)
-    return {"y_conditioned": out_dec["y_hat"], "psnr": psnr(x, x_hat), "ms-ssim": ms_ssim(x, x_hat, data_range=1.0) if with_msssim else None, "bpp": bpp,
+    quality = _metrics(x, x_hat, with_msssim)
+    return {"y_conditioned": out_dec["y_hat"], "psnr": quality[0], "ms-ssim": quality[1], "bpp": bpp,
             "estimate_bpp": sum(est.values()),
             "estimate_y_bpp": est.get("y"), "estimate_z_bpp": est.get("z"), "y_bpp": len(out_enc["strings"][0][0]) * 8.0 / num_pixels,
             "z_bpp": len(out_enc["strings"][1][0]) * 8.0 / num_pixels, "encoding_time": enc_time, "decoding_time": dec_time,
@@ -142,7 +168,8 @@ def inference_pframe(imodel, stem, x, y_conditioned, with_msssim=True):
     x_hat = bitstream.crop(x_hat, (h, w))
     num_pixels = x.size(0) * h * w
     bpp, est = _bpp_terms(out_enc, out_forward, num_pixels)
-    return {"y_conditioned": y_hat, "psnr": psnr(x, x_hat), "ms-ssim": ms_ssim(x, x_hat, data_range=1.0) if with_msssim else None, "bpp": bpp,
+    quality = _metrics(x, x_hat, with_msssim)
+    return {"y_conditioned": y_hat, "psnr": quality[0], "ms-ssim": quality[1], "bpp": bpp,
             "estimate_bpp": sum(est.values()),
             "estimate_y_bpp": est.get("y"), "estimate_z_bpp": est.get("z"), "y_bpp": len(out_enc["strings"][0][0]) * 8.0 / num_pixels,
             "z_bpp": len(out_enc["strings"][1][0]) * 8.0 / num_pixels, "encoding_time": enc_time, "decoding_time": dec_time,
@@ -156,7 +183,8 @@ def eval_gop(imodel, stem, frames, gop=12, all_intra=False, with_msssim=True):
     (1-based) with k % gop == 1 is an I frame, every other one a P frame conditioned on the previous frame's decoded latents
     (stem/evalSTEM.py:186-209; gop = 12 for UVG, 10 for the HEVC classes).  Returns the per-frame dictionaries of the two
     inference functions (plus "type") and the sequence averages the script logs (:217-224).  with_msssim=False leaves the host-side
-    MS-SSIM out (a reporting metric next to the codec path, ~0.3 s per 1080p frame on the host)."""
+    MS-SSIM out (a reporting metric next to the codec path, ~0.3 s per 1080p frame on the host); with_msssim="device" takes "ms-ssim"
+    and "psnr" of every frame from the HIP kernel instead (`_metrics`)."""
     per_frame, y_cond = [], None
     for index, x in enumerate(frames, start=1):
         if all_intra or index % gop == 1 or y_cond is None:

@@ -1076,6 +1076,38 @@ def weighted_sqerr_sum(xhat, x, lam):
     return acc.reshape(())
 
 
+_MS_SSIM_WORKSPACES = {}
+
+
+def ms_ssim(x, y, data_range=1.0, return_terms=False):
+    """MS-SSIM and mean squared error of two image batches [B,C,H,W] (stem/evalSTEM.py:81,147 and :29-31; the arithmetic of
+    evaluation.ms_ssim with fp64 window means) -> (ms_ssim[B], mse[B]) fp32 device tensors, plus terms[B,C,5] (the clamped per-scale
+    means before exponentiation) with return_terms.  No host synchronisation.  ValueError for frames without a fifth scale
+    (smaller side <= 160).  The workspace is kept per (device, shape): a second call on the same stream re-uses it."""
+    x, y = x.detach().float(), y.detach().float()
+    _require_cuda(x, y)
+    if x.dim() != 4 or x.shape != y.shape:
+        raise ValueError(f"ms_ssim takes two [B,C,H,W] batches of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    B, Cc, H, W = x.shape
+    if min(H, W) <= 160:
+        raise ValueError(f"ms_ssim: {H} x {W} frames have no fifth scale (the smaller side must exceed 160)")
+    if not data_range > 0:
+        raise ValueError(f"ms_ssim: data_range must be positive, got {data_range}")
+    x, y = x.contiguous(), y.contiguous()
+    key = (x.device, B, Cc, H, W)
+    ws = _MS_SSIM_WORKSPACES.get(key)
+    if ws is None:
+        n = C.c_size_t(0)
+        _chk(_lib.hip().stem_ms_ssim_workspace(B, Cc, H, W, C.byref(n)))
+        ws = _MS_SSIM_WORKSPACES[key] = torch.empty(n.value, dtype=torch.uint8, device=x.device)
+    out = torch.empty(B, dtype=torch.float32, device=x.device)
+    mse = torch.empty(B, dtype=torch.float32, device=x.device)
+    terms = torch.empty((B, Cc, 5), dtype=torch.float32, device=x.device) if return_terms else None
+    _chk(_lib.hip().stem_ms_ssim(x.data_ptr(), y.data_ptr(), B, Cc, H, W, float(data_range), ws.data_ptr(), ws.numel(), out.data_ptr(),
+                                 mse.data_ptr(), None if terms is None else terms.data_ptr(), _stream()))
+    return (out, mse, terms) if return_terms else (out, mse)
+
+
 def weighted_sqerr_bwd(xhat, x, lam, g, coef):
     B, Cc, H, W = xhat.shape
     g = g.to(torch.float64).contiguous()
