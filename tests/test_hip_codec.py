@@ -119,7 +119,7 @@ def test_fused_decode_loop_equals_stepwise_entry_points(cls_name, monkeypatch):
 
 def test_lockstep_batch_decode_equals_per_image_decode(monkeypatch):
     """decompress() of a batch: by default one persistent decoder per image, all five at once on an XCD each
-    (codec._decode_concurrently); STEM_AR_CONCURRENT=0 / STEM_AR_FORCE_BATCH=1: the images advance in lockstep
+    (codec._Decode.concurrent); STEM_AR_CONCURRENT=0 / STEM_AR_FORCE_BATCH=1: the images advance in lockstep
     (stem_ar_decode_batch); STEM_AR_NO_BATCH=1: one image after the other.  Per image every route must reproduce what the
     per-position loop (stem_ar_decode_image, the reference's order) decodes, bit for bit -- 5 images, non-square."""
     import spatiotemporalentropymodel_amd.models as M

@@ -570,6 +570,43 @@ def test_layerwise_plan_hands_planes_between_fp16_convolutions():
         FusedSequential(pair[0], torch.nn.Sigmoid()).plan((4, 64, 16, 16), "nhwc", True, True)
 
 
+def test_decode_route_reproduces_the_decoder_form_table():
+    """codec.decode_route (pure: no library is asked) against the boolean expressions the decoder evaluated in line before the
+    route was decided in one place (codec.py:317-325, 331, 356, 364, 372 at commit f75d243), transcribed below: every combination
+    of the five ar_* switches x B in {1, 2, 5} x persistent_ok x force_loop, 384 cases; all five kinds occur."""
+    import itertools
+    from spatiotemporalentropymodel_amd import codec, config
+
+    def transcription(B, cfg, persistent_ok, _FORCE_LOOP):
+        stepwise = cfg.ar_stepwise
+        lockstep = (B > 1 or cfg.ar_force_batch) and not stepwise and not cfg.ar_no_batch
+        persistent = (cfg.ar_persistent and not _FORCE_LOOP and not stepwise
+                      and persistent_ok)
+        if _FORCE_LOOP:
+            lockstep = False
+        concurrent = False
+        if B > 1 and persistent and cfg.ar_concurrent and not cfg.ar_force_batch and not cfg.ar_no_batch:
+            concurrent = True                   # _decode_concurrently(...)
+            lockstep = False
+        # what an image the batch form did not decode gets: `for b, s in enumerate(strings[0] if not lockstep else [])`
+        image = "stepwise" if stepwise else "persistent" if persistent else "loop"
+        return ("concurrent" if concurrent else "lockstep" if lockstep else None), image
+
+    names = ("ar_persistent", "ar_stepwise", "ar_force_batch", "ar_concurrent", "ar_no_batch")
+    seen, cases = set(), 0
+    for bits in itertools.product((False, True), repeat=5):
+        cfg = config.StemRuntimeConfig(**dict(zip(names, bits)))
+        for B, ok, force in itertools.product((1, 2, 5), (False, True), (False, True)):
+            batch, image = transcription(B, cfg, ok, force)
+            if batch == "concurrent":
+                assert image == "persistent"    # the images a concurrent run leaves undone are retried alone, persistently
+            kind = codec.decode_route(B, cfg, ok, force)
+            assert kind == (batch or image), (dict(zip(names, bits)), B, ok, force, kind, batch, image)
+            seen.add(kind)
+            cases += 1
+    assert cases == 384 and seen == {"stepwise", "concurrent", "lockstep", "persistent", "loop"}
+
+
 def test_planes_byte_count_matches_the_library():
     """F16Planes.empty sizes its storage in Python (hot path); the C ABI's stem_f16x2_planes_bytes is the definition."""
     from spatiotemporalentropymodel_amd import _lib

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The canonical launch list of the layer-wise paths: which library entry points a set of scenarios calls, in order, with every
-argument that is not an address.  Dev tool for refactors of layers.py / engine.py that must not change a launch: run it at the
+"""The canonical launch list of the layer-wise paths and the codec: which library entry points a set of scenarios calls, in order, with
+every argument that is not an address.  Dev tool for refactors of layers.py / engine.py / codec.py that must not change a launch: run it at the
 parent commit and at the new one and `diff` the two files.
 
     python tools/launch_list.py OUT.txt [scenario-name-prefix ...]
@@ -153,6 +153,33 @@ def _codec():
         enc = m.compress(x)
         m.decompress(enc["strings"], enc["shape"])
     return run
+
+
+def _stem_codec(cls_name, B):
+    """compress() then decompress() of a [B, 96, 8, 12] latent; the persistent decoder's once-per-process self-check is forgotten
+    first, so each scenario's first call lists it at the moment its route asks for it"""
+    import spatiotemporalentropymodel_amd.models as M
+    from spatiotemporalentropymodel_amd import codec
+    from spatiotemporalentropymodel_amd.weights import closed_form_fill_, closed_form_input
+    m = closed_form_fill_(getattr(M, cls_name)(64, 96)).to(DEV).eval()
+    m.update(force=True)
+    y_cur = closed_form_input("ll:y", (B, 96, 8, 12), -6, 6).to(DEV)
+    y_cond = closed_form_input("ll:c", (B, 96, 8, 12), -6, 6).to(DEV)
+    codec._ARP_TRUSTED.clear()
+
+    def run():
+        with torch.no_grad():
+            enc = m.compress(y_cur, y_cond)
+            m.decompress(enc["strings"], enc["shape"], y_cond)
+    return run
+
+
+# every form of the decoder's loop (codec.decode_route); B=3 with the defaults issues its launches from worker threads: compare
+# that scenario's lines sorted
+for cls_name in ("SpatioTemporalPriorModel_Res", "SpatioTemporalPriorModelWithoutTPM"):
+    for B, cfg in ((1, {}), (1, {"ar_persistent": False}), (1, {"ar_stepwise": True}), (1, {"ar_force_batch": True}),
+                   (3, {}), (3, {"ar_concurrent": False}), (3, {"ar_no_batch": True, "ar_persistent": False})):
+        scenario(f"STEM codec {cls_name} B={B} {cfg}", **cfg)(lambda cls_name=cls_name, B=B: _stem_codec(cls_name, B))
 
 
 @scenario("STEM P-frame step, small geometry")
