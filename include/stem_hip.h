@@ -617,6 +617,17 @@ int stem_ms_ssim(const float *x, const float *y, int B, int C, int H, int W, flo
                  void *workspace, size_t workspace_bytes,
                  float *ms_ssim /* [B] */, float *mse /* [B], may be NULL */, float *terms /* [B][C][5], may be NULL */,
                  void *stream);
+/* d ms_ssim[b] / d x of the function above, times grad_ms[b]: one launch per scale, coarse to fine, fp64 window means and adjoint sums,
+ * no atomics (bit-reproducible, independent of the batch around an image); a channel with a clamped term gets exactly 0.
+ * `fwd_workspace` is the workspace as stem_ms_ssim left it on the same x, y (the pooled planes of scales 2-5 and the clamped means
+ * are read from it); `workspace`: stem_ms_ssim_bwd_workspace() bytes, 8-byte aligned, nothing to initialise (the fp64 gradient
+ * planes of scales 2-5).  The gradient with respect to y is the same call with x and y swapped and the forward workspace of the
+ * swapped call.  No host synchronisation. */
+int stem_ms_ssim_bwd_workspace(int B, int C, int H, int W, size_t *bytes);
+int stem_ms_ssim_bwd(const float *x, const float *y, int B, int C, int H, int W, float data_range,
+                     const void *fwd_workspace, size_t fwd_workspace_bytes,
+                     const float *grad_ms /* [B] */, void *workspace, size_t workspace_bytes,
+                     float *dx /* [B,C,H,W], overwritten */, void *stream);
 
 #ifdef __cplusplus
 }

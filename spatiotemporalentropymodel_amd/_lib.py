@@ -136,6 +136,8 @@ _HIP_SIG = {
                              vp, vp, vp],
     "stem_ms_ssim_workspace": [ci, ci, ci, ci, vp],
     "stem_ms_ssim": [vp, vp, ci, ci, ci, ci, cf, vp, sz, vp, vp, vp, vp],
+    "stem_ms_ssim_bwd_workspace": [ci, ci, ci, ci, vp],
+    "stem_ms_ssim_bwd": [vp, vp, ci, ci, ci, ci, cf, vp, sz, vp, vp, sz, vp, vp],
     "stem_sumsq": [vp, sz, vp, vp],
     "stem_sumsq_set": [vp, sz, vp, vp],
     "stem_clip_scale": [vp, sz, vp, cf, vp],

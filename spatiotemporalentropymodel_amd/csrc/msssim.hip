@@ -330,3 +330,288 @@ STEM_EXPORT int stem_ms_ssim(const float *x, const float *y, int B, int C, int H
     STEM_LAUNCH_CHECK("stem_ms_ssim");
     return 0;
 }
+
+// ---- backward: d ms_ssim[b] / d x ------------------------------------------------------------------------------------------------
+// The function differentiated is exactly the one above.  With m_{s,c} the clamped mean of scale s and channel c and
+// P_c = prod_s m_{s,c}^{w_s}, d ms / d m_{s,c} = w_s P_c / (C m_{s,c}); a channel with any clamped term has P_c = 0 and a gradient
+// of exactly 0.  Per scale, with f the per-pixel cs (ssim on scale 5) as a function of the window means mu1 = G[x], e11 = G[x*x],
+// e12 = G[x*y], the gradient at that scale's resolution is  G^T[k f_mu1] + 2x G^T[k f_e11] + y G^T[k f_e12]  (k = grad_ms[b] *
+// d ms / d m / number of filtered pixels; G^T the "full" correlation with the same window) plus the pooling adjoint of the coarser
+// scale's gradient: pixel (r, c) takes a quarter of coarse pixel ((r + H % 2) / 2, (c + W % 2) / 2).
+//
+// One launch per scale, coarse to fine; a 512-thread workgroup owns one 32 x 32 tile of one plane of that scale's gradient:
+//   1. the 52 x 52 halo of x and y (origin 10 above / left of the tile) goes to LDS, zero beyond the plane;
+//   2. horizontal pass of the five quantities, 52 rows x 42 columns, fp64 -> LDS;
+//   3. vertical pass on the 42 x 42 ring of filtered pixels the tile's adjoint reaches, the three coefficient maps in fp64 -> LDS
+//      (zero where the ring leaves the filtered map);
+//   4. adjoint vertical pass (42 -> 32 rows, over the memory of step 2), adjoint horizontal pass in registers;
+//   5. + a quarter of the coarser scale's gradient; one plain store per pixel (fp64 planes of scales 2-5 in the workspace, fp32 dx).
+// Every LDS index is linear in the work-item number: fp64 rows are read 32 consecutive doubles per half-wave, one bank row.
+// No atomics; nothing depends on the batch around an image.
+namespace {
+
+constexpr int MB_THREADS = 512;
+constexpr int MB_RING = MS_T + MS_TAPS - 1;        // 42: filtered pixels per side that reach the tile
+constexpr int MB_HALO = MB_RING + MS_TAPS - 1;     // 52: input pixels per side under that ring
+constexpr int MB_PITCH = MB_HALO + 1;              // 53 floats
+
+struct MsBwdScale {
+    int H, W;                                      // plane size at this scale
+    int nty, ntx;                                  // tiles of the H x W gradient plane
+    int scale;                                     // 0 .. 4
+};
+
+// per plane and scale: grad_ms[b] * w_s * P_c / (C * m_{s,c} * count_s); 0 for every scale of a channel with a clamped term
+struct MsInvCount {
+    double v[MS_SCALES];
+};
+__global__ __launch_bounds__(256) void msssim_bwd_coef_kernel(const double *__restrict__ mean, const float *__restrict__ grad_ms, int planes,
+                                                              int C, MsInvCount inv, double *__restrict__ coef)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= planes) return;
+    double m[MS_SCALES], prod = 1.0;
+    bool alive = true;
+#pragma unroll
+    for (int s = 0; s < MS_SCALES; ++s) {
+        m[s] = mean[(size_t)p * MS_SCALES + s];
+        alive = alive && m[s] > 0.0;
+        prod *= pow(m[s], kExponent[s]);
+    }
+    const double g = (double)grad_ms[p / C];
+    double k[MS_SCALES];
+#pragma unroll
+    for (int s = 0; s < MS_SCALES; ++s) {
+        k[s] = alive ? g * kExponent[s] * prod * inv.v[s] / ((double)C * m[s]) : 0.0;
+        alive = alive && isfinite(k[s]);
+    }
+#pragma unroll
+    for (int s = 0; s < MS_SCALES; ++s) coef[(size_t)p * MS_SCALES + s] = alive ? k[s] : 0.0;
+}
+
+// derivatives of cs (scales 1-4) or ssim (scale 5) of one pixel with respect to mu1, e11, e12.  Contraction off, as in ssim_pixel.
+template <bool FULL>
+__device__ inline void ssim_pixel_grad(double mu1, double mu2, double e11, double e22, double e12, double C1, double C2, double &d_mu1,
+                                       double &d_e11, double &d_e12)
+{
+#pragma clang fp contract(off)
+    const double m11 = mu1 * mu1, m22 = mu2 * mu2, m12 = mu1 * mu2;
+    const double s11 = e11 - m11, s22 = e22 - m22, s12 = e12 - m12;
+    const double den = (s11 + s22) + C2, cs = (2.0 * s12 + C2) / den;
+    const double c_mu1 = 2.0 * (cs * mu1 - mu2) / den, c_e11 = -cs / den, c_e12 = 2.0 / den;
+    if (!FULL) {
+        d_mu1 = c_mu1;
+        d_e11 = c_e11;
+        d_e12 = c_e12;
+        return;
+    }
+    const double lden = (m11 + m22) + C1, l = (2.0 * m12 + C1) / lden;
+    const double l_mu1 = 2.0 * (mu2 - l * mu1) / lden;
+    d_mu1 = l_mu1 * cs + l * c_mu1;
+    d_e11 = l * c_e11;
+    d_e12 = l * c_e12;
+}
+
+// x, y: [planes][H][W] of this scale; coef: [planes][5]; gc: [planes][(H+1)/2][(W+1)/2] fp64 gradient of the next scale (COARSE);
+// out: [planes][H][W], fp64 (workspace) or fp32 (dx)
+template <bool FULL, bool COARSE, typename OutT>
+__global__ __launch_bounds__(MB_THREADS) void msssim_bwd_scale_kernel(const float *__restrict__ x, const float *__restrict__ y, MsBwdScale sc,
+                                                                      MsWindow win, double C1, double C2, const double *__restrict__ coef,
+                                                                      const double *__restrict__ gc, OutT *__restrict__ out)
+{
+    __shared__ float xs[MB_HALO][MB_PITCH], ys[MB_HALO][MB_PITCH];
+    __shared__ double hb[5 * MB_HALO * MB_RING];                       // [5][52][42]; later the adjoint's [3][32][42]
+    __shared__ double qm[3][MB_RING][MB_RING];
+
+    const int ntiles = sc.nty * sc.ntx;
+    const int plane = blockIdx.x / ntiles, tile = blockIdx.x - plane * ntiles;
+    const int ty = tile / sc.ntx, tx = tile - ty * sc.ntx;
+    const int H = sc.H, W = sc.W, Ho = H - (MS_TAPS - 1), Wo = W - (MS_TAPS - 1);
+    const int oy0 = ty * MS_T, ox0 = tx * MS_T;
+    const int hy0 = oy0 - (MS_TAPS - 1), hx0 = ox0 - (MS_TAPS - 1);   // origin of the halo and of the ring
+    const float *xp = x + (size_t)plane * H * W, *yp = y + (size_t)plane * H * W;
+    const double k = coef[(size_t)plane * MS_SCALES + sc.scale];      // the same for the whole workgroup
+
+    double acc[2][3];                                                  // the three adjoints of this thread's two pixels
+#pragma unroll
+    for (int o = 0; o < 2; ++o) acc[o][0] = acc[o][1] = acc[o][2] = 0.0;
+
+    if (k != 0.0) {
+        // 1. halo -> LDS, zero beyond the plane (those pixels only feed ring positions that are masked out in step 3)
+        for (int i = threadIdx.x; i < MB_HALO * MB_HALO; i += MB_THREADS) {
+            const int r = i / MB_HALO, c = i - r * MB_HALO;
+            const int gy = hy0 + r, gx = hx0 + c;
+            const bool ok = gy >= 0 && gy < H && gx >= 0 && gx < W;
+            const size_t g = ok ? (size_t)gy * W + gx : 0;
+            xs[r][c] = ok ? xp[g] : 0.f;
+            ys[r][c] = ok ? yp[g] : 0.f;
+        }
+        __syncthreads();
+
+        double w[MS_TAPS];
+#pragma unroll
+        for (int t = 0; t < MS_TAPS; ++t) w[t] = (double)win.w[t];
+
+        // 2. horizontal pass, as the forward's: 52 rows x 42 columns of the five quantities
+        for (int i = threadIdx.x; i < MB_HALO * MB_RING; i += MB_THREADS) {
+            const int r = i / MB_RING, c = i - r * MB_RING;
+            double a = 0.0, b = 0.0, aa = 0.0, bb = 0.0, ab = 0.0;
+#pragma unroll
+            for (int t = 0; t < MS_TAPS; ++t) {
+                const double xv = (double)xs[r][c + t], yv = (double)ys[r][c + t];
+                a += w[t] * xv;
+                b += w[t] * yv;
+                aa += w[t] * (xv * xv);
+                bb += w[t] * (yv * yv);
+                ab += w[t] * (xv * yv);
+            }
+            hb[0 * MB_HALO * MB_RING + i] = a;
+            hb[1 * MB_HALO * MB_RING + i] = b;
+            hb[2 * MB_HALO * MB_RING + i] = aa;
+            hb[3 * MB_HALO * MB_RING + i] = bb;
+            hb[4 * MB_HALO * MB_RING + i] = ab;
+        }
+        __syncthreads();
+
+        // 3. vertical pass on the ring; k * (f_mu1, f_e11, f_e12), zero outside the filtered map
+        for (int i = threadIdx.x; i < MB_RING * MB_RING; i += MB_THREADS) {
+            const int r = i / MB_RING, c = i - r * MB_RING;
+            double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int t = 0; t < MS_TAPS; ++t)
+#pragma unroll
+                for (int q = 0; q < 5; ++q) v[q] += w[t] * hb[q * MB_HALO * MB_RING + i + t * MB_RING];
+            const int my = hy0 + r, mx = hx0 + c;
+            const bool ok = my >= 0 && my < Ho && mx >= 0 && mx < Wo;
+            double d0, d1, d2;
+            ssim_pixel_grad<FULL>(v[0], v[1], v[2], v[3], v[4], C1, C2, d0, d1, d2);
+            qm[0][r][c] = ok ? k * d0 : 0.0;
+            qm[1][r][c] = ok ? k * d1 : 0.0;
+            qm[2][r][c] = ok ? k * d2 : 0.0;
+        }
+        __syncthreads();
+
+        // 4a. adjoint, vertical: output row ro takes ring rows ro .. ro + 10 with the window reversed -> [3][32][42] over hb
+        for (int i = threadIdx.x; i < MS_T * MB_RING; i += MB_THREADS) {
+            double v[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int t = 0; t < MS_TAPS; ++t)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) v[q] += w[MS_TAPS - 1 - t] * (&qm[q][0][0])[i + t * MB_RING];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) hb[q * MS_T * MB_RING + i] = v[q];
+        }
+        __syncthreads();
+
+        // 4b. adjoint, horizontal: two pixels per thread, 16 rows apart
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            const int i = threadIdx.x + o * MB_THREADS, r = i >> 5, c = i & 31;
+#pragma unroll
+            for (int t = 0; t < MS_TAPS; ++t)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) acc[o][q] += w[MS_TAPS - 1 - t] * hb[q * MS_T * MB_RING + r * MB_RING + c + t];
+        }
+    }
+
+    // 5. the pixel's own factors, the pooled adjoint, one store
+    const int padh = H & 1, padw = W & 1, Wp = (W + 1) >> 1;
+    const size_t cplane = (size_t)plane * ((H + 1) >> 1) * Wp;
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+        const int i = threadIdx.x + o * MB_THREADS, r = i >> 5, c = i & 31;
+        const int gy = oy0 + r, gx = ox0 + c;
+        if (gy >= H || gx >= W) continue;
+        double g = 0.0;
+        if (k != 0.0) {
+#pragma clang fp contract(off)
+            const double xv = (double)xs[r + MS_TAPS - 1][c + MS_TAPS - 1], yv = (double)ys[r + MS_TAPS - 1][c + MS_TAPS - 1];
+            g = (acc[o][0] + (2.0 * xv) * acc[o][1]) + yv * acc[o][2];
+        }
+        if (COARSE) g += 0.25 * gc[cplane + (size_t)((gy + padh) >> 1) * Wp + ((gx + padw) >> 1)];
+        out[(size_t)plane * H * W + (size_t)gy * W + gx] = (OutT)g;
+    }
+}
+
+// the backward's workspace: the coefficients, then the fp64 gradient planes of scales 2-5
+struct MsBwdPlan {
+    MsBwdScale sc[MS_SCALES];
+    size_t coef, grad[MS_SCALES], bytes;
+};
+
+int ms_bwd_plan(const char *who, int B, int C, const MsPlan &f, MsBwdPlan *p)
+{
+    const size_t planes = (size_t)B * C;
+    size_t off = 0;
+    p->coef = off;
+    off += align256(planes * MS_SCALES * sizeof(double));
+    for (int s = 0; s < MS_SCALES; ++s) {
+        const int h = f.sc[s].H, w = f.sc[s].W;
+        p->sc[s] = {h, w, cdiv(h, MS_T), cdiv(w, MS_T), s};
+        STEM_CHECK_ARG(planes * p->sc[s].nty * p->sc[s].ntx < (size_t)1 << 31, "%s: [%d,%d,%d,%d] is too large", who, B, C, f.sc[0].H, f.sc[0].W);
+        p->grad[s] = off;
+        if (s) off += align256(planes * h * w * sizeof(double));
+    }
+    p->bytes = off;
+    return 0;
+}
+
+}   // namespace
+
+STEM_EXPORT int stem_ms_ssim_bwd_workspace(int B, int C, int H, int W, size_t *bytes)
+{
+    STEM_CHECK_ARG(bytes, "stem_ms_ssim_bwd_workspace: null pointer");
+    MsPlan f;
+    if (int rc = ms_plan("stem_ms_ssim_bwd_workspace", B, C, H, W, &f)) return rc;
+    MsBwdPlan p;
+    if (int rc = ms_bwd_plan("stem_ms_ssim_bwd_workspace", B, C, f, &p)) return rc;
+    *bytes = p.bytes;
+    return 0;
+}
+
+STEM_EXPORT int stem_ms_ssim_bwd(const float *x, const float *y, int B, int C, int H, int W, float data_range, const void *fwd_workspace,
+                                 size_t fwd_workspace_bytes, const float *grad_ms, void *workspace, size_t workspace_bytes, float *dx,
+                                 void *stream)
+{
+    STEM_CHECK_ARG(x && y && fwd_workspace && grad_ms && workspace && dx, "stem_ms_ssim_bwd: null pointer");
+    STEM_CHECK_ARG(data_range > 0.f, "stem_ms_ssim_bwd: data_range must be positive, got %g", (double)data_range);
+    MsPlan f;
+    if (int rc = ms_plan("stem_ms_ssim_bwd", B, C, H, W, &f)) return rc;
+    MsBwdPlan p;
+    if (int rc = ms_bwd_plan("stem_ms_ssim_bwd", B, C, f, &p)) return rc;
+    STEM_CHECK_ARG(fwd_workspace_bytes >= f.bytes, "stem_ms_ssim_bwd: forward workspace of %zu bytes, %zu needed (stem_ms_ssim_workspace)",
+                   fwd_workspace_bytes, f.bytes);
+    STEM_CHECK_ARG(workspace_bytes >= p.bytes, "stem_ms_ssim_bwd: workspace of %zu bytes, %zu needed (stem_ms_ssim_bwd_workspace)", workspace_bytes,
+                   p.bytes);
+    STEM_CHECK_ARG(((((uintptr_t)workspace) | ((uintptr_t)fwd_workspace)) & 7) == 0, "stem_ms_ssim_bwd: workspaces must be 8-byte aligned");
+
+    const char *fws = static_cast<const char *>(fwd_workspace);
+    char *ws = static_cast<char *>(workspace);
+    const int planes = B * C;
+    const double C1 = (0.01 * (double)data_range) * (0.01 * (double)data_range), C2 = (0.03 * (double)data_range) * (0.03 * (double)data_range);
+    hipStream_t st = (hipStream_t)stream;
+    double *coef = reinterpret_cast<double *>(ws + p.coef);
+    MsInvCount inv;
+    for (int s = 0; s < MS_SCALES; ++s) inv.v[s] = 1.0 / ((double)(f.sc[s].H - (MS_TAPS - 1)) * (double)(f.sc[s].W - (MS_TAPS - 1)));
+    hipLaunchKernelGGL(msssim_bwd_coef_kernel, dim3(cdiv(planes, 256)), dim3(256), 0, st, reinterpret_cast<const double *>(fws + f.mean), grad_ms,
+                       planes, C, inv, coef);
+    STEM_LAUNCH_CHECK("stem_ms_ssim_bwd");
+    for (int s = MS_SCALES - 1; s >= 0; --s) {
+        const MsBwdScale &sc = p.sc[s];
+        const size_t plane_bytes = align256((size_t)planes * sc.H * sc.W * sizeof(float));
+        const float *xs = s ? reinterpret_cast<const float *>(fws + f.pyr[s]) : x;
+        const float *ys = s ? reinterpret_cast<const float *>(fws + f.pyr[s] + plane_bytes) : y;
+        const double *gc = s + 1 < MS_SCALES ? reinterpret_cast<const double *>(ws + p.grad[s + 1]) : nullptr;
+        const dim3 grid((unsigned)(planes * sc.nty * sc.ntx)), block(MB_THREADS);
+        if (s == MS_SCALES - 1)
+            hipLaunchKernelGGL((msssim_bwd_scale_kernel<true, false, double>), grid, block, 0, st, xs, ys, sc, kWindow, C1, C2, coef, gc,
+                               reinterpret_cast<double *>(ws + p.grad[s]));
+        else if (s)
+            hipLaunchKernelGGL((msssim_bwd_scale_kernel<false, true, double>), grid, block, 0, st, xs, ys, sc, kWindow, C1, C2, coef, gc,
+                               reinterpret_cast<double *>(ws + p.grad[s]));
+        else
+            hipLaunchKernelGGL((msssim_bwd_scale_kernel<false, true, float>), grid, block, 0, st, xs, ys, sc, kWindow, C1, C2, coef, gc, dx);
+        STEM_LAUNCH_CHECK("stem_ms_ssim_bwd");
+    }
+    return 0;
+}

@@ -1079,33 +1079,80 @@ def weighted_sqerr_sum(xhat, x, lam):
 _MS_SSIM_WORKSPACES = {}
 
 
+def _ms_ssim_check(x, y, data_range, who):
+    """argument checks of the MS-SSIM entry points -> contiguous fp32 x, y"""
+    x, y = x.detach().float(), y.detach().float()
+    _require_cuda(x, y)
+    if x.dim() != 4 or x.shape != y.shape:
+        raise ValueError(f"{who} takes two [B,C,H,W] batches of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    H, W = x.shape[2:]
+    if min(H, W) <= 160:
+        raise ValueError(f"{who}: {H} x {W} frames have no fifth scale (the smaller side must exceed 160)")
+    if not data_range > 0:
+        raise ValueError(f"{who}: data_range must be positive, got {data_range}")
+    return x.contiguous(), y.contiguous()
+
+
+def _ms_ssim_workspace(x, which="stem_ms_ssim_workspace", cached=True):
+    """the workspace of one stem_ms_ssim / stem_ms_ssim_bwd call on batches shaped like x; cached=True: kept per (device, shape)"""
+    key = (which, x.device) + tuple(x.shape)
+    ws = _MS_SSIM_WORKSPACES.get(key) if cached else None
+    if ws is None:
+        n = C.c_size_t(0)
+        _chk(getattr(_lib.hip(), which)(*x.shape, C.byref(n)))
+        ws = torch.empty(n.value, dtype=torch.uint8, device=x.device)
+        if cached:
+            _MS_SSIM_WORKSPACES[key] = ws
+    return ws
+
+
+def _ms_ssim_run(x, y, data_range, ws, want_mse=True, want_terms=False):
+    """one stem_ms_ssim call on checked inputs into workspace `ws` -> (ms_ssim[B], mse[B] or None, terms[B,C,5] or None)"""
+    B, Cc, H, W = x.shape
+    out = torch.empty(B, dtype=torch.float32, device=x.device)
+    mse = torch.empty(B, dtype=torch.float32, device=x.device) if want_mse else None
+    terms = torch.empty((B, Cc, 5), dtype=torch.float32, device=x.device) if want_terms else None
+    _chk(_lib.hip().stem_ms_ssim(x.data_ptr(), y.data_ptr(), B, Cc, H, W, float(data_range), ws.data_ptr(), ws.numel(), out.data_ptr(),
+                                 None if mse is None else mse.data_ptr(), None if terms is None else terms.data_ptr(), _stream()))
+    return out, mse, terms
+
+
 def ms_ssim(x, y, data_range=1.0, return_terms=False):
     """MS-SSIM and mean squared error of two image batches [B,C,H,W] (stem/evalSTEM.py:81,147 and :29-31; the arithmetic of
     evaluation.ms_ssim with fp64 window means) -> (ms_ssim[B], mse[B]) fp32 device tensors, plus terms[B,C,5] (the clamped per-scale
     means before exponentiation) with return_terms.  No host synchronisation.  ValueError for frames without a fifth scale
     (smaller side <= 160).  The workspace is kept per (device, shape): a second call on the same stream re-uses it."""
-    x, y = x.detach().float(), y.detach().float()
-    _require_cuda(x, y)
-    if x.dim() != 4 or x.shape != y.shape:
-        raise ValueError(f"ms_ssim takes two [B,C,H,W] batches of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
-    B, Cc, H, W = x.shape
-    if min(H, W) <= 160:
-        raise ValueError(f"ms_ssim: {H} x {W} frames have no fifth scale (the smaller side must exceed 160)")
-    if not data_range > 0:
-        raise ValueError(f"ms_ssim: data_range must be positive, got {data_range}")
-    x, y = x.contiguous(), y.contiguous()
-    key = (x.device, B, Cc, H, W)
-    ws = _MS_SSIM_WORKSPACES.get(key)
-    if ws is None:
-        n = C.c_size_t(0)
-        _chk(_lib.hip().stem_ms_ssim_workspace(B, Cc, H, W, C.byref(n)))
-        ws = _MS_SSIM_WORKSPACES[key] = torch.empty(n.value, dtype=torch.uint8, device=x.device)
-    out = torch.empty(B, dtype=torch.float32, device=x.device)
-    mse = torch.empty(B, dtype=torch.float32, device=x.device)
-    terms = torch.empty((B, Cc, 5), dtype=torch.float32, device=x.device) if return_terms else None
-    _chk(_lib.hip().stem_ms_ssim(x.data_ptr(), y.data_ptr(), B, Cc, H, W, float(data_range), ws.data_ptr(), ws.numel(), out.data_ptr(),
-                                 mse.data_ptr(), None if terms is None else terms.data_ptr(), _stream()))
+    x, y = _ms_ssim_check(x, y, data_range, "ms_ssim")
+    out, mse, terms = _ms_ssim_run(x, y, data_range, _ms_ssim_workspace(x), want_terms=return_terms)
     return (out, mse, terms) if return_terms else (out, mse)
+
+
+def ms_ssim_forward_keep(x, y, data_range=1.0):
+    """ms_ssim for a caller that differentiates later (losses.ms_ssim): -> (ms_ssim[B], workspace).  The workspace is this call's
+    own, not the cached one, so it still holds this pair's pyramid and means when ms_ssim_backward reads it."""
+    x, y = _ms_ssim_check(x, y, data_range, "ms_ssim")
+    ws = _ms_ssim_workspace(x, cached=False)
+    return _ms_ssim_run(x, y, data_range, ws, want_mse=False)[0], ws
+
+
+def ms_ssim_backward(x, y, grad_ms, data_range=1.0, fwd_workspace=None):
+    """sum_b grad_ms[b] * d ms_ssim(x, y)[b] / d x -> dx [B,C,H,W] fp32 (stem_ms_ssim_bwd: fp64 window means and adjoint sums, no
+    atomics, no host synchronisation).  `fwd_workspace`: the workspace ms_ssim_forward_keep(x, y, data_range) returned; without it
+    the forward runs here first.  The gradient with respect to y is ms_ssim_backward(y, x, ...)."""
+    x, y = _ms_ssim_check(x, y, data_range, "ms_ssim_backward")
+    B, Cc, H, W = x.shape
+    grad_ms = grad_ms.detach().float().contiguous()
+    _require_cuda(grad_ms)
+    if grad_ms.shape != (B,):
+        raise ValueError(f"ms_ssim_backward: grad_ms must be [{B}], got {tuple(grad_ms.shape)}")
+    if fwd_workspace is None:
+        fwd_workspace = _ms_ssim_workspace(x)
+        _ms_ssim_run(x, y, data_range, fwd_workspace, want_mse=False)
+    ws = _ms_ssim_workspace(x, "stem_ms_ssim_bwd_workspace")
+    dx = torch.empty_like(x)
+    _chk(_lib.hip().stem_ms_ssim_bwd(x.data_ptr(), y.data_ptr(), B, Cc, H, W, float(data_range), fwd_workspace.data_ptr(),
+                                     fwd_workspace.numel(), grad_ms.data_ptr(), ws.data_ptr(), ws.numel(), dx.data_ptr(), _stream()))
+    return dx
 
 
 def weighted_sqerr_bwd(xhat, x, lam, g, coef):

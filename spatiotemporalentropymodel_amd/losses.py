@@ -50,11 +50,17 @@ class EMLoss(nn.Module):
 
 class RateDistortionLoss(nn.Module):
     """utils.py:30-50: bpp + lmbda * 255^2 * MSE(x_hat, target).  The distortion term is the same fp64-accumulating
-    squared-error kernel the variable-rate criterion uses (stem_weighted_sqerr_sum / _bwd) with a unit weight map."""
+    squared-error kernel the variable-rate criterion uses (stem_weighted_sqerr_sum / _bwd) with a unit weight map.
 
-    def __init__(self, lmbda=1e-2):
+    metric="ms-ssim": bpp + lmbda * (1 - mean_b MS-SSIM(x_hat, target)), CompressAI's convention for that metric, with the keys
+    {"bpp_loss", "ms_ssim_loss", "loss"}; the distortion term is `ms_ssim` below (stem_ms_ssim / stem_ms_ssim_bwd)."""
+
+    def __init__(self, lmbda=1e-2, metric="mse"):
         super().__init__()
+        if metric not in ("mse", "ms-ssim"):
+            raise ValueError(f"RateDistortionLoss: metric must be 'mse' or 'ms-ssim', got {metric!r}")
         self.lmbda = lmbda
+        self.metric = metric
         self._ones = None
 
     def _unit_map(self, target):
@@ -69,6 +75,10 @@ class RateDistortionLoss(nn.Module):
         num_pixels = N * H * W
         out = {}
         out["bpp_loss"] = sum(log2_sum(l) / (-num_pixels) for l in output["likelihoods"].values())
+        if self.metric == "ms-ssim":
+            out["ms_ssim_loss"] = 1 - ms_ssim(output["x_hat"], target).mean()
+            out["loss"] = self.lmbda * out["ms_ssim_loss"] + out["bpp_loss"]
+            return out
         out["mse_loss"] = _WeightedMSEFunction.apply(output["x_hat"], target, self._unit_map(target))
         out["loss"] = self.lmbda * 255 ** 2 * out["mse_loss"] + out["bpp_loss"]
         return out
@@ -87,6 +97,36 @@ class _WeightedMSEFunction(torch.autograd.Function):
     def backward(ctx, g):
         x_hat, target, lmbdamap = ctx.saved_tensors
         return F.weighted_sqerr_bwd(x_hat, target, lmbdamap, g, 1.0 / x_hat.numel()), None, None
+
+
+class _MSSSIMFunction(torch.autograd.Function):
+    """ms_ssim[b] of (x_hat, target) by stem_ms_ssim; backward: one stem_ms_ssim_bwd per argument that needs a gradient.  The
+    kernel differentiates its first argument, so the target's gradient is the same call with the arguments swapped, on the
+    forward workspace of the swapped pair."""
+
+    @staticmethod
+    def forward(ctx, x_hat, target, data_range):
+        x_hat, target = x_hat.contiguous(), target.contiguous()
+        out, ws = F.ms_ssim_forward_keep(x_hat, target, data_range)
+        ctx.save_for_backward(x_hat, target, ws)
+        ctx.data_range = data_range
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x_hat, target, ws = ctx.saved_tensors
+        dx = dt = None
+        if ctx.needs_input_grad[0]:
+            dx = F.ms_ssim_backward(x_hat, target, g, ctx.data_range, fwd_workspace=ws)
+        if ctx.needs_input_grad[1]:
+            dt = F.ms_ssim_backward(target, x_hat, g, ctx.data_range)
+        return dx, dt, None
+
+
+def ms_ssim(x_hat, target, data_range=1.0):
+    """differentiable MS-SSIM of two device batches [B,C,H,W] -> [B] (functional.ms_ssim's value, bit for bit); ValueError for
+    frames without a fifth scale (smaller side <= 160), RuntimeError for CPU tensors."""
+    return _MSSSIMFunction.apply(x_hat, target, data_range)
 
 
 class PixelwiseRateDistortionLoss(nn.Module):

@@ -1,6 +1,6 @@
 """Time of the MS-SSIM / MSE kernel (stem_ms_ssim, csrc/msssim.hip) and what each `with_msssim` route adds to the evaluation loop.
 
-    python tools/metrics_bench.py [--launches 60] [--passes 3] [--out profiles/metrics_bench.json]
+    python tools/metrics_bench.py [--launches 60] [--passes 3] [--only kernel,grad,eval_gop] [--out profiles/metrics_bench.json]
 
 1. stem_ms_ssim at [1,3,1080,1920] and [8,3,1080,1920]: HIP events around every launch after a warm-up, the median of `--launches`
    (>= 50).  Bytes moved are computed from the shapes -- both images read once, the pooled planes of scales 2-5 written and read
@@ -8,6 +8,10 @@
    counted: the figure is the algorithm's traffic over the kernel's time, not a counter).
 2. evaluation.eval_gop on one synthetic 1080p GOP of 12 (the models of `bench.py --config eval`) with with_msssim = False, True and
    "device", alternating, `--passes` passes each: wall time per GOP and the cost each metric route adds per frame over False.
+3. forward + backward of the differentiable metric (stem_ms_ssim + stem_ms_ssim_bwd, as losses.ms_ssim runs them for a gradient
+   with respect to x_hat) at [16,3,256,256] and [1,3,1080,1920], and beside it torch autograd through the fp32 body of
+   evaluation.ms_ssim on the same GPU (what a user had before): HIP events around every forward + backward after a warm-up, the
+   two routes alternating, medians; the largest difference of the two gradients over the largest gradient is reported with them.
 
 Needs an MI355X: without a GPU it fails, it measures nothing on a CPU.
 """
@@ -67,6 +71,74 @@ def time_kernel(shape, launches, warmup=10):
             "ms_ssim": out.tolist(), "mse": mse.tolist()}
 
 
+def torch_ms_ssim(x, y, data_range=1.0):
+    """the fp32 body of evaluation.ms_ssim on the tensors' own device, graph attached -> [B]"""
+    from spatiotemporalentropymodel_amd.evaluation import _MS_WEIGHTS, _gauss_filter, _gauss_window
+    win = _gauss_window().to(x.device)
+    C1, C2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+    terms = []
+    for level in range(5):
+        mu1, mu2 = _gauss_filter(x, win), _gauss_filter(y, win)
+        s11 = _gauss_filter(x * x, win) - mu1 * mu1
+        s22 = _gauss_filter(y * y, win) - mu2 * mu2
+        s12 = _gauss_filter(x * y, win) - mu1 * mu2
+        cs_map = (2 * s12 + C2) / (s11 + s22 + C2)
+        if level < 4:
+            terms.append(torch.relu(cs_map.flatten(2).mean(-1)))
+            pad = [s % 2 for s in x.shape[2:]]
+            x = torch.nn.functional.avg_pool2d(x, kernel_size=2, padding=pad)
+            y = torch.nn.functional.avg_pool2d(y, kernel_size=2, padding=pad)
+        else:
+            ssim_map = (2 * mu1 * mu2 + C1) / (mu1 * mu1 + mu2 * mu2 + C1) * cs_map
+            terms.append(torch.relu(ssim_map.flatten(2).mean(-1)))
+    w = torch.tensor(_MS_WEIGHTS, device=x.device).view(-1, 1, 1)
+    return torch.prod(torch.stack(terms) ** w, dim=0).mean(1)
+
+
+def time_grad(shape, launches, warmup=5):
+    from spatiotemporalentropymodel_amd import functional as F
+    dev = torch.device("cuda", 0)
+    B = shape[0]
+    g = torch.Generator(device=dev).manual_seed(1)
+    target = torch.rand(shape, device=dev, generator=g)
+    x_hat = (target + 0.02 * torch.randn(shape, device=dev, generator=g)).clamp(0, 1)
+    up = torch.full((B,), -1.0 / B, device=dev)
+    got = {}
+
+    def hip():
+        _, ws = F.ms_ssim_forward_keep(x_hat, target)
+        got["hip"] = F.ms_ssim_backward(x_hat, target, up, fwd_workspace=ws)
+
+    def autograd():
+        xr = x_hat.clone().requires_grad_(True)
+        torch_ms_ssim(xr, target).backward(up)
+        got["torch"] = xr.grad
+
+    routes = {"hip": hip, "torch": autograd}
+    for _ in range(warmup):
+        for fn in routes.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in routes}
+    events = []
+    for _ in range(launches):
+        for k, fn in routes.items():                                                   # alternating
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            events.append((k, a, b))
+    torch.cuda.synchronize()
+    for k, a, b in events:
+        times[k].append(a.elapsed_time(b))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    diff = float((got["hip"] - got["torch"]).abs().max() / got["torch"].abs().max())
+    return {"shape": list(shape), "launches": launches, "hip_kernels_per_call": 12,
+            "median_ms": {"stem_ms_ssim + stem_ms_ssim_bwd": med["hip"], "torch autograd, fp32 body of evaluation.ms_ssim": med["torch"]},
+            "min_ms": {k: min(v) for k, v in times.items()}, "p90_ms": {k: sorted(v)[int(0.9 * (launches - 1))] for k, v in times.items()},
+            "torch_over_hip": med["torch"] / med["hip"], "max_gradient_difference_over_max_gradient": diff}
+
+
 def time_eval(passes):
     from spatiotemporalentropymodel_amd import evaluation
     from spatiotemporalentropymodel_amd.models import SpatioTemporalPriorModel_Res
@@ -108,6 +180,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=60)
     ap.add_argument("--passes", type=int, default=3)
+    ap.add_argument("--only", default="kernel,grad,eval_gop", help="comma-separated parts to run")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "metrics_bench.json"))
     args = ap.parse_args()
     if args.launches < 50:
@@ -115,9 +188,16 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("metrics_bench: no GPU -- this tool measures on an MI355X and has no other mode")
     torch.cuda.set_device(0)
-    res = {"device": torch.cuda.get_device_name(0),
-           "kernel": [time_kernel((1, 3, 1080, 1920), args.launches), time_kernel((8, 3, 1080, 1920), args.launches)],
-           "eval_gop": time_eval(args.passes)}
+    only = set(args.only.split(","))
+    if not only or only - {"kernel", "grad", "eval_gop"}:
+        sys.exit("metrics_bench: --only takes kernel, grad, eval_gop")
+    res = {"device": torch.cuda.get_device_name(0)}
+    if "kernel" in only:
+        res["kernel"] = [time_kernel((1, 3, 1080, 1920), args.launches), time_kernel((8, 3, 1080, 1920), args.launches)]
+    if "grad" in only:
+        res["grad"] = [time_grad((16, 3, 256, 256), args.launches), time_grad((1, 3, 1080, 1920), args.launches)]
+    if "eval_gop" in only:
+        res["eval_gop"] = time_eval(args.passes)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
