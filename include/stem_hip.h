@@ -629,6 +629,40 @@ int stem_ms_ssim_bwd(const float *x, const float *y, int B, int C, int H, int W,
                      const float *grad_ms /* [B] */, void *workspace, size_t workspace_bytes,
                      float *dx /* [B,C,H,W], overwritten */, void *stream);
 
+/* ---- raw YUV 4:2:0 sequences --------------------------------------------- */
+/* Planar 4:2:0 frames as video test sets ship them (8-bit samples, or 10 bits in little-endian 16-bit words; BT.709, full range)
+ * to and from the fp32 NCHW RGB the models take.  Planes: y [B,H,W], u and v [B,H/2,W/2], dense; sample_bytes 1 or 2, bit_depth 8 or
+ * 10 (10 needs two bytes), peak = 2^bit_depth - 1; H and W even and >= 2.  No host synchronisation.
+ *
+ * compressai/transforms/functional.py:47-65 after :100-135 -- ycbcr2rgb(yuv_420_to_444((y, u, v) / peak, mode)) in one pass:
+ * chroma x2 upsampling with the borders of F.interpolate(scale_factor=2, align_corners=False) (bilinear: 0.25 / 0.75 taps, indices
+ * clamped at the plane's edge; or nearest), then r and b from y, g from them; clamp01 != 0 clamps the result to [0,1]. */
+#define STEM_YUV_BILINEAR 0
+#define STEM_YUV_NEAREST 1
+#define STEM_YUV_AVG_POOL 2
+int stem_yuv420_to_rgb(const void *y, const void *u, const void *v, int B, int H, int W, int sample_bytes, int bit_depth,
+                       int upsample, int clamp01, float *rgb /* [B,3,H,W] */, void *stream);
+/* compressai/transforms/functional.py:68-97 after :26-44 -- yuv_444_to_420(rgb2ycbcr(rgb)) in one pass, evaluated in fp64, written as
+ *   yf / uf / vf   (all three or none) fp32 planes: the reference's result, rounded once;
+ *   yi / ui / vi   (all three or none) integer planes of sample_bytes at bit_depth: rint(clamp(value, 0, 1) * peak), half to even.
+ * At least one of the two sets.  With source planes ys / us / vs (all three or none; geometry and sample type of the integer
+ * planes, which must be asked for) the same pass leaves in sse[b][0..2] the sums over image b of the squared differences of the
+ * Y, U and V samples written and the source's, as exact 64-bit integers: the decoded frame's YUV distortion.  That needs
+ * `workspace`: stem_rgb_to_yuv420_workspace() bytes of device memory, 8-byte aligned, nothing to initialise (one slot per
+ * workgroup, summed by a second launch: no atomics).  sample_bytes / bit_depth are not looked at without integer planes. */
+int stem_rgb_to_yuv420_workspace(int B, int H, int W, size_t *bytes);
+int stem_rgb_to_yuv420(const float *rgb /* [B,3,H,W] */, int B, int H, int W, float *yf, float *uf, float *vf,
+                       void *yi, void *ui, void *vi, int sample_bytes, int bit_depth,
+                       const void *ys, const void *us, const void *vs, void *workspace, size_t workspace_bytes,
+                       unsigned long long *sse /* [B][3] */, void *stream);
+/* The single steps of the same file on fp32 NCHW tensors, fp32 arithmetic in the reference's order of operations:
+ * :26-65 -- rgb2ycbcr (to_rgb == 0) or ycbcr2rgb (to_rgb != 0) of [N,3,H,W], element by element;
+ * :68-135 -- one plane-wise half of yuv_420_to_444 / yuv_444_to_420 on [planes,H,W] (the INPUT size): mode STEM_YUV_BILINEAR or
+ * STEM_YUV_NEAREST writes [planes,2H,2W] (F.interpolate, scale_factor=2, align_corners=False), STEM_YUV_AVG_POOL writes
+ * [planes,H/2,W/2] (F.avg_pool2d, kernel 2; H and W even). */
+int stem_ycbcr_convert(const float *in, float *out, int N, int H, int W, int to_rgb, void *stream);
+int stem_plane_resample2(const float *in, float *out, int planes, int H, int W, int mode, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,11 @@ _HIP_SIG = {
     "stem_ms_ssim": [vp, vp, ci, ci, ci, ci, cf, vp, sz, vp, vp, vp, vp],
     "stem_ms_ssim_bwd_workspace": [ci, ci, ci, ci, vp],
     "stem_ms_ssim_bwd": [vp, vp, ci, ci, ci, ci, cf, vp, sz, vp, vp, sz, vp, vp],
+    "stem_yuv420_to_rgb": [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp],
+    "stem_ycbcr_convert": [vp, vp, ci, ci, ci, ci, vp],
+    "stem_plane_resample2": [vp, vp, ci, ci, ci, ci, vp],
+    "stem_rgb_to_yuv420_workspace": [ci, ci, ci, vp],
+    "stem_rgb_to_yuv420": [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, sz, vp, vp],
     "stem_sumsq": [vp, sz, vp, vp],
     "stem_sumsq_set": [vp, sz, vp, vp],
     "stem_clip_scale": [vp, sz, vp, cf, vp],

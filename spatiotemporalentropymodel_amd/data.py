@@ -5,6 +5,8 @@ reference, so a seeded run picks the same crops / flips / quality maps), the dev
     VimeoSepTuplet        stem/dataset_vidseq.py:24-96       shared random crop (torch RNG) + temporal flip (`random`)
     VimeoSepTuplet_QMap   stem_roi/stem_roi_dataset.py:13-163 crop + flip + quality map: uniform / gradation / Gaussians
     get_loader / get_loader_roi                               iterate device batches: (list of 7 x [B,3,c,c]) [, qmap [B,1,c,c]]
+    YUVSequence / write_yuv420                                raw planar YUV 4:2:0 test sequences (UVG, HEVC classes, MCL-JCV) in
+                                                              and out: integer planes over the host link, conversion on the device
 
 `__getitem__` returns the decoded uint8 frames plus the drawn parameters (no per-pixel host work); `device_batch`
 uploads one pinned uint8 block and launches `stem_crop_u8_to_f32` (+ `stem_qmap_render`).  A 16-septuplet batch is
@@ -231,3 +233,119 @@ def get_loader_roi(mode, data_root, batch_size, shuffle, num_workers, cropsize=2
     """stem_roi/stem_roi_dataset.py:156-163"""
     ds = VimeoSepTuplet_QMap(data_root, is_training=(mode == "train"), cropsize=cropsize, level=level)
     return DeviceLoader(ds, batch_size, shuffle, num_workers, device)
+
+
+# ----------------------------------------------------------------------------- raw planar YUV 4:2:0 sequences
+def _yuv_geometry(width, height, bit_depth):
+    if bit_depth not in (8, 10):
+        raise ValueError(f"bit_depth is 8 or 10, got {bit_depth!r}")
+    if width < 2 or height < 2 or width % 2 or height % 2:
+        raise ValueError(f"4:2:0 frames have even sides >= 2, got {width} x {height}")
+    sample_bytes = 1 if bit_depth == 8 else 2
+    return sample_bytes, (width * height * 3 // 2) * sample_bytes
+
+
+class YUVSequence:
+    """A raw planar YUV 4:2:0 file (frame after frame: the Y plane, then U, then V; 8-bit samples, or 10 bits in little-endian
+    16-bit words; BT.709, full range) as an iterable of RGB frames for evaluation.eval_gop.
+
+    The frame count comes from the file length (ValueError if it is not a whole number of frames); `frames` keeps the first so
+    many.  Iterating reads ONE frame at a time into a pinned staging buffer, uploads the integer planes (an eighth of the bytes of
+    the fp32 RGB frame) and converts on the device (functional.yuv420_to_rgb, bilinear chroma): yields [3,h,w] fp32 tensors on
+    `device`, clamped to [0,1] with clamp=True.  Each yielded tensor carries its source as plain ATTRIBUTES (not a Tensor
+    subclass: the models see an ordinary tensor): `yuv_planes` = (y [1,h,w], u [1,h/2,w/2], v) integer tensors on the same
+    device, and `bit_depth`.  evaluation's yuv=True measures the decoded frame against those planes.  Attributes do not survive
+    tensor operations; take them from the yielded tensor itself.
+
+    With device="cpu" the same frames are computed by transforms.yuv420_planes_to_rgb (torch on the host: for a data-loader
+    worker).  `planes(i)` returns frame i's planes as host tensors and never touches a device."""
+
+    def __init__(self, path, width, height, bit_depth=8, frames=None, device="cuda", clamp=True):
+        self.path, self.width, self.height, self.bit_depth = path, int(width), int(height), int(bit_depth)
+        self.sample_bytes, self.frame_bytes = _yuv_geometry(self.width, self.height, self.bit_depth)
+        size = os.path.getsize(path)
+        if size == 0 or size % self.frame_bytes:
+            raise ValueError(f"{path}: {size} bytes is not a whole number of {self.width} x {self.height} {self.bit_depth}-bit 4:2:0 frames "
+                             f"({self.frame_bytes} bytes each)")
+        self.nframes = size // self.frame_bytes
+        if frames is not None:
+            if not 0 < int(frames) <= self.nframes:
+                raise ValueError(f"{path} holds {self.nframes} frames, {frames} asked for")
+            self.nframes = int(frames)
+        self.device, self.clamp = torch.device(device), bool(clamp)
+
+    def __len__(self):
+        return self.nframes
+
+    def _split(self, flat):
+        """flat: one frame's samples (1-D tensor of the sample type) -> (y [1,h,w], u [1,h/2,w/2], v)"""
+        h, w = self.height, self.width
+        n, c = h * w, (h // 2) * (w // 2)
+        return flat[:n].view(1, h, w), flat[n:n + c].view(1, h // 2, w // 2), flat[n + c:].view(1, h // 2, w // 2)
+
+    def _dtype(self):
+        return torch.uint8 if self.sample_bytes == 1 else torch.uint16
+
+    def planes(self, index):
+        """(y, u, v) of frame `index` as host tensors (uint8 / uint16)"""
+        if not 0 <= index < self.nframes:
+            raise IndexError(index)
+        raw = np.fromfile(self.path, dtype=np.uint8 if self.sample_bytes == 1 else "<u2", count=self.frame_bytes // self.sample_bytes,
+                          offset=index * self.frame_bytes)
+        return self._split(torch.from_numpy(raw.astype(raw.dtype.newbyteorder("="), copy=False)))
+
+    def __iter__(self):
+        if self.device.type != "cuda":
+            from . import transforms
+            for i in range(self.nframes):
+                planes = self.planes(i)
+                x = transforms.yuv420_planes_to_rgb(planes, self.bit_depth, "bilinear", self.clamp)[0]
+                x.yuv_planes, x.bit_depth = planes, self.bit_depth
+                yield x
+            return
+        stage = torch.empty(self.frame_bytes, dtype=torch.uint8).pin_memory()
+        host = stage.numpy()
+        done = torch.cuda.Event()
+        with open(self.path, "rb") as f:
+            for _ in range(self.nframes):
+                if f.readinto(host) != self.frame_bytes:
+                    raise ValueError(f"{self.path}: truncated while reading")
+                dev = torch.empty(self.frame_bytes, dtype=torch.uint8, device=self.device)
+                with torch.cuda.device(self.device):
+                    dev.copy_(stage, non_blocking=True)
+                    done.record()
+                    planes = self._split(dev.view(self._dtype()))
+                    x = F.yuv420_to_rgb(*planes, bit_depth=self.bit_depth, upsample="bilinear", clamp01=self.clamp)[0]
+                x.yuv_planes, x.bit_depth = planes, self.bit_depth
+                done.synchronize()                     # the staging buffer is free again
+                yield x
+
+
+def _write_planes(path_or_file, planes, append=True):
+    """planes: (y [B,h,w], u, v) integer tensors -> the file, image after image, each as Y, U, V (little-endian samples)"""
+    y, u, v = (np.ascontiguousarray(p.cpu().numpy()) for p in planes)
+    if y.dtype.itemsize == 2:
+        y, u, v = (a.astype("<u2", copy=False) for a in (y, u, v))
+    f = open(path_or_file, "ab" if append else "wb") if isinstance(path_or_file, (str, os.PathLike)) else path_or_file
+    try:
+        for b in range(y.shape[0]):
+            for a in (y, u, v):
+                f.write(a[b].tobytes())
+    finally:
+        if f is not path_or_file:
+            f.close()
+
+
+def write_yuv420(path_or_file, x_hat, bit_depth=8, append=True):
+    """Write decoded RGB frames x_hat ([3,h,w] or [B,3,h,w], fp32 in [0,1]; h, w even) to a raw planar 4:2:0 file in the format
+    YUVSequence reads, quantised by functional.rgb_to_yuv420 on the device (host tensors: transforms.rgb_to_yuv420_planes).
+    path_or_file: a path (append=True adds to the file's end, False starts it anew) or a binary file object.  Returns the planes
+    written, (y [B,h,w], u, v) on x_hat's device."""
+    x = x_hat.unsqueeze(0) if x_hat.dim() == 3 else x_hat
+    if x.is_cuda:
+        planes = F.rgb_to_yuv420(x.float(), bit_depth=bit_depth)
+    else:
+        from . import transforms
+        planes = transforms.rgb_to_yuv420_planes(x.float(), bit_depth=bit_depth)
+    _write_planes(path_or_file, planes, append)
+    return planes

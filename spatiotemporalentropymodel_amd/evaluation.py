@@ -14,6 +14,10 @@ against an independent scipy formulation and its defining properties.  It is a r
 regions, computed on the host by default and by the HIP kernel on request: `with_msssim="device"` takes "ms-ssim" and "psnr" of a frame
 from one stem_ms_ssim call (functional.ms_ssim, `ms_ssim_device` below; tests/test_hip_msssim.py holds it against float64); frames smaller than 161 pixels on a side have no five-scale MS-SSIM and report None.  One deliberate difference: the script's I frame runs
 on the CPU and moves `y_conditioned` to the GPU for the P frames (:196-207); here everything stays on the models' device.
+`yuv=True` (not in the script, which reads PNGs): every frame dictionary gains "psnr_y", "psnr_u", "psnr_v" and "psnr_yuv" =
+(6 Y + U + V) / 8, the numbers video-coding papers tabulate, measured in the sample domain of the source: the decoded frame is
+quantised to planar 4:2:0 at the source's bit depth and compared with the source's integer planes (`_yuv_metrics`); `write_to=`
+appends each decoded frame to a raw .yuv file.  With yuv=False and no write_to nothing changes.
 The script's last line reads out_dec["entropy_params"], a key the reference model's decompress() does not return
 (spatiotemporalpriors.py:1012 -> KeyError at :152 as shipped); the key is returned holding None.
 
@@ -106,6 +110,41 @@ def _metrics(x, x_hat, with_msssim):
     return psnr(x, x_hat), (ms_ssim(x, x_hat, data_range=1.0) if with_msssim else None)
 
 
+def _source_planes(frame):
+    """the integer 4:2:0 planes a frame [3,h,w] came from and their bit depth: what data.YUVSequence attached to it, or, for a plain
+    RGB tensor, the frame itself quantised at 8 bits"""
+    planes = getattr(frame, "yuv_planes", None)
+    if planes is not None:
+        return planes, int(getattr(frame, "bit_depth", 8))
+    from . import functional
+    return functional.rgb_to_yuv420(frame.unsqueeze(0).float(), bit_depth=8), 8
+
+
+def _psnr_int(sse, count, peak):
+    """PSNR from an integer sum of squared sample errors; exactly zero error is +inf"""
+    return float("inf") if sse == 0 else 10 * math.log10(peak * peak * count / sse)
+
+
+def _yuv_metrics(frame, x_hat, yuv, write_to):
+    """the yuv=True entries of one frame's dictionary (and the write_to side effect).  One stem_rgb_to_yuv420 call quantises the
+    cropped x_hat [1,3,h,w] to the source's sample format and sums the squared integer differences against the source planes."""
+    if not yuv and write_to is None:
+        return {}
+    from . import data, functional
+    if not yuv:                                        # only the file is wanted: the source's depth, not its planes
+        data.write_yuv420(write_to, x_hat, bit_depth=int(getattr(frame, "bit_depth", 8)), append=True)
+        return {}
+    planes, bit_depth = _source_planes(frame)
+    y, u, v, sse = functional.rgb_to_yuv420(x_hat.float(), bit_depth=bit_depth, source=planes)
+    if write_to is not None:
+        data._write_planes(write_to, (y, u, v), append=True)
+    sy, su, sv = sse[0].tolist()
+    peak = (1 << bit_depth) - 1
+    out = {"psnr_y": _psnr_int(sy, y.numel(), peak), "psnr_u": _psnr_int(su, u.numel(), peak), "psnr_v": _psnr_int(sv, v.numel(), peak)}
+    out["psnr_yuv"] = (6 * out["psnr_y"] + out["psnr_u"] + out["psnr_v"]) / 8
+    return out
+
+
 def _sync(t):
     if t.is_cuda:
         torch.cuda.synchronize(t.device)
@@ -118,10 +157,10 @@ def _bpp_terms(out_enc, out_forward, num_pixels):
 
 
 @torch.no_grad()
-def inference_iframe(model, x, with_msssim=True):
+def inference_iframe(model, x, with_msssim=True, yuv=False, write_to=None):
     """x: one image [3,h,w] in [0,1].  Pad to multiples of 64 (centred), compress + forward (the rate estimate), decompress, crop.
-    `y_conditioned` is the DECODED latent of the padded image: what the next P frame is conditioned on."""
-    x = x.unsqueeze(0)
+    `y_conditioned` is the DECODED latent of the padded image: what the next P frame is conditioned on.  yuv, write_to: `_yuv_metrics`."""
+    frame, x = x, x.unsqueeze(0)
     h, w = x.size(2), x.size(3)
     x_padded = bitstream.pad(x, 64)
     _sync(x)
@@ -142,14 +181,15 @@ def inference_iframe(model, x, with_msssim=True):
             "estimate_bpp": sum(est.values()),
             "estimate_y_bpp": est.get("y"), "estimate_z_bpp": est.get("z"), "y_bpp": len(out_enc["strings"][0][0]) * 8.0 / num_pixels,
             "z_bpp": len(out_enc["strings"][1][0]) * 8.0 / num_pixels, "encoding_time": enc_time, "decoding_time": dec_time,
-            "out_forward": out_forward, "strings": out_enc["strings"], "shape": tuple(out_enc["shape"]), "x_hat": x_hat}
+            "out_forward": out_forward, "strings": out_enc["strings"], "shape": tuple(out_enc["shape"]), "x_hat": x_hat,
+            **_yuv_metrics(frame, x_hat, yuv, write_to)}
 
 
 @torch.no_grad()
-def inference_pframe(imodel, stem, x, y_conditioned, with_msssim=True):
+def inference_pframe(imodel, stem, x, y_conditioned, with_msssim=True, yuv=False, write_to=None):
     """x: one frame [3,h,w]; y_conditioned: the previous frame's decoded latents.  encode = getY + forward + compress, decode =
-    decompress + getX, timed as the script times them."""
-    x = x.unsqueeze(0)
+    decompress + getX, timed as the script times them.  yuv, write_to: `_yuv_metrics`."""
+    frame, x = x, x.unsqueeze(0)
     h, w = x.size(2), x.size(3)
     x_padded = bitstream.pad(x, 64)
     _sync(x)
@@ -174,29 +214,37 @@ def inference_pframe(imodel, stem, x, y_conditioned, with_msssim=True):
             "estimate_y_bpp": est.get("y"), "estimate_z_bpp": est.get("z"), "y_bpp": len(out_enc["strings"][0][0]) * 8.0 / num_pixels,
             "z_bpp": len(out_enc["strings"][1][0]) * 8.0 / num_pixels, "encoding_time": enc_time, "decoding_time": dec_time,
             "entropy_params": out_dec.get("entropy_params") if isinstance(out_dec, dict) else None,
-            "strings": out_enc["strings"], "shape": tuple(out_enc["shape"]), "x_hat": x_hat}
+            "strings": out_enc["strings"], "shape": tuple(out_enc["shape"]), "x_hat": x_hat, **_yuv_metrics(frame, x_hat, yuv, write_to)}
 
 
 @torch.no_grad()
-def eval_gop(imodel, stem, frames, gop=12, all_intra=False, with_msssim=True):
+def eval_gop(imodel, stem, frames, gop=12, all_intra=False, with_msssim=True, yuv=False, write_to=None):
     """frames: iterable of [3,h,w] images of ONE sequence, in display order (the script's f001.png, f002.png, ...).  Frame k
     (1-based) with k % gop == 1 is an I frame, every other one a P frame conditioned on the previous frame's decoded latents
     (stem/evalSTEM.py:186-209; gop = 12 for UVG, 10 for the HEVC classes).  Returns the per-frame dictionaries of the two
     inference functions (plus "type") and the sequence averages the script logs (:217-224).  with_msssim=False leaves the host-side
     MS-SSIM out (a reporting metric next to the codec path, ~0.3 s per 1080p frame on the host); with_msssim="device" takes "ms-ssim"
-    and "psnr" of every frame from the HIP kernel instead (`_metrics`)."""
+    and "psnr" of every frame from the HIP kernel instead (`_metrics`).  yuv=True adds "psnr_y", "psnr_u", "psnr_v", "psnr_yuv" to every
+    frame (against the planes a data.YUVSequence frame carries, else against the frame quantised at 8 bits) and their averages
+    "psnr_y_ave" ... "psnr_yuv_ave" to the result; write_to (a path or a binary file object) gets every decoded frame appended as raw
+    planar 4:2:0 at the source's bit depth."""
+    extra = {} if not yuv and write_to is None else {"yuv": yuv, "write_to": write_to}      # nothing new is passed through by default
     per_frame, y_cond = [], None
     for index, x in enumerate(frames, start=1):
         if all_intra or index % gop == 1 or y_cond is None:
-            out = inference_iframe(imodel, x, with_msssim)
+            out = inference_iframe(imodel, x, with_msssim, **extra)
             out["type"] = "I"
         else:
-            out = inference_pframe(imodel, stem, x, y_cond, with_msssim)
+            out = inference_pframe(imodel, stem, x, y_cond, with_msssim, **extra)
             out["type"] = "P"
         y_cond = out["y_conditioned"]
         per_frame.append(out)
     n = max(1, len(per_frame))
     ms = [f["ms-ssim"] for f in per_frame if f["ms-ssim"] is not None]
-    return {"frames": per_frame, "psnr_ave": sum(f["psnr"] for f in per_frame) / n, "bpp_ave": sum(f["bpp"] for f in per_frame) / n,
-            "msssim_ave": (sum(ms) / len(ms)) if ms else None,
-            "estimate_bpp_ave": sum(f["estimate_bpp"] for f in per_frame) / n}
+    res = {"frames": per_frame, "psnr_ave": sum(f["psnr"] for f in per_frame) / n, "bpp_ave": sum(f["bpp"] for f in per_frame) / n,
+           "msssim_ave": (sum(ms) / len(ms)) if ms else None,
+           "estimate_bpp_ave": sum(f["estimate_bpp"] for f in per_frame) / n}
+    if yuv:
+        for k in ("psnr_y", "psnr_u", "psnr_v", "psnr_yuv"):
+            res[k + "_ave"] = sum(f[k] for f in per_frame) / n
+    return res

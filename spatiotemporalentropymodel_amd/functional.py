@@ -1155,6 +1155,126 @@ def ms_ssim_backward(x, y, grad_ms, data_range=1.0, fwd_workspace=None):
     return dx
 
 
+# ----------------------------------------------------------------------------- raw YUV 4:2:0 frames (csrc/yuv.hip)
+YUV_UPSAMPLE = {"bilinear": 0, "nearest": 1}
+
+
+def _yuv_dtype(bit_depth):
+    if bit_depth not in (8, 10):
+        raise ValueError(f"bit_depth is 8 or 10, got {bit_depth!r}")
+    return torch.uint8 if bit_depth == 8 else torch.uint16
+
+
+def _yuv_planes_check(y, u, v, bit_depth, who):
+    """three dense integer device planes of one 4:2:0 geometry -> (y, u, v, B, H, W, sample_bytes)"""
+    for t in (y, u, v):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{who}: STEM HIP kernels need CUDA/ROCm tensors (no CPU fallback exists)")
+    if bit_depth not in (8, 10):
+        raise ValueError(f"{who}: bit_depth is 8 or 10, got {bit_depth!r}")
+    if y.dtype not in (torch.uint8, torch.uint16) or u.dtype != y.dtype or v.dtype != y.dtype:
+        raise TypeError(f"{who}: planes are uint8 or uint16 and of one type, got {y.dtype}, {u.dtype}, {v.dtype}")
+    if y.dtype == torch.uint8 and bit_depth != 8:
+        raise ValueError(f"{who}: {bit_depth}-bit samples need uint16 planes")
+    if y.dim() != 3:
+        raise ValueError(f"{who}: the Y plane is [B,H,W], got {tuple(y.shape)}")
+    B, H, W = y.shape
+    if H % 2 or W % 2 or H < 2 or W < 2:
+        raise ValueError(f"{who}: 4:2:0 frames have even sides >= 2, got {H} x {W}")
+    if tuple(u.shape) != (B, H // 2, W // 2) or tuple(v.shape) != (B, H // 2, W // 2):
+        raise ValueError(f"{who}: chroma planes of a [{B},{H},{W}] Y plane are [{B},{H // 2},{W // 2}], got {tuple(u.shape)} and {tuple(v.shape)}")
+    if B < 1:
+        raise ValueError(f"{who}: empty batch")
+    return y.contiguous(), u.contiguous(), v.contiguous(), B, H, W, y.element_size()
+
+
+def yuv420_to_rgb(y, u, v, bit_depth=8, upsample="bilinear", clamp01=True):
+    """Planar 4:2:0 integer planes (y [B,H,W], u and v [B,H/2,W/2]; uint8, or uint16 holding `bit_depth` bits) -> fp32 RGB
+    [B,3,H,W]: the reference's ycbcr2rgb(yuv_420_to_444(planes / (2^bit_depth - 1), mode=upsample)) as one kernel
+    (stem_yuv420_to_rgb; BT.709, full range).  clamp01 clamps the result to [0,1].  No host synchronisation."""
+    y, u, v, B, H, W, sb = _yuv_planes_check(y, u, v, bit_depth, "yuv420_to_rgb")
+    if upsample not in YUV_UPSAMPLE:
+        raise ValueError(f'Invalid upsampling mode "{upsample}".')
+    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=y.device)
+    _chk(_lib.hip().stem_yuv420_to_rgb(y.data_ptr(), u.data_ptr(), v.data_ptr(), B, H, W, sb, bit_depth, YUV_UPSAMPLE[upsample], int(bool(clamp01)),
+                                       out.data_ptr(), _stream()))
+    return out
+
+
+def rgb_to_yuv420(x, bit_depth=None, source=None):
+    """fp32 RGB [B,3,H,W] -> planar 4:2:0 (y [B,H,W], u, v [B,H/2,W/2]) by one kernel (stem_rgb_to_yuv420; BT.709, full range):
+        bit_depth=None     fp32 planes, the reference's yuv_444_to_420(rgb2ycbcr(x))
+        bit_depth=8 | 10   integer planes (uint8 | uint16): rint(clamp(value, 0, 1) * (2^bit_depth - 1)), half to even
+    With `source` = (y, u, v) integer planes of the same geometry and type, also returns sse [B,3] int64: per image, the sums of
+    squared differences between the planes written and the source's -- (y, u, v, sse).  No host synchronisation."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("rgb_to_yuv420: STEM HIP kernels need CUDA/ROCm tensors (no CPU fallback exists)")
+    if x.dtype != torch.float32:
+        raise TypeError(f"rgb_to_yuv420: the RGB batch is fp32, got {x.dtype}")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"rgb_to_yuv420 takes an RGB batch [B,3,H,W], got {tuple(x.shape)}")
+    B, _, H, W = x.shape
+    if H % 2 or W % 2 or H < 2 or W < 2:
+        raise ValueError(f"rgb_to_yuv420: 4:2:0 frames have even sides >= 2, got {H} x {W}")
+    if B < 1:
+        raise ValueError("rgb_to_yuv420: empty batch")
+    x = x.detach().contiguous()
+    dt = torch.float32 if bit_depth is None else _yuv_dtype(bit_depth)
+    yo = torch.empty((B, H, W), dtype=dt, device=x.device)
+    uo = torch.empty((B, H // 2, W // 2), dtype=dt, device=x.device)
+    vo = torch.empty((B, H // 2, W // 2), dtype=dt, device=x.device)
+    lib = _lib.hip()
+    if bit_depth is None:
+        if source is not None:
+            raise ValueError("rgb_to_yuv420: squared errors against source planes are taken on integer planes (give bit_depth)")
+        _chk(lib.stem_rgb_to_yuv420(x.data_ptr(), B, H, W, yo.data_ptr(), uo.data_ptr(), vo.data_ptr(), None, None, None, 0, 0, None, None, None,
+                                    None, 0, None, _stream()))
+        return yo, uo, vo
+    if source is None:
+        _chk(lib.stem_rgb_to_yuv420(x.data_ptr(), B, H, W, None, None, None, yo.data_ptr(), uo.data_ptr(), vo.data_ptr(), yo.element_size(),
+                                    bit_depth, None, None, None, None, 0, None, _stream()))
+        return yo, uo, vo
+    if len(source) != 3:
+        raise ValueError("rgb_to_yuv420: source is a tuple of three planes (y, u, v)")
+    ys, us, vs, Bs, Hs, Ws, _ = _yuv_planes_check(*source, bit_depth, "rgb_to_yuv420 (source planes)")
+    if (Bs, Hs, Ws) != (B, H, W) or ys.dtype != dt or ys.device != x.device:
+        raise ValueError(f"rgb_to_yuv420: source planes [{Bs},{Hs},{Ws}] {ys.dtype} do not match the [{B},{H},{W}] {dt} planes to write")
+    n = C.c_size_t(0)
+    _chk(lib.stem_rgb_to_yuv420_workspace(B, H, W, C.byref(n)))
+    ws = torch.empty(max(n.value // 8, 1), dtype=torch.int64, device=x.device)      # 24 bytes per workgroup: this call's own
+    sse = torch.empty((B, 3), dtype=torch.int64, device=x.device)
+    _chk(lib.stem_rgb_to_yuv420(x.data_ptr(), B, H, W, None, None, None, yo.data_ptr(), uo.data_ptr(), vo.data_ptr(), yo.element_size(), bit_depth,
+                                ys.data_ptr(), us.data_ptr(), vs.data_ptr(), ws.data_ptr(), ws.numel() * 8, sse.data_ptr(), _stream()))
+    return yo, uo, vo, sse
+
+
+def ycbcr_convert(x, to_rgb):
+    """transforms.ycbcr2rgb (to_rgb) / rgb2ycbcr of an fp32 device tensor [3,H,W] or [N,3,H,W] (stem_ycbcr_convert)"""
+    _require_cuda(x)
+    if x.dim() not in (3, 4) or x.shape[-3] != 3 or x.numel() == 0:
+        raise ValueError(f"ycbcr_convert takes [3,H,W] or [N,3,H,W], got {tuple(x.shape)}")
+    x = x.detach().contiguous()
+    out = torch.empty_like(x)
+    _chk(_lib.hip().stem_ycbcr_convert(x.data_ptr(), out.data_ptr(), x.shape[0] if x.dim() == 4 else 1, x.shape[-2], x.shape[-1], int(bool(to_rgb)),
+                                       _stream()))
+    return out
+
+
+def plane_resample2(x, mode):
+    """fp32 device planes [P,H,W] -> [P,2H,2W] (mode 0 bilinear with align_corners=False borders, 1 nearest) or [P,H/2,W/2] (mode 2,
+    the 2 x 2 mean; H, W even) by stem_plane_resample2"""
+    _require_cuda(x)
+    if x.dim() != 3 or x.numel() == 0:
+        raise ValueError(f"plane_resample2 takes planes [P,H,W], got {tuple(x.shape)}")
+    P, H, W = x.shape
+    if mode == 2 and (H % 2 or W % 2):
+        raise ValueError(f"the 2 x 2 mean needs even sides, got {H} x {W}")
+    x = x.detach().contiguous()
+    out = torch.empty((P, H // 2, W // 2) if mode == 2 else (P, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
+    _chk(_lib.hip().stem_plane_resample2(x.data_ptr(), out.data_ptr(), P, H, W, int(mode), _stream()))
+    return out
+
+
 def weighted_sqerr_bwd(xhat, x, lam, g, coef):
     B, Cc, H, W = xhat.shape
     g = g.to(torch.float64).contiguous()
