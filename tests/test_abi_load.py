@@ -1,15 +1,13 @@
 """CPU: the C-ABI libraries load and export every symbol include/*.h declares (no compute calls)."""
 import ctypes
 import os
-import re
 
 from conftest import REPO
 
 
 def _declared(header):
-    src = open(os.path.join(REPO, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(stem_[a-z0-9_]+)\s*\(", src)))
+    from spatiotemporalentropymodel_amd import _abi
+    return sorted(_abi.prototypes(os.path.join(REPO, "include", header)))
 
 
 def test_hip_library_exports_header_symbols():
