@@ -305,7 +305,8 @@ int stem_uniform_noise_epoch(float *out, size_t n, uint64_t seed, uint64_t offse
  * stem_eb_forward_train / stem_gc_forward_train: training-mode forward of the entropy models (entropy_models.py:424-452,
  *   588-596) that also emits dlik = coef / lik (EMLoss is a sum of logs, utils.py:18-27: coef = -1 / (ln 2 * N*H*W)) and
  *   per-workgroup partial sums of log2(lik) (double, `partials` holds stem_rate_partials(npix*C) entries).
- * stem_em_loss_finalize: out3 = {y_bpp, z_bpp, loss} = scale * fixed-order sums of the partials (scale = -1/(N*H*W)).
+ * stem_em_loss_finalize: out3 = {y_bpp, z_bpp, loss} = scale * fixed-order sums of the partials (scale = -1/(N*H*W)); loss is
+ *   y_bpp + z_bpp of the values as written (one rounded add); a list of 0 partials may be a null pointer and sums to 0.
  * stem_eb_aux_loss_grad: EntropyBottleneck.loss (entropy_models.py:383-386) and its gradient w.r.t. the quantiles in
  *   one workgroup: loss[0] is written (not accumulated), dquantiles written or added (accumulate != 0).             */
 int stem_prior_prologue(const float *y_cur, int ldc, const float *y_cond, int ldd, float *he_in, int ldh, float *target,

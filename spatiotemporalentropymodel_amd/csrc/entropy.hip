@@ -874,9 +874,13 @@ __global__ __launch_bounds__(256) void em_loss_finalize_kernel(const double *py,
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        out[0] = red[0][0] * scale;
-        out[1] = red[1][0] * scale;
-        out[2] = out[0] + out[1];
+        // the loss is the sum of the two terms AS REPORTED (rounded): contracted into a fused multiply-add, out[2] would differ from
+        // out[0] + out[1] in the last bit
+#pragma clang fp contract(off)
+        const double y = red[0][0] * scale, z = red[1][0] * scale;
+        out[0] = y;
+        out[1] = z;
+        out[2] = y + z;
     }
 }
 
@@ -1063,7 +1067,8 @@ STEM_EXPORT int stem_gc_forward_backward_train(const float *y, const float *scal
 STEM_EXPORT int stem_em_loss_finalize(const double *partials_y, int ny, const double *partials_z, int nz, double scale, double *out3,
                                       void *stream)
 {
-    STEM_CHECK_ARG(partials_y && partials_z && out3 && ny >= 0 && nz >= 0, "stem_em_loss_finalize: bad arguments");
+    // an empty list may come with a null pointer (a tensor without elements has none): its sum is 0
+    STEM_CHECK_ARG(out3 && ny >= 0 && nz >= 0 && (partials_y || ny == 0) && (partials_z || nz == 0), "stem_em_loss_finalize: bad arguments");
     hipLaunchKernelGGL(em_loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials_y, ny, partials_z, nz, scale, out3);
     STEM_LAUNCH_CHECK("em_loss_finalize");
     return 0;
