@@ -1,4 +1,4 @@
-"""ctypes loader for the three C-ABI libraries (include/stem_hip.h, include/stem_rans.h, include/stem_dp.h).
+"""ctypes loader for the three C-ABI libraries (include/stem_hip.h + include/stem_ar_batch.h, include/stem_rans.h, include/stem_dp.h).
 
 The headers are the single statement of the ABI: every prototype and descriptor structure below is read from them (_abi.py).
 
@@ -43,6 +43,8 @@ def _tables(header):
 
 # tape.py classifies the argument slots of a recorded call by _HIP_SIG and leaves the entries of _RESTYPE out of a schedule
 _HIP_PROTO, _HIP_SIG, _RESTYPE = _tables("stem_hip.h")
+# libstem_hip.so's batched coding entry points (not launch-tape entries: tape.py does not see them)
+_HIP_BATCH_PROTO, _HIP_BATCH_SIG, _ = _tables("stem_ar_batch.h")
 _RANS_PROTO, _RANS_SIG, _RANS_RESTYPE = _tables("stem_rans.h")
 _DP_PROTO, _DP_SIG, _ = _tables("stem_dp.h")
 _STRUCTS = _abi.structs(_header("stem_hip.h"))
@@ -88,7 +90,7 @@ def hip():
             raise StemLibraryError(
                 f"{HIP_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the STEM kernels.")
-        _hip = _bind(C.CDLL(HIP_SO), _HIP_PROTO)
+        _hip = _bind(_bind(C.CDLL(HIP_SO), _HIP_PROTO), _HIP_BATCH_PROTO)
     return _hip
 
 
@@ -108,6 +110,10 @@ def check(rc: int):
 
 def declared_hip_symbols():
     return sorted(_HIP_SIG)
+
+
+def declared_hip_batch_symbols():
+    return sorted(_HIP_BATCH_SIG)
 
 
 def dp():

@@ -10,7 +10,10 @@ inside the library (stem_ar_decode_image): per position four launches (the first
 the last also emits the CDF indexes), one stream synchronisation and one call of the host rANS decoder -- injected as a
 C function pointer -- through a pinned mailbox.  (A cooperative single-launch variant was measured slower on ROCm 7.2:
 0.74 s vs 0.44 s per 1080p frame.)  By default one persistent kernel per image instead (csrc/ar_persistent.hip);
-`decode_route` names every form of the loop and says which one runs.  All forms are bit-identical.
+`decode_route` names every form of the loop and says which one runs.  All forms are bit-identical.  A batch is encoded in lockstep
+(stem_ar_encode_batch: one queue of wavefront steps for all images, one copy, the host coder per image on a thread pool), and the
+`*_each` entry points code several independent chains -- the GOPs evaluation.eval_sequence walks side by side -- with every transform
+at batch 1 and only the coding loops batched.
 """
 from __future__ import annotations
 
@@ -148,6 +151,16 @@ class _ARContext:
             F._chk(lib.stem_ar_finish_encode_wave(wgp.data_ptr(), self.table.data_ptr(), self.table.numel(), self.bound,
                                                   buf.data_ptr(), sym.data_ptr(), idx.data_ptr(), M, t, H, W, Wp, _P, st))
 
+    def encode_batch(self, buf, G, H, W, tp_b, hp_b, sym, idx):
+        """G images in lockstep (csrc/ar.hip: stem_ar_encode_batch): the five launches of a wavefront step cover all G images, whose
+        arithmetic -- and so every symbol and index -- is that of `encode_wavefront` image by image.  buf [G, H+4, W+4, M]; sym / idx
+        [G, H*W, M]; tp_b / hp_b: where the first image's priors start."""
+        M, P = self.M, 2 * self.M
+        npmax = min(H, (W + 2) // 3)
+        scratch = [torch.empty((G, npmax, n), device=buf.device) for n in (P, self.w0.shape[0], self.w1.shape[0], P)]
+        F._chk(_lib.hip().stem_ar_encode_batch(*self.net_args(), buf.data_ptr(), G, H, W, M, _P, tp_b, hp_b, *[t.data_ptr() for t in scratch],
+                                               *self.table_args(), sym.data_ptr(), idx.data_ptr(), F._stream()))
+
     def position_decode(self, buf, Wp, h, w, tp_pix, hp_pix, sym_prev, pix_prev, prev_is_left, idx_out):
         """The four products of position (h, w) as the decoder issues them (_Decode.stepwise): the first also writes back the previous
         position's y_hat (and uses it in place of the not-yet-visible left neighbour), the last one also emits the CDF indexes."""
@@ -219,6 +232,20 @@ def _encode_latents(model, target, hp, tp):
     dev = target.device
     ar = _ARContext(model, dev)
     tables = model.gaussian_conditional.host_tables()
+    if B > 1 and not _config.runtime().ar_stepwise:
+        # one queue of wavefront steps for the whole batch, one copy of all symbols and indexes, the host coder once per image on the pool
+        buf = torch.zeros((B, H + 2 * _P, W + 2 * _P, M), device=dev, dtype=torch.float32)
+        buf[:, _P:_P + H, _P:_P + W].permute(0, 3, 1, 2).copy_(target)
+        si = torch.empty((2, B, H * W, M), device=dev, dtype=torch.int32)
+        ar.encode_batch(buf, B, H, W, *_prior_addrs(tp, hp, 0, H, W, M), si[0], si[1])
+        sym, idx = si.cpu().numpy()
+
+        def code(b):
+            enc = BufferedRansEncoder()
+            enc.encode_with_indexes(sym[b], idx[b], tables)                        # ctypes releases the GIL for the call
+            return enc.flush()
+
+        return list(_POOL.map(code, range(B)))
     y_strings = []
     for b in range(B):
         buf = _padded(target[b:b + 1], H, W, M, dev)
@@ -240,6 +267,50 @@ def stem_decompress(model, strings, shape, y_cond):
     if model.RESIDUAL:
         out = F.add(out, _dense(yd))
     return out
+
+
+def _same_shapes(tensors, what):
+    shapes = {tuple(t.shape) for t in tensors}
+    if len(shapes) != 1 or next(iter(shapes))[0] != 1:
+        raise ValueError(f"{what}: one [1, ...] tensor per chain, all of one size, got {sorted(shapes)}")
+
+
+def stem_compress_each(model, y_curs, y_conds):
+    """`stem_compress` of several independent chains (the GOPs evaluation.eval_sequence codes side by side), one [1, M, H, W] pair per
+    chain.  The transforms of every chain run at batch 1 -- at another batch size the hyper-prior convolutions may pick another tile /
+    split-K plan and move a mean by an ulp, and a stream coded so need not decode at batch 1, which is how a stand-alone decoder runs --
+    and only the raster-order coding is batched (`_encode_latents`: its per-image arithmetic is fixed).  -> one result per chain, with
+    the keys and the bits `stem_compress` gives for that chain alone."""
+    _same_shapes(list(y_curs) + list(y_conds), "stem_compress_each")
+    if not model.HAS_SPM:
+        return [stem_compress(model, yc, yd) for yc, yd in zip(y_curs, y_conds)]
+    zs, hps, tps, targets = [], [], [], []
+    for y_cur, y_cond in zip(y_curs, y_conds):
+        z_strings, zshape, hp, tp = _hyper(model, y_cur, y_cond)
+        yc, yd = F.to_nhwc(y_cur.detach()), F.to_nhwc(y_cond.detach())
+        targets.append(F.sub(_dense(yc), _dense(yd)) if model.RESIDUAL else _dense(yc))
+        zs.append((z_strings, zshape)), hps.append(hp), tps.append(tp)
+    y_strings = _encode_latents(model, _cat_nhwc(targets), _cat_nhwc(hps), _cat_nhwc(tps) if tps[0] is not None else None)
+    return [{"strings": [[y], z], "shape": zshape} for y, (z, zshape) in zip(y_strings, zs)]
+
+
+def stem_decompress_each(model, strings, shapes, y_conds):
+    """`stem_decompress` of several independent chains: strings[i], shapes[i], y_conds[i] are one chain's arguments.  Transforms per chain
+    at batch 1, one batched `_decode_latents` call (the concurrent / lockstep routes of `decode_route`).  -> one decoded latent per chain
+    (what `stem_decompress` returns: the model's decompress() wraps it)."""
+    _same_shapes(y_conds, "stem_decompress_each")
+    if not model.HAS_SPM:
+        return [stem_decompress(model, s, sh, yd) for s, sh, yd in zip(strings, shapes, y_conds)]
+    hps, tps = [], []
+    for s, sh, y_cond in zip(strings, shapes, y_conds):
+        _, _, hp, tp = _hyper(model, None, y_cond, strings_z=s[1], shape=sh)
+        hps.append(hp), tps.append(tp)
+    out = _decode_latents(model, [s[0][0] for s in strings], _cat_nhwc(hps), _cat_nhwc(tps) if tps[0] is not None else None)
+    res = []
+    for i, y_cond in enumerate(y_conds):
+        o = _slice_nhwc(out, i)
+        res.append(F.add(o, _dense(F.to_nhwc(y_cond.detach()))) if model.RESIDUAL else o)
+    return res
 
 
 _ARP_TRUSTED = {}          # (M, EPM widths, device) -> the persistent decoder reproduced the per-position loop on this process's self-check
@@ -465,6 +536,63 @@ def iframe_decompress(model, strings, shape):
     y_hat = _decode_latents(model, strings[0], params, None)
     x_hat = F.to_nchw(model.g_s(y_hat), clamp01=True)
     return {"x_hat": x_hat, "y_hat": y_hat}
+
+
+def iframe_compress_each(model, xs):
+    """`iframe_compress` of several independent images, one [1, 3, h, w] tensor each: g_a, h_a, h_s per image at batch 1 (see
+    `stem_compress_each`), one batched raster-order coding.  -> one result per image, the bits of `iframe_compress` of it alone."""
+    _same_shapes(xs, "iframe_compress_each")
+    eb = model.entropy_bottleneck
+    zs, ys, params = [], [], []
+    for x in xs:
+        y = model.g_a(x)
+        z = model.h_a(y)
+        z_strings = eb.compress(z)
+        z_hat = eb.decompress(z_strings, z.shape[-2:]).to(y.device).float()
+        p = _dense(F.to_nhwc(model.h_s(z_hat)))
+        yn = _dense(F.to_nhwc(y.detach()))
+        _check_latent_size(yn, p, "images")
+        zs.append((z_strings, z.shape[-2:])), ys.append(yn), params.append(p)
+    y_strings = _encode_latents(model, _cat_nhwc(ys), _cat_nhwc(params), None)
+    return [{"strings": [[y], z], "shape": zshape} for y, (z, zshape) in zip(y_strings, zs)]
+
+
+def iframe_decompress_each(model, strings, shapes):
+    """`iframe_decompress` of several independent images: h_s and g_s per image at batch 1, one batched `_decode_latents` call.
+    -> one {"x_hat", "y_hat"} per image."""
+    dev = next(model.parameters()).device
+    params = []
+    for s, sh in zip(strings, shapes):
+        assert isinstance(s, list) and len(s) == 2
+        z_hat = model.entropy_bottleneck.decompress(s[1], sh)
+        params.append(_dense(F.to_nhwc(model.h_s(z_hat.to(dev).float()))))
+    _same_shapes(params, "iframe_decompress_each")
+    y_hats = _decode_latents(model, [s[0][0] for s in strings], _cat_nhwc(params), None)
+    res = []
+    for i in range(len(params)):
+        y_hat = _slice_nhwc(y_hats, i)
+        res.append({"x_hat": F.to_nchw(model.g_s(y_hat), clamp01=True), "y_hat": y_hat})
+    return res
+
+
+def _cat_nhwc(ts):
+    """dense NHWC [1, C, H, W] tensors -> one dense NHWC [len, C, H, W] (a copy per image, no arithmetic)"""
+    if len(ts) == 1:
+        return ts[0]
+    _, Cn, H, W = ts[0].shape
+    out = F.empty_nhwc(len(ts), Cn, H, W, ts[0].device)
+    for i, t in enumerate(ts):
+        out[i:i + 1].copy_(t)
+    return out
+
+
+def _slice_nhwc(t, i):
+    """image i of a dense NHWC batch as a dense NHWC [1, C, H, W] tensor of its own"""
+    if t.shape[0] == 1:
+        return t
+    out = F.empty_nhwc(1, *t.shape[1:], t.device)
+    out.copy_(t[i:i + 1])
+    return out
 
 
 def _dense(t):

@@ -13,6 +13,7 @@
 #include <chrono>
 
 #include "stem_common.h"
+#include "../../include/stem_ar_batch.h"
 
 // Encoder and decoder must produce the SAME floats for every entropy parameter (a mean that differs in the last bit
 // shifts y_hat, which feeds later contexts; a scale on the other side of a table entry desynchronises the coder), and the
@@ -628,5 +629,186 @@ STEM_EXPORT int stem_ar_decode_batch(const float *w_ctx, int ld_ctx, const float
                 t_launch / (H * W), t_wait / (H * W), t_host / (H * W));
     hipLaunchKernelGGL(ar_finish_decode_batch_kernel, dim3(cdiv(M * G, 256)), dim3(256), 0, st, gp, (long)P, sym_host, pix_prev, bufs, M, G);
     STEM_LAUNCH_CHECK("ar_decode_batch");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// ENCODER, G images in lockstep: the counterpart of stem_ar_decode_batch.  One image's wavefront step is five launches of a few
+// microseconds of work each, so W + 3(H-1) steps cost their launch latency; G independent images (the GOP chains of
+// evaluation.eval_sequence, the batch elements of compress()) share it: the same five launches cover the G * np positions of
+// step t.  The image index is folded into the position loop (j = g * np + p), every wavefront still spreads each dot product over its 64 lanes, and
+// a wavefront takes WAVE_R rows and up to WAVE_U positions at once: a register tile of WAVE_R * WAVE_U dot products fed by
+// WAVE_R + WAVE_U loads per k step.  Every (image, position, row) sum is accumulated exactly as
+// gemv3_wave_kernel does it -- k = lane * 4, += 256, segment after segment, xor-shuffle reduction -- so each image's floats,
+// symbols and indexes are those of stem_ar_encode_image.
+namespace {
+
+struct WSegB {
+    const float *x;      // image 0
+    int len, woff;
+    long sh, sw, sp;
+    long sg;             // floats between consecutive images
+};
+
+constexpr int WAVE_ROWS_B = 32;   // workgroup rows over which the G * np positions of a step are spread
+constexpr int WAVE_U = 4;         // positions a wavefront accumulates side by side ...
+constexpr int WAVE_R = 4;         // ... for this many output rows
+
+__host__ __device__ __forceinline__ void wave_range_hd(int t, int H, int Wd, int &h0, int &np)
+{
+    int lo = t - (Wd - 1);
+    lo = lo > 0 ? (lo + 2) / 3 : 0;
+    int hi = t / 3;
+    if (hi > H - 1) hi = H - 1;
+    h0 = lo;
+    np = hi - lo + 1;
+}
+
+// positions j0, j0 + dj, ..., j0 + (U-1) dj of the step (all < G * np) for the output rows n .. n + WAVE_R - 1: every k step loads
+// WAVE_R weight vectors and U x vectors for WAVE_R * U dot products (the single-image kernel loads two vectors per product; at G = 8
+// the step is bound by those L1 reads, not by launches)
+template <int U>
+__device__ __forceinline__ void wave_dots(const float *wr, int ldw, const float (&b)[WAVE_R], const WSegB (&segs)[3], float *y, int ldy, long ygs,
+                                          int n, int act, float slope, int lane, int j0, int dj, int np, int h0, int t)
+{
+    float acc[U][WAVE_R];
+    const float *xp[U][3];
+    size_t yo[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int j = j0 + u * dj, g = j / np, p = j - g * np;
+        const int h = h0 + p, w = t - 3 * h;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) xp[u][q] = segs[q].x + segs[q].sg * g + segs[q].sh * h + segs[q].sw * w + segs[q].sp * p;
+        yo[u] = (size_t)g * ygs + (size_t)p * ldy + n;
+#pragma unroll
+        for (int r = 0; r < WAVE_R; ++r) acc[u][r] = 0.f;
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const WSegB s = segs[q];
+        for (int k = lane * 4; k < s.len; k += 256) {
+            f32x4 wv[WAVE_R], xv[U];
+#pragma unroll
+            for (int r = 0; r < WAVE_R; ++r) wv[r] = *reinterpret_cast<const f32x4 *>(wr + (size_t)r * ldw + s.woff + k);
+#pragma unroll
+            for (int u = 0; u < U; ++u) xv[u] = *reinterpret_cast<const f32x4 *>(xp[u][q] + k);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int r = 0; r < WAVE_R; ++r) acc[u][r] += xv[u][0] * wv[r][0] + xv[u][1] * wv[r][1] + xv[u][2] * wv[r][2] + xv[u][3] * wv[r][3];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int r = 0; r < WAVE_R; ++r) {
+            float a = acc[u][r];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
+            if (lane == 0) {
+                float v = a + b[r];
+                if (act == STEM_ACT_LRELU) v = v > 0.f ? v : v * slope;
+                y[yo[u] + r] = v;
+            }
+        }
+}
+
+// N % WAVE_R == 0 (the entry point checks it): a wavefront's WAVE_R rows are all inside the matrix
+__global__ __launch_bounds__(256) void gemv3_wave_batch_kernel(const float *W, int ldw, const float *bias, WSegB s0, WSegB s1, WSegB s2,
+                                                               float *y, int ldy, long ygs, int N, int act, float slope, int t, int H, int Wd,
+                                                               int G)
+{
+    const int lane = threadIdx.x & 63;
+    const int n = (blockIdx.x * 4 + (threadIdx.x >> 6)) * WAVE_R;
+    if (n >= N) return;
+    int h0, np;
+    wave_range_hd(t, H, Wd, h0, np);
+    const int total = G * np, dj = gridDim.y;
+    const float *wr = W + (size_t)n * ldw;
+    float b[WAVE_R];
+#pragma unroll
+    for (int r = 0; r < WAVE_R; ++r) b[r] = bias ? bias[n + r] : 0.f;
+    const WSegB segs[3] = {s0, s1, s2};
+    int j = blockIdx.y;
+    for (; j + (WAVE_U - 1) * dj < total; j += WAVE_U * dj) wave_dots<WAVE_U>(wr, ldw, b, segs, y, ldy, ygs, n, act, slope, lane, j, dj, np, h0, t);
+    for (; j + dj < total; j += 2 * dj) wave_dots<2>(wr, ldw, b, segs, y, ldy, ygs, n, act, slope, lane, j, dj, np, h0, t);
+    for (; j < total; j += dj) wave_dots<1>(wr, ldw, b, segs, y, ldy, ygs, n, act, slope, lane, j, dj, np, h0, t);
+}
+
+__global__ void ar_finish_encode_wave_batch_kernel(const float *gp, long gps, const float *table, int T, float scale_bound, float *buf, long bufs,
+                                                   int32_t *sym, int32_t *idx, int M, int t, int H, int Wd, int Wp, int pad, int G)
+{
+    int h0, np;
+    wave_range_hd(t, H, Wd, h0, np);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= G * np * M) return;
+    const int j = i / M, c = i - j * M;
+    const int g = j / np, p = j - g * np;
+    const int h = h0 + p, w = t - 3 * h;
+    const float *gpp = gp + (size_t)g * gps + (size_t)p * 2 * M;
+    const float s = fmaxf(gpp[c], scale_bound), mu = gpp[M + c];
+    int k = T - 1;
+    for (int q = 0; q < T - 1; ++q) k -= (s <= table[q]) ? 1 : 0;
+    float *pix = buf + (size_t)g * bufs + ((size_t)(h + pad) * Wp + (w + pad)) * M;
+    const float qv = rintf(pix[c] - mu);
+    pix[c] = qv + mu;
+    const size_t o = (((size_t)g * H + h) * Wd + w) * M + c;
+    sym[o] = (int32_t)qv;
+    idx[o] = k;
+}
+
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+}   // namespace
+
+STEM_EXPORT int stem_ar_encode_batch(const float *w_ctx, int ld_ctx, const float *b_ctx, const float *w0, int ld0, const float *b0, int n0,
+                                     const float *w1, int ld1, const float *b1, int n1, const float *w2, int ld2, const float *b2,
+                                     float *buf, int G, int H, int W, int M, int pad, const float *tp, const float *hp,
+                                     float *wctx, float *wh1, float *wh2, float *wgp, const float *table, int T, float scale_bound,
+                                     float slope, int32_t *sym, int32_t *idx, void *stream)
+{
+    STEM_CHECK_ARG(w_ctx && b_ctx && w0 && b0 && w1 && b1 && w2 && b2 && buf && hp && wctx && wh1 && wh2 && wgp && table && sym && idx,
+                   "stem_ar_encode_batch: null pointer");
+    STEM_CHECK_ARG(G >= 1, "stem_ar_encode_batch: at least one image per call, got %d", G);
+    static_assert(WAVE_R == 4, "the size check below is what keeps a wavefront's WAVE_R rows inside each matrix (2M, n0, n1)");
+    STEM_CHECK_ARG(H > 0 && W > 0 && M > 0 && M % 4 == 0 && n0 > 0 && n1 > 0 && n0 % 4 == 0 && n1 % 4 == 0 && ld_ctx % 4 == 0 && ld0 % 4 == 0 &&
+                   ld1 % 4 == 0 && ld2 % 4 == 0 && T >= 1 && pad == 2, "stem_ar_encode_batch: bad sizes");
+    STEM_CHECK_ARG(aligned16(w_ctx) && aligned16(w0) && aligned16(w1) && aligned16(w2) && aligned16(buf) && aligned16(tp) && aligned16(hp) &&
+                   aligned16(wctx) && aligned16(wh1) && aligned16(wh2) && aligned16(wgp), "stem_ar_encode_batch: weights, buf, tp, hp and scratch must be 16-byte aligned");
+    const int maxp = H < (W + 2) / 3 ? H : (W + 2) / 3;
+    STEM_CHECK_ARG((long)G * maxp * M <= 0x7fffffffL, "stem_ar_encode_batch: G * positions per step * M = %ld does not fit an int", (long)G * maxp * M);
+    hipStream_t st = (hipStream_t)stream;
+    const int P = 2 * M, Wp = W + 2 * pad;
+    const long row = (long)Wp * M;
+    const long bufs = (long)(H + 2 * pad) * row, pris = (long)H * W * P;            // image strides of buf and of tp / hp
+    const WSegB none{nullptr, 0, 0, 0, 0, 0, 0};
+    // context window of position (h, w): rows h, h+1 (5 pixels) and h+2 (2 pixels) of the image's padded buffer, starting at column w
+    const WSegB c0{buf, 5 * M, 0, row, M, 0, bufs}, c1{buf + row, 5 * M, 5 * M, row, M, 0, bufs}, c2{buf + 2 * row, 2 * M, 10 * M, row, M, 0, bufs};
+    const WSegB sctx{wctx, P, tp ? 2 * P : P, 0, 0, P, (long)maxp * P};
+    const WSegB stp{tp, P, 0, (long)W * P, P, 0, pris}, shp{hp, P, tp ? P : 0, (long)W * P, P, 0, pris};
+    const WSegB sh1{wh1, n0, 0, 0, 0, n0, (long)maxp * n0}, sh2{wh2, n1, 0, 0, 0, n1, (long)maxp * n1};
+    for (int t = 0; t < W + 3 * (H - 1); ++t) {
+        int h0, np;
+        wave_range_hd(t, H, W, h0, np);
+        if (np <= 0) continue;                   // W < 3: steps between two rows hold no position
+        const int total = G * np;
+        const int gy = total < WAVE_ROWS_B ? total : WAVE_ROWS_B;
+        hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(P, 4 * WAVE_R), gy), dim3(256), 0, st, w_ctx, ld_ctx, b_ctx, c0, c1, c2, wctx, P, (long)maxp * P, P,
+                           0, 0.f, t, H, W, G);
+        if (tp)
+            hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(n0, 4 * WAVE_R), gy), dim3(256), 0, st, w0, ld0, b0, stp, shp, sctx, wh1, n0, (long)maxp * n0, n0,
+                               (int)STEM_ACT_LRELU, slope, t, H, W, G);
+        else
+            hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(n0, 4 * WAVE_R), gy), dim3(256), 0, st, w0, ld0, b0, shp, sctx, none, wh1, n0, (long)maxp * n0, n0,
+                               (int)STEM_ACT_LRELU, slope, t, H, W, G);
+        hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(n1, 4 * WAVE_R), gy), dim3(256), 0, st, w1, ld1, b1, sh1, none, none, wh2, n1, (long)maxp * n1, n1,
+                           (int)STEM_ACT_LRELU, slope, t, H, W, G);
+        hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(P, 4 * WAVE_R), gy), dim3(256), 0, st, w2, ld2, b2, sh2, none, none, wgp, P, (long)maxp * P, P,
+                           0, 0.f, t, H, W, G);
+        hipLaunchKernelGGL(ar_finish_encode_wave_batch_kernel, dim3(cdiv(total * M, 256)), dim3(256), 0, st, wgp, (long)maxp * P, table, T, scale_bound,
+                           buf, bufs, sym, idx, M, t, H, W, Wp, pad, G);
+    }
+    STEM_LAUNCH_CHECK("ar_encode_batch");
     return 0;
 }

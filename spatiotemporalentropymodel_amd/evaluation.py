@@ -26,7 +26,9 @@ an I + 2 P chain) through tests/test_hip_codec.py::test_eval_gop_chain_matches_r
 """
 from __future__ import annotations
 
+import io
 import math
+import os
 import time
 
 import torch
@@ -239,6 +241,125 @@ def eval_gop(imodel, stem, frames, gop=12, all_intra=False, with_msssim=True, yu
             out["type"] = "P"
         y_cond = out["y_conditioned"]
         per_frame.append(out)
+    n = max(1, len(per_frame))
+    ms = [f["ms-ssim"] for f in per_frame if f["ms-ssim"] is not None]
+    res = {"frames": per_frame, "psnr_ave": sum(f["psnr"] for f in per_frame) / n, "bpp_ave": sum(f["bpp"] for f in per_frame) / n,
+           "msssim_ave": (sum(ms) / len(ms)) if ms else None,
+           "estimate_bpp_ave": sum(f["estimate_bpp"] for f in per_frame) / n}
+    if yuv:
+        for k in ("psnr_y", "psnr_u", "psnr_v", "psnr_yuv"):
+            res[k + "_ave"] = sum(f[k] for f in per_frame) / n
+    return res
+
+
+def gop_schedule(n_frames, gop, concurrent_gops, all_intra=False):
+    """The order in which `eval_sequence` codes a sequence of `n_frames` frames (pure: no device).  A GOP is an I frame and the P frames
+    that follow it, an independent chain; GOP boundaries are `eval_gop`'s (frame k, 1-based, with k % gop == 1 is an I frame, and so is the
+    first frame; all_intra: every frame).  Up to `concurrent_gops` consecutive GOPs form a group whose chains advance together: step s of
+    a group holds the s-th frame of each of its GOPs, a chain drops out when its GOP ends (the last GOP may be short, the last group
+    small).  -> the list of steps, each a list of (frame index, 0-based, "I" | "P", chain = the GOP's number in the sequence)."""
+    if gop < 1 or concurrent_gops < 1:
+        raise ValueError(f"gop and concurrent_gops are at least 1, got {gop} and {concurrent_gops}")
+    starts = [i for i in range(n_frames) if all_intra or i == 0 or (i + 1) % gop == 1]
+    gops = [range(a, b) for a, b in zip(starts, starts[1:] + [n_frames])]
+    steps = []
+    for g0 in range(0, len(gops), concurrent_gops):
+        group = list(enumerate(gops[g0:g0 + concurrent_gops], start=g0))
+        for s in range(max(len(r) for _, r in group)):
+            steps.append([(r[s], "I" if s == 0 else "P", chain) for chain, r in group if s < len(r)])
+    return steps
+
+
+class _InOrder:
+    """`write_to` of eval_sequence: frames finish chain by chain, the file wants display order.  Every frame's planes arrive as bytes
+    (already on the host) and wait until all earlier frames have been written."""
+
+    def __init__(self, sink):
+        self.sink, self.next, self.held = sink, 0, {}
+
+    def put(self, index, data):
+        self.held[index] = data
+        while self.next in self.held:
+            data = self.held.pop(self.next)
+            if isinstance(self.sink, (str, os.PathLike)):
+                with open(self.sink, "ab") as f:
+                    f.write(data)
+            else:
+                self.sink.write(data)
+            self.next += 1
+
+
+@torch.no_grad()
+def eval_sequence(imodel, stem, frames, gop=12, concurrent_gops=8, all_intra=False, with_msssim=True, yuv=False, write_to=None):
+    """`eval_gop` with the sequence's GOPs coded side by side (`gop_schedule`): every GOP is an independent chain, and the raster-order
+    coding loops -- launch- and latency-bound for one image -- advance up to `concurrent_gops` chains together (codec.iframe_*_each,
+    codec.stem_*_each: one batched encoder queue, the concurrent / lockstep decoders).  Every transform still runs per chain at batch 1,
+    so each frame's strings, latents and reconstruction are the bits `eval_gop` produces for it and decode on their own.
+    frames: a sequence (indexable, with a length) or an iterable of [3,h,w] images of one size, in display order.  Returns what `eval_gop`
+    returns: "frames" in display order, each with `eval_gop`'s keys and values, and the same averages.  Only the timing differs:
+    "encoding_time" / "decoding_time" are the wall time of the frame's step divided by the number of chains in it, which the new key
+    "concurrent" holds.  write_to receives the frames in display order.  concurrent_gops=1: one chain per step."""
+    from . import codec
+    if not (hasattr(frames, "__getitem__") and hasattr(frames, "__len__")):
+        frames = list(frames)
+    writer = _InOrder(write_to) if write_to is not None else None
+    per_frame = [None] * len(frames)
+    y_cond = {}                                                  # chain -> the decoded latents of its previous frame
+    for step in gop_schedule(len(frames), gop, concurrent_gops, all_intra):
+        srcs = [frames[i] for i, _, _ in step]
+        xs = [f.unsqueeze(0) for f in srcs]
+        padded = [bitstream.pad(x, 64) for x in xs]
+        ipos = [k for k, (_, kind, _) in enumerate(step) if kind == "I"]
+        ppos = [k for k, (_, kind, _) in enumerate(step) if kind == "P"]
+        enc, fwd, dec, y_hat, x_hat = ([None] * len(step) for _ in range(5))
+        _sync(xs[0])
+        start = time.time()
+        if ipos:
+            for k, e in zip(ipos, codec.iframe_compress_each(imodel, [padded[k] for k in ipos])):
+                enc[k] = e
+                fwd[k] = imodel(padded[k])
+        if ppos:
+            conds = [y_cond[step[k][2]] for k in ppos]
+            y_curs = [imodel.getY(padded[k])[0] for k in ppos]
+            for k, y_cur, c in zip(ppos, y_curs, conds):
+                fwd[k] = stem(y_cur, c)
+            for k, e in zip(ppos, codec.stem_compress_each(stem, y_curs, conds)):
+                enc[k] = e
+        _sync(xs[0])
+        enc_time = (time.time() - start) / len(step)
+        start = time.time()
+        if ipos:
+            for k, d in zip(ipos, codec.iframe_decompress_each(imodel, [enc[k]["strings"] for k in ipos], [enc[k]["shape"] for k in ipos])):
+                dec[k], y_hat[k], x_hat[k] = d, d["y_hat"], d["x_hat"]
+        if ppos:
+            outs = codec.stem_decompress_each(stem, [enc[k]["strings"] for k in ppos], [enc[k]["shape"] for k in ppos], conds)
+            for k, y in zip(ppos, outs):
+                dec[k] = {"y_hat": y} if stem.DECOMPRESS_RETURNS_DICT else y
+                y_hat[k] = y
+                x_hat[k] = imodel.getX(y)
+        _sync(xs[0])
+        dec_time = (time.time() - start) / len(step)
+        for k, (index, kind, chain) in enumerate(step):
+            x = xs[k]
+            h, w = x.size(2), x.size(3)
+            xh = bitstream.crop(x_hat[k], (h, w))
+            num_pixels = x.size(0) * h * w
+            bpp, est = _bpp_terms(enc[k], fwd[k], num_pixels)
+            quality = _metrics(x, xh, with_msssim)
+            sink = io.BytesIO() if writer is not None else None
+            out = {"y_conditioned": y_hat[k], "psnr": quality[0], "ms-ssim": quality[1], "bpp": bpp, "estimate_bpp": sum(est.values()),
+                   "estimate_y_bpp": est.get("y"), "estimate_z_bpp": est.get("z"), "y_bpp": len(enc[k]["strings"][0][0]) * 8.0 / num_pixels,
+                   "z_bpp": len(enc[k]["strings"][1][0]) * 8.0 / num_pixels, "encoding_time": enc_time, "decoding_time": dec_time}
+            if kind == "I":
+                out["out_forward"] = fwd[k]
+            else:
+                out["entropy_params"] = dec[k].get("entropy_params") if isinstance(dec[k], dict) else None
+            out.update({"strings": enc[k]["strings"], "shape": tuple(enc[k]["shape"]), "x_hat": xh, **_yuv_metrics(srcs[k], xh, yuv, sink),
+                        "type": kind, "concurrent": len(step)})
+            if writer is not None:
+                writer.put(index, sink.getvalue())
+            per_frame[index] = out
+        y_cond = {chain: y_hat[k] for k, (_, _, chain) in enumerate(step)}      # a chain that left the step has ended
     n = max(1, len(per_frame))
     ms = [f["ms-ssim"] for f in per_frame if f["ms-ssim"] is not None]
     res = {"frames": per_frame, "psnr_ave": sum(f["psnr"] for f in per_frame) / n, "bpp_ave": sum(f["bpp"] for f in per_frame) / n,
