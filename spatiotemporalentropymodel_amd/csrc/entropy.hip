@@ -891,9 +891,11 @@ __global__ __launch_bounds__(256) void em_loss_finalize_kernel(const double *py,
 //   phase 2: one (channel, quantile) pair per thread, AUX_T pairs per pass (3 C = 768 for the training model: one pass): the
 //            forward keeps the gates' tanh values, the reverse pass walks only the input-gradient chain (no parameter gradients)
 //            and re-uses them.
-// Same numbers as before: the transforms, the forward and the d/dv chain are the operations of eb_prepare / eb_logits /
-// eb_logits_bwd in their order, and the |d| terms are summed in the order of the 256-thread kernel (item t, t + 256, t + 512 per
-// slot, then the same tree).  86 -> ~15 us per launch.
+// The same operations as eb_aux_kernel -- the transforms, the forward and the d/dv chain are those of eb_prepare / eb_logits /
+// eb_logits_bwd in their order -- but not the same bits: the compiler contracts the two bodies differently, so dq differs from
+// eb_aux_kernel's in the last place or two (up to 2.4e-7 absolute measured on gfx950), and the loss is summed in another order
+// (here item t, t + 256, t + 512, ... per slot, then one tree; there one tree per workgroup of 256 consecutive items and an atomic
+// per workgroup), which shows from C = 86 on.  Both are held to float64 by tests/test_hip_entropy_ops.py.  86 -> ~15 us per launch.
 constexpr int AUX_T = 768;
 __global__ __launch_bounds__(AUX_T) void eb_aux_block_kernel(const float *quant, const float *pack, const float *target, float *loss,
                                                              float *dq, int C, int accumulate)
