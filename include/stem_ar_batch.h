@@ -1,5 +1,6 @@
 /*
- * stem_ar_batch.h -- C ABI of libstem_hip.so, continued: raster-order coding of several independent images in one queue.
+ * stem_ar_batch.h -- C ABI of libstem_hip.so, continued: raster-order coding of several independent images in one queue, and the
+ * wavefront symbol order (a second, opt-in order of the coded symbols in which the decoder advances a step of positions at a time).
  *
  * Same conventions as stem_hip.h (device pointers owned by the caller, asynchronous on `stream`, 0 on success, stem_last_error()
  * on failure).  The entry points here are not launch-tape entries (csrc/tape_entries.inc lists stem_hip.h's): the coding loops
@@ -26,6 +27,45 @@ int stem_ar_encode_batch(const float *w_ctx, int ld_ctx, const float *b_ctx, con
                          float *buf, int G, int H, int W, int M, int pad, const float *tp, const float *hp,
                          float *wctx, float *wh1, float *wh2, float *wgp, const float *table, int T, float scale_bound,
                          float slope, int32_t *sym, int32_t *idx, void *stream);
+
+/* ---- wavefront symbol order ------------------------------------------------------------------------------------------------
+ * Under the 5x5 type-A mask position (h, w) reads rows h-2 and h-1 at columns w-2 .. w+2 and row h at columns w-2 and w-1, so all
+ * positions with equal t = w + 3h are independent of each other.  A stream in WAVEFRONT ORDER holds the symbols of an H x W latent of
+ * M channels like this:
+ *   - steps run t = 0 .. W + 3(H-1) - 1;
+ *   - within a step, rows run h = h0(t) .. h0(t) + np(t) - 1 in ascending order, with w = t - 3h, where
+ *     h0(t) = max(0, ceil((t - (W-1)) / 3)) and np(t) = min(H-1, floor(t / 3)) - h0(t) + 1  (wave_range of csrc/ar.hip; np(t) = 0 for
+ *     the steps between two rows of a latent with W < 3);
+ *   - within a position, channels run c = 0 .. M-1.
+ * The rank of (h, w, c) is therefore M * (sum over t' < t of np(t')) + (h - h0(t)) * M + c.  codec.wave_order(H, W) states the same
+ * order on the host.  Raster order (rank (h * W + w) * M + c) is the reference's and stays the default; a wavefront stream is this
+ * project's own format. */
+
+/* sym_raster / idx_raster [G][H*W][M] (what stem_ar_encode_image / stem_ar_encode_batch write) -> sym_wave / idx_wave [G][H*W][M] in
+ * wavefront order per image; one launch gathers both tensors.  Device pointers; source and destination must not overlap. */
+int stem_ar_to_wave_order(const int32_t *sym_raster, const int32_t *idx_raster, int32_t *sym_wave, int32_t *idx_wave, int G, int H, int W,
+                          int M, void *stream);
+
+/* the host symbol decoder of stem_ar_decode_wave_batch: the signature of stem_rans_decoder_decode (include/stem_rans.h), and of
+ * stem_symbol_decoder_fn (stem_hip.h) */
+typedef int (*stem_wave_symbol_decoder_fn)(void *dec, const int32_t *indexes, size_t n, const int32_t *cdfs, int ncdf, int cdf_stride,
+                                           const int32_t *sizes, const int32_t *offsets, int32_t *out);
+
+/* Decoder of wavefront-ordered streams for G >= 1 independent images of equal H, W, M in lockstep: W + 3(H-1) steps instead of the
+ * H * W positions of stem_ar_decode_batch.  Step t issues the four products of stem_ar_encode_batch's step t (same kernel, grid and
+ * accumulation order: every entropy parameter is the encoder's float), writes the step's CDF indexes to the pinned mailbox, makes ONE
+ * stream synchronisation, calls `decode(decs[g], idx_host + g * npmax * M, np(t) * M, ..., sym_host + g * npmax * M)` once per
+ * image, and commits y_hat = symbol + mean of the step's positions to buf.  buf [G][(H+4)][(W+4)][M], zero on entry, y_hat on return
+ * (the call returns after the stream has drained: the mailboxes are free again); tp (may be NULL) / hp [G][H*W][2M];
+ * wctx/wh1/wh2/wgp: scratch [G][npmax][2M | n0 | n1 | 2M] with npmax = min(H,(W+2)/3); idx_host / sym_host: pinned, device-visible
+ * [G][npmax][M]; decs[G]: one decoder handle per image.  Device pointers 16-byte aligned, pad == 2, M, n0, n1 and the row lengths
+ * multiples of 4. */
+int stem_ar_decode_wave_batch(const float *w_ctx, int ld_ctx, const float *b_ctx, const float *w0, int ld0, const float *b0, int n0,
+                              const float *w1, int ld1, const float *b1, int n1, const float *w2, int ld2, const float *b2,
+                              float *buf, int G, int H, int W, int M, int pad, const float *tp, const float *hp,
+                              float *wctx, float *wh1, float *wh2, float *wgp, const float *table, int T, float scale_bound, float slope,
+                              int32_t *idx_host, int32_t *sym_host, stem_wave_symbol_decoder_fn decode, void *const *decs,
+                              const int32_t *cdfs, int ncdf, int cdf_stride, const int32_t *sizes, const int32_t *offsets, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,8 @@
 """Bitstream container of the reference tooling (compressai_examples/codec.py:63-220), byte-compatible:
 
     2 bytes  header: model id | (metric << 4 | quality-1)           get_header / parse_header  (:93-119)
+             bit 7 of the second byte (never set by the reference: its metric ids stay below 8) marks a record whose y string is in
+             wavefront symbol order (codec.wave_order), this project's own format; `stream_order` reads it
     2 x u32  original (h, w)                                         big-endian                 (:181-182)
     3 x u32  (shape[0], shape[1], n_strings)                                                    (:183-184)
     n x      u32 length + raw bytes of each string (one batch element per string list)          (:185-187)
@@ -59,22 +61,45 @@ def _read_exact(fd, n):
     return buf
 
 
-def get_header(model_name, metric, quality):
-    """1 byte model id, 4 bits metric, 4 bits quality-1 (codec.py:93-102)."""
+ORDER_BIT = 0x80       # second header byte: the y string is in wavefront symbol order
+
+
+class _Header(tuple):
+    """(model, metric, quality) as parse_header always returned it, with the record's symbol order as an attribute"""
+    order = "raster"
+
+
+def get_header(model_name, metric, quality, order="raster"):
+    """1 byte model id, 4 bits metric, 4 bits quality-1 (codec.py:93-102).  order="wavefront" sets bit 7 of the second byte; raster
+    headers are the reference's."""
+    if order not in ("raster", "wavefront"):
+        raise ValueError(f'unknown symbol order "{order}"')
     if model_name not in model_ids:
         raise ValueError(f'unknown model "{model_name}"')
     if metric not in metric_ids:
         raise ValueError(f'unknown metric "{metric}"')
     code = (metric_ids[metric] << 4) | (quality - 1 & 0x0F)
-    return model_ids[model_name], code
+    if metric_ids[metric] >= 8:
+        raise ValueError(f'metric id {metric_ids[metric]} of "{metric}" reaches the symbol-order bit')
+    return model_ids[model_name], code | (ORDER_BIT if order == "wavefront" else 0)
 
 
 def parse_header(header):
-    """codec.py:105-119"""
+    """codec.py:105-119; the symbol-order bit is masked: the same triple for both orders (it carries the order as `.order`)"""
     model_id, code = header
     quality = (code & 0x0F) + 1
-    metric = code >> 4
-    return inverse_dict(model_ids)[model_id], inverse_dict(metric_ids)[metric], quality
+    metric = (code & ~ORDER_BIT & 0xFF) >> 4
+    parsed = _Header((inverse_dict(model_ids)[model_id], inverse_dict(metric_ids)[metric], quality))
+    parsed.order = "wavefront" if code & ORDER_BIT else "raster"
+    return parsed
+
+
+def stream_order(header):
+    """the symbol order of a record's y string, from its 2-byte header as `get_header` made it or from what `parse_header` /
+    `read_frame` returned for it: "raster" or "wavefront" """
+    if isinstance(header, _Header):
+        return header.order
+    return "wavefront" if header[1] & ORDER_BIT else "raster"
 
 
 def write_frame(fd, header, original_size, shape, strings):

@@ -14,6 +14,11 @@ C function pointer -- through a pinned mailbox.  (A cooperative single-launch va
 (stem_ar_encode_batch: one queue of wavefront steps for all images, one copy, the host coder per image on a thread pool), and the
 `*_each` entry points code several independent chains -- the GOPs evaluation.eval_sequence walks side by side -- with every transform
 at batch 1 and only the coding loops batched.
+
+`order="wavefront"` (every compress / decompress entry point; default "raster", the reference's) codes the same symbols in the order of
+the encoder's wavefront steps (`wave_order`; include/stem_ar_batch.h states it): the decoder then advances a step of positions per host
+round trip -- W + 3(H-1) of them instead of H * W -- with the encoder's own launches (stem_ar_decode_wave_batch).  Every quantised value
+is that of the raster route; the y string is this project's own format, which the reference's decoder cannot read.
 """
 from __future__ import annotations
 
@@ -21,6 +26,7 @@ import ctypes as C
 import warnings
 from concurrent.futures import ThreadPoolExecutor
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -31,6 +37,34 @@ from .weights import closed_form_input
 
 _K = 5      # context kernel size
 _P = 2      # its padding
+
+
+ORDERS = ("raster", "wavefront")
+
+
+def _check_order(order, model=None):
+    """`order` names a symbol order, and the model has a raster loop to reorder (asked before any device work)"""
+    if order not in ORDERS:
+        raise ValueError(f"order is one of {ORDERS}, got {order!r}")
+    if order == "wavefront" and model is not None and not model.HAS_SPM:
+        raise ValueError(f'order="wavefront": {type(model).__name__} has no spatial prior -- its latents are coded in one shot, there is no '
+                         "raster-order loop whose symbols could be reordered")
+
+
+def wave_order(H, W):
+    """The wavefront symbol order of an H x W latent (pure: numpy only).  Steps run t = 0 .. W + 3(H-1) - 1; within a step rows run
+    h = h0(t) .. h0(t) + np(t) - 1 ascending with w = t - 3h (h0, np: wave_range of csrc/ar.hip); within a position the channels run
+    0 .. M-1.  -> (the raster indices h * W + w in wavefront order, int64 [H*W]; the step sizes np(t), int64 [W + 3(H-1)])"""
+    if H < 1 or W < 1:
+        raise ValueError(f"wave_order: a latent has at least one position, got {H} x {W}")
+    order, sizes = [], []
+    for t in range(W + 3 * (H - 1)):
+        lo = t - (W - 1)
+        h0 = (lo + 2) // 3 if lo > 0 else 0
+        h1 = min(t // 3, H - 1)
+        sizes.append(max(0, h1 - h0 + 1))
+        order.extend(h * W + (t - 3 * h) for h in range(h0, h1 + 1))
+    return np.asarray(order, dtype=np.int64), np.asarray(sizes, dtype=np.int64)
 
 
 def _chain(layers, x):
@@ -213,7 +247,16 @@ def _decoder_on(string):
     return dec
 
 
-def stem_compress(model, y_cur, y_cond):
+def _result(y_strings, z_strings, zshape, order):
+    """what compress returns; "order" only where it is not the reference's, so raster results are the dictionaries they were"""
+    res = {"strings": [y_strings, z_strings], "shape": zshape}
+    if order != "raster":
+        res["order"] = order
+    return res
+
+
+def stem_compress(model, y_cur, y_cond, order="raster"):
+    _check_order(order, model)
     z_strings, zshape, hp, tp = _hyper(model, y_cur, y_cond)
     yc, yd = F.to_nhwc(y_cur.detach()), F.to_nhwc(y_cond.detach())
     target = F.sub(_dense(yc), _dense(yd)) if model.RESIDUAL else _dense(yc)
@@ -221,17 +264,39 @@ def stem_compress(model, y_cur, y_cond):
         indexes, means = _one_shot(model, hp, tp)
         y_strings = model.gaussian_conditional.compress(target, indexes, means=means)
     else:
-        y_strings = _encode_latents(model, target, hp, tp)
-    return {"strings": [y_strings, z_strings], "shape": zshape}
+        y_strings = _encode_latents(model, target, hp, tp, order)
+    return _result(y_strings, z_strings, zshape, order)
 
 
-def _encode_latents(model, target, hp, tp):
+def _encode_latents(model, target, hp, tp, order="raster"):
     """the raster-order coding of `target` (dense NHWC [B, M, H, W]) given the hyper prior `hp` and the temporal prior `tp` (or
-    None): spatiotemporalpriors.py:916-961 / priors.py:586-631 -> one string per image"""
+    None): spatiotemporalpriors.py:916-961 / priors.py:586-631 -> one string per image.  order="wavefront": the same symbols and
+    indexes, handed to the host coder in the order of `wave_order`."""
+    _check_order(order)
     B, M, H, W = target.shape
     dev = target.device
     ar = _ARContext(model, dev)
     tables = model.gaussian_conditional.host_tables()
+    if order == "wavefront":
+        # the existing encoder (one image or the batch), one launch that gathers symbols and indexes into step order, one copy
+        si = torch.empty((2, B, H * W, M), device=dev, dtype=torch.int32)
+        if B > 1 and not _config.runtime().ar_stepwise:
+            buf = torch.zeros((B, H + 2 * _P, W + 2 * _P, M), device=dev, dtype=torch.float32)
+            buf[:, _P:_P + H, _P:_P + W].permute(0, 3, 1, 2).copy_(target)
+            ar.encode_batch(buf, B, H, W, *_prior_addrs(tp, hp, 0, H, W, M), si[0], si[1])
+        else:
+            for b in range(B):
+                ar.encode_wavefront(_padded(target[b:b + 1], H, W, M, dev), H, W, *_prior_addrs(tp, hp, b, H, W, M), si[0, b], si[1, b])
+        sw = torch.empty_like(si)
+        F._chk(_lib.hip().stem_ar_to_wave_order(si[0].data_ptr(), si[1].data_ptr(), sw[0].data_ptr(), sw[1].data_ptr(), B, H, W, M, F._stream()))
+        sym, idx = sw.cpu().numpy()
+
+        def code_wave(b):
+            enc = BufferedRansEncoder()
+            enc.encode_with_indexes(sym[b], idx[b], tables)                        # one host call per image
+            return enc.flush()
+
+        return list(_POOL.map(code_wave, range(B))) if B > 1 else [code_wave(0)]
     if B > 1 and not _config.runtime().ar_stepwise:
         # one queue of wavefront steps for the whole batch, one copy of all symbols and indexes, the host coder once per image on the pool
         buf = torch.zeros((B, H + 2 * _P, W + 2 * _P, M), device=dev, dtype=torch.float32)
@@ -257,13 +322,14 @@ def _encode_latents(model, target, hp, tp):
     return y_strings
 
 
-def stem_decompress(model, strings, shape, y_cond):
+def stem_decompress(model, strings, shape, y_cond, order="raster"):
+    _check_order(order, model)
     _, _, hp, tp = _hyper(model, None, y_cond, strings_z=strings[1], shape=shape)
     yd = F.to_nhwc(y_cond.detach())
     if not model.HAS_SPM:
         indexes, means = _one_shot(model, hp, tp)
         return model.gaussian_conditional.decompress(strings[0], indexes, means=means)
-    out = _decode_latents(model, strings[0], hp, tp)
+    out = _decode_latents(model, strings[0], hp, tp, order=order)
     if model.RESIDUAL:
         out = F.add(out, _dense(yd))
     return out
@@ -275,12 +341,13 @@ def _same_shapes(tensors, what):
         raise ValueError(f"{what}: one [1, ...] tensor per chain, all of one size, got {sorted(shapes)}")
 
 
-def stem_compress_each(model, y_curs, y_conds):
+def stem_compress_each(model, y_curs, y_conds, order="raster"):
     """`stem_compress` of several independent chains (the GOPs evaluation.eval_sequence codes side by side), one [1, M, H, W] pair per
     chain.  The transforms of every chain run at batch 1 -- at another batch size the hyper-prior convolutions may pick another tile /
     split-K plan and move a mean by an ulp, and a stream coded so need not decode at batch 1, which is how a stand-alone decoder runs --
     and only the raster-order coding is batched (`_encode_latents`: its per-image arithmetic is fixed).  -> one result per chain, with
     the keys and the bits `stem_compress` gives for that chain alone."""
+    _check_order(order, model)
     _same_shapes(list(y_curs) + list(y_conds), "stem_compress_each")
     if not model.HAS_SPM:
         return [stem_compress(model, yc, yd) for yc, yd in zip(y_curs, y_conds)]
@@ -290,14 +357,15 @@ def stem_compress_each(model, y_curs, y_conds):
         yc, yd = F.to_nhwc(y_cur.detach()), F.to_nhwc(y_cond.detach())
         targets.append(F.sub(_dense(yc), _dense(yd)) if model.RESIDUAL else _dense(yc))
         zs.append((z_strings, zshape)), hps.append(hp), tps.append(tp)
-    y_strings = _encode_latents(model, _cat_nhwc(targets), _cat_nhwc(hps), _cat_nhwc(tps) if tps[0] is not None else None)
-    return [{"strings": [[y], z], "shape": zshape} for y, (z, zshape) in zip(y_strings, zs)]
+    y_strings = _encode_latents(model, _cat_nhwc(targets), _cat_nhwc(hps), _cat_nhwc(tps) if tps[0] is not None else None, order)
+    return [_result([y], z, zshape, order) for y, (z, zshape) in zip(y_strings, zs)]
 
 
-def stem_decompress_each(model, strings, shapes, y_conds):
+def stem_decompress_each(model, strings, shapes, y_conds, order="raster"):
     """`stem_decompress` of several independent chains: strings[i], shapes[i], y_conds[i] are one chain's arguments.  Transforms per chain
     at batch 1, one batched `_decode_latents` call (the concurrent / lockstep routes of `decode_route`).  -> one decoded latent per chain
     (what `stem_decompress` returns: the model's decompress() wraps it)."""
+    _check_order(order, model)
     _same_shapes(y_conds, "stem_decompress_each")
     if not model.HAS_SPM:
         return [stem_decompress(model, s, sh, yd) for s, sh, yd in zip(strings, shapes, y_conds)]
@@ -305,7 +373,7 @@ def stem_decompress_each(model, strings, shapes, y_conds):
     for s, sh, y_cond in zip(strings, shapes, y_conds):
         _, _, hp, tp = _hyper(model, None, y_cond, strings_z=s[1], shape=sh)
         hps.append(hp), tps.append(tp)
-    out = _decode_latents(model, [s[0][0] for s in strings], _cat_nhwc(hps), _cat_nhwc(tps) if tps[0] is not None else None)
+    out = _decode_latents(model, [s[0][0] for s in strings], _cat_nhwc(hps), _cat_nhwc(tps) if tps[0] is not None else None, order=order)
     res = []
     for i, y_cond in enumerate(y_conds):
         o = _slice_nhwc(out, i)
@@ -375,11 +443,16 @@ def decode_route(B, cfg, persistent_ok, force_loop=False):
     return "persistent" if persistent else "loop"
 
 
-def _decode_latents(model, strings_y, hp, tp, force_loop=False):
+def _decode_latents(model, strings_y, hp, tp, force_loop=False, order="raster"):
     """the raster-order decoding of spatiotemporalpriors.py:1015-1054 / priors.py:676-716 for every image of the batch, given the
     hyper prior `hp` (dense NHWC [B, 2M, H, W]) and the temporal prior `tp` (or None) -> the decoded latents, dense NHWC.
-    `force_loop`: the per-position loop whatever the configuration prefers (_persistent_selfcheck's reference)."""
+    `force_loop`: the per-position loop whatever the configuration prefers (_persistent_selfcheck's reference).  order="wavefront":
+    the strings hold their symbols in the order of `wave_order`; one runner decodes them (`_Decode.wave`), `decode_route` is not asked."""
+    _check_order(order)
     d = _Decode(model, strings_y, hp, tp)
+    if order == "wavefront":
+        d.wave()
+        return d.out
     cfg = _config.runtime()
     kind = decode_route(d.B, cfg, _persistent_ok(model, d.ar, d.dev, cfg, force_loop), force_loop)
     if kind == "lockstep":
@@ -430,6 +503,24 @@ class _Decode:
                                                  self.decode_fn, C.addressof(handles), *self.tables.args(), F._stream()))
             self.out[b0:b0 + G].copy_(buf[:, _P:_P + H, _P:_P + W].permute(0, 3, 1, 2))
 
+    def wave(self):
+        """Wavefront-ordered strings (csrc/ar.hip: stem_ar_decode_wave_batch): W + 3(H-1) steps instead of H * W positions.  A step is
+        the encoder's four batched products over the step's positions of up to eight images, one stream synchronisation and one call
+        of the host coder per image for the step's np * M symbols, through mailboxes of the largest step's size."""
+        ar, B, H, W, M, dev = self.ar, self.B, self.H, self.W, self.M, self.dev
+        npmax = min(H, (W + 2) // 3)
+        for b0 in range(0, B, 8):                            # up to eight images per call
+            G = min(8, B - b0)
+            buf = torch.zeros((G, H + 2 * _P, W + 2 * _P, M), device=dev, dtype=torch.float32)
+            scratch = [torch.empty((G, npmax, n), device=dev, dtype=torch.float32) for n in (2 * M, ar.w0.shape[0], ar.w1.shape[0], 2 * M)]
+            idx_g, sym_g = (torch.empty((G, npmax, M), dtype=torch.int32).pin_memory() for _ in range(2))
+            decs = [_decoder_on(s) for s in self.strings[b0:b0 + G]]
+            handles = (C.c_void_p * G)(*[d._h for d in decs])
+            F._chk(self.lib.stem_ar_decode_wave_batch(*ar.net_args(), buf.data_ptr(), G, H, W, M, _P, *_prior_addrs(self.tp, self.hp, b0, H, W, M),
+                                                      *[t.data_ptr() for t in scratch], *ar.table_args(), idx_g.data_ptr(), sym_g.data_ptr(),
+                                                      self.decode_fn, C.addressof(handles), *self.tables.args(), F._stream()))
+            self.out[b0:b0 + G].copy_(buf[:, _P:_P + H, _P:_P + W].permute(0, 3, 1, 2))
+
     def stepwise(self, b):
         """The loop of stem_ar_decode_image written with the single-step C-ABI entry points (stem_gemv3_decode, stem_gemv3, stem_ar_finish_decode)
         and the Python RansDecoder: what a host without the fused call would run; the GPU tests check that both produce the same latents."""
@@ -446,6 +537,10 @@ class _Decode:
                 pos = h * W + w
                 hp_pix = hp_b + 4 * (pos * 2 * M)
                 tp_pix = tp_b + 4 * (pos * 2 * M) if tp_b else 0
+                if prev_pix and w == 0 and W <= 3:
+                    # the previous position (h-1, W-1) is inside this window's rows above: committed first, not folded into the product
+                    F._chk(self.lib.stem_ar_finish_decode(ar.gp.data_ptr(), sym, prev_pix, M, F._stream()))
+                    prev_pix = 0
                 ar.position_decode(buf, Wp, h, w, tp_pix, hp_pix, sym if prev_pix else 0, prev_pix, w > 0, idx)
                 stream.synchronize()
                 sym_np[:] = dec.decode_stream_np(idx_np, self.tables)
@@ -513,9 +608,10 @@ class _Decode:
 
 
 # ---- the I-frame codec: JointAutoregressiveHierarchicalPriors ("mbt2018") --------------------------------------------------------
-def iframe_compress(model, x):
+def iframe_compress(model, x, order="raster"):
     """compressai/models/priors.py:544-584: y = g_a(x), z = h_a(y) through the bottleneck's coder, params = h_s(z_hat), then the
     raster-order coding of y itself given params -- the same loop as a STEM model without temporal prior and without residual"""
+    _check_order(order, model)
     eb = model.entropy_bottleneck
     y = model.g_a(x)
     z = model.h_a(y)
@@ -524,23 +620,25 @@ def iframe_compress(model, x):
     params = _dense(F.to_nhwc(model.h_s(z_hat)))
     yn = _dense(F.to_nhwc(y.detach()))
     _check_latent_size(yn, params, "images")
-    return {"strings": [_encode_latents(model, yn, params, None), z_strings], "shape": z.shape[-2:]}
+    return _result(_encode_latents(model, yn, params, None, order), z_strings, z.shape[-2:], order)
 
 
-def iframe_decompress(model, strings, shape):
+def iframe_decompress(model, strings, shape, order="raster"):
     """compressai/models/priors.py:633-674 -> {"x_hat", "y_hat"}"""
+    _check_order(order, model)
     assert isinstance(strings, list) and len(strings) == 2
     z_hat = model.entropy_bottleneck.decompress(strings[1], shape)
     dev = next(model.parameters()).device
     params = _dense(F.to_nhwc(model.h_s(z_hat.to(dev).float())))
-    y_hat = _decode_latents(model, strings[0], params, None)
+    y_hat = _decode_latents(model, strings[0], params, None, order=order)
     x_hat = F.to_nchw(model.g_s(y_hat), clamp01=True)
     return {"x_hat": x_hat, "y_hat": y_hat}
 
 
-def iframe_compress_each(model, xs):
+def iframe_compress_each(model, xs, order="raster"):
     """`iframe_compress` of several independent images, one [1, 3, h, w] tensor each: g_a, h_a, h_s per image at batch 1 (see
     `stem_compress_each`), one batched raster-order coding.  -> one result per image, the bits of `iframe_compress` of it alone."""
+    _check_order(order, model)
     _same_shapes(xs, "iframe_compress_each")
     eb = model.entropy_bottleneck
     zs, ys, params = [], [], []
@@ -553,13 +651,14 @@ def iframe_compress_each(model, xs):
         yn = _dense(F.to_nhwc(y.detach()))
         _check_latent_size(yn, p, "images")
         zs.append((z_strings, z.shape[-2:])), ys.append(yn), params.append(p)
-    y_strings = _encode_latents(model, _cat_nhwc(ys), _cat_nhwc(params), None)
-    return [{"strings": [[y], z], "shape": zshape} for y, (z, zshape) in zip(y_strings, zs)]
+    y_strings = _encode_latents(model, _cat_nhwc(ys), _cat_nhwc(params), None, order)
+    return [_result([y], z, zshape, order) for y, (z, zshape) in zip(y_strings, zs)]
 
 
-def iframe_decompress_each(model, strings, shapes):
+def iframe_decompress_each(model, strings, shapes, order="raster"):
     """`iframe_decompress` of several independent images: h_s and g_s per image at batch 1, one batched `_decode_latents` call.
     -> one {"x_hat", "y_hat"} per image."""
+    _check_order(order, model)
     dev = next(model.parameters()).device
     params = []
     for s, sh in zip(strings, shapes):
@@ -567,7 +666,7 @@ def iframe_decompress_each(model, strings, shapes):
         z_hat = model.entropy_bottleneck.decompress(s[1], sh)
         params.append(_dense(F.to_nhwc(model.h_s(z_hat.to(dev).float()))))
     _same_shapes(params, "iframe_decompress_each")
-    y_hats = _decode_latents(model, [s[0][0] for s in strings], _cat_nhwc(params), None)
+    y_hats = _decode_latents(model, [s[0][0] for s in strings], _cat_nhwc(params), None, order=order)
     res = []
     for i in range(len(params)):
         y_hat = _slice_nhwc(y_hats, i)

@@ -364,7 +364,12 @@ STEM_EXPORT int stem_ar_decode_image(const float *w_ctx, int ld_ctx, const float
             const size_t pos = (size_t)h * W + w;
             const float *r0 = buf + ((size_t)h * Wp + w) * M, *r1 = r0 + (size_t)Wp * M, *r2 = r1 + (size_t)Wp * M;
             DecodeExtra head = none;
-            if (pix_prev) {
+            if (pix_prev && w == 0 && W <= 3) {
+                // a latent of at most three columns: the previous position (h-1, W-1) lies in the rows ABOVE this window, where the
+                // context product reads the buffer itself -- the write-back folded into that launch would race with those reads, so
+                // the pixel is committed by a launch of its own first (same float: symbol + mean)
+                hipLaunchKernelGGL(ar_finish_decode_kernel, dim3(cdiv(M, 256)), dim3(256), 0, st, gp, sym_host, pix_prev, M);
+            } else if (pix_prev) {
                 head.sym_prev = sym_host; head.mean_prev = gp + M; head.pix_prev = pix_prev; head.prev_is_left = w > 0 ? 1 : 0;
             }
             hipLaunchKernelGGL(gemv3_decode_kernel, dim3(cdiv(P, 4)), dim3(256), 0, st, w_ctx, ld_ctx, b_ctx, Seg{r0, 5 * M, 0}, Seg{r1, 5 * M, 5 * M},
@@ -810,5 +815,176 @@ STEM_EXPORT int stem_ar_encode_batch(const float *w_ctx, int ld_ctx, const float
                            buf, bufs, sym, idx, M, t, H, W, Wp, pad, G);
     }
     STEM_LAUNCH_CHECK("ar_encode_batch");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// WAVEFRONT SYMBOL ORDER (include/stem_ar_batch.h states it).  The raster-order decoders above are bound by the count of sequential
+// steps, H * W, and that count belongs to the order of the symbols in the stream, not to the model: coded step by step (t = w + 3h, rows
+// ascending inside a step, channels inside a position) the decoder needs W + 3(H-1) host round trips -- 321 instead of 8160 for a 1080p
+// frame -- and every input of the encoder's wavefront products is already decoded when step t starts.  So the decoder below runs the
+// encoder's own launches (gemv3_wave_batch_kernel with stem_ar_encode_batch's grids): no float can differ from the encoder's.
+namespace {
+
+// positions in steps 0 .. t-1: row h' holds min(max(t - 3h', 0), Wd) of them
+__host__ __device__ __forceinline__ long wave_positions_before(int t, int H, int Wd)
+{
+    long n = 0;
+    for (int h = 0; h < H && 3 * h < t; ++h) n += t - 3 * h < Wd ? t - 3 * h : Wd;
+    return n;
+}
+
+// one workgroup per raster position and image: the M symbols and the M indexes of the position move to its wavefront rank
+__global__ __launch_bounds__(64) void ar_to_wave_order_kernel(const int32_t *sym_r, const int32_t *idx_r, int32_t *sym_w, int32_t *idx_w,
+                                                              int H, int Wd, int M)
+{
+    const int pos = blockIdx.x, g = blockIdx.y;
+    const int h = pos / Wd, w = pos - h * Wd, t = w + 3 * h;
+    int h0, np;
+    wave_range_hd(t, H, Wd, h0, np);
+    const size_t img = (size_t)g * H * Wd * M;
+    const size_t src = img + (size_t)pos * M, dst = img + (size_t)(wave_positions_before(t, H, Wd) + (h - h0)) * M;
+    for (int c = threadIdx.x; c < M; c += blockDim.x) {
+        sym_w[dst + c] = sym_r[src + c];
+        idx_w[dst + c] = idx_r[src + c];
+    }
+}
+
+// step t of G images: index = build_indexes(scale) of the step's positions, in wavefront order per image, into the pinned mailbox
+__global__ void ar_index_wave_batch_kernel(const float *gp, long gps, const float *table, int T, float scale_bound, int32_t *idx, long idxs,
+                                           int M, int t, int H, int Wd, int G)
+{
+    int h0, np;
+    wave_range_hd(t, H, Wd, h0, np);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= G * np * M) return;
+    const int j = i / M, c = i - j * M;
+    const int g = j / np, p = j - g * np;
+    const float s = fmaxf(gp[(size_t)g * gps + (size_t)p * 2 * M + c], scale_bound);
+    int k = T - 1;
+    for (int q = 0; q < T - 1; ++q) k -= (s <= table[q]) ? 1 : 0;
+    idx[(size_t)g * idxs + (size_t)p * M + c] = k;
+}
+
+// step t of G images: buffer <- symbol + mean (symbols from the pinned mailbox, means from the step's wgp)
+__global__ void ar_finish_decode_wave_batch_kernel(const float *gp, long gps, const int32_t *sym, long syms, float *buf, long bufs, int M,
+                                                   int t, int H, int Wd, int Wp, int pad, int G)
+{
+    int h0, np;
+    wave_range_hd(t, H, Wd, h0, np);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= G * np * M) return;
+    const int j = i / M, c = i - j * M;
+    const int g = j / np, p = j - g * np;
+    const int h = h0 + p, w = t - 3 * h;
+    float *pix = buf + (size_t)g * bufs + ((size_t)(h + pad) * Wp + (w + pad)) * M;
+    pix[c] = (float)sym[(size_t)g * syms + (size_t)p * M + c] + gp[(size_t)g * gps + (size_t)p * 2 * M + M + c];
+}
+
+}   // namespace
+
+STEM_EXPORT int stem_ar_to_wave_order(const int32_t *sym_raster, const int32_t *idx_raster, int32_t *sym_wave, int32_t *idx_wave, int G, int H,
+                                      int W, int M, void *stream)
+{
+    STEM_CHECK_ARG(sym_raster && idx_raster && sym_wave && idx_wave, "stem_ar_to_wave_order: null pointer");
+    STEM_CHECK_ARG(G >= 1 && G <= 65535 && H > 0 && W > 0 && M > 0 && (long)H * W <= 0x7fffffffL, "stem_ar_to_wave_order: bad sizes (G=%d H=%d W=%d M=%d)",
+                   G, H, W, M);
+    STEM_CHECK_ARG(sym_raster != sym_wave && idx_raster != idx_wave && sym_wave != idx_wave, "stem_ar_to_wave_order: source and destination overlap");
+    hipLaunchKernelGGL(ar_to_wave_order_kernel, dim3(H * W, G), dim3(64), 0, (hipStream_t)stream, sym_raster, idx_raster, sym_wave, idx_wave, H, W, M);
+    STEM_LAUNCH_CHECK("ar_to_wave_order");
+    return 0;
+}
+
+STEM_EXPORT int stem_ar_decode_wave_batch(const float *w_ctx, int ld_ctx, const float *b_ctx, const float *w0, int ld0, const float *b0, int n0,
+                                          const float *w1, int ld1, const float *b1, int n1, const float *w2, int ld2, const float *b2,
+                                          float *buf, int G, int H, int W, int M, int pad, const float *tp, const float *hp,
+                                          float *wctx, float *wh1, float *wh2, float *wgp, const float *table, int T, float scale_bound, float slope,
+                                          int32_t *idx_host, int32_t *sym_host, stem_wave_symbol_decoder_fn decode, void *const *decs,
+                                          const int32_t *cdfs, int ncdf, int cdf_stride, const int32_t *sizes, const int32_t *offsets, void *stream)
+{
+    STEM_CHECK_ARG(w_ctx && b_ctx && w0 && b0 && w1 && b1 && w2 && b2 && buf && hp && wctx && wh1 && wh2 && wgp && table && idx_host && sym_host &&
+                   decode && decs, "stem_ar_decode_wave_batch: null pointer");
+    STEM_CHECK_ARG(G >= 1, "stem_ar_decode_wave_batch: at least one image per call, got %d", G);
+    static_assert(WAVE_R == 4, "the size check below is what keeps a wavefront's WAVE_R rows inside each matrix (2M, n0, n1)");
+    STEM_CHECK_ARG(H > 0 && W > 0 && M > 0 && M % 4 == 0 && n0 > 0 && n1 > 0 && n0 % 4 == 0 && n1 % 4 == 0 && ld_ctx % 4 == 0 && ld0 % 4 == 0 &&
+                   ld1 % 4 == 0 && ld2 % 4 == 0 && T >= 1 && pad == 2, "stem_ar_decode_wave_batch: bad sizes");
+    STEM_CHECK_ARG(aligned16(w_ctx) && aligned16(w0) && aligned16(w1) && aligned16(w2) && aligned16(buf) && aligned16(tp) && aligned16(hp) &&
+                   aligned16(wctx) && aligned16(wh1) && aligned16(wh2) && aligned16(wgp), "stem_ar_decode_wave_batch: weights, buf, tp, hp and scratch must be 16-byte aligned");
+    STEM_CHECK_ARG((((uintptr_t)idx_host | (uintptr_t)sym_host) & 3) == 0, "stem_ar_decode_wave_batch: the mailboxes must be 4-byte aligned");
+    const int maxp = H < (W + 2) / 3 ? H : (W + 2) / 3;
+    STEM_CHECK_ARG((long)G * maxp * M <= 0x7fffffffL, "stem_ar_decode_wave_batch: G * positions per step * M = %ld does not fit an int", (long)G * maxp * M);
+    for (int g = 0; g < G; ++g) STEM_CHECK_ARG(decs[g], "stem_ar_decode_wave_batch: no decoder handle for image %d", g);
+    hipStream_t st = (hipStream_t)stream;
+    const int P = 2 * M, Wp = W + 2 * pad;
+    const long row = (long)Wp * M;
+    const long bufs = (long)(H + 2 * pad) * row, pris = (long)H * W * P;            // image strides of buf and of tp / hp
+    const long gps = (long)maxp * P, boxs = (long)maxp * M;                          // ... of wgp and of the mailboxes
+    static const bool prof = getenv("STEM_AR_PROFILE") != nullptr;         // where a step's time goes (launch / wait / host coder)
+    double t_launch = 0, t_wait = 0, t_host = 0;
+    auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    // the segments of stem_ar_encode_batch
+    const WSegB none{nullptr, 0, 0, 0, 0, 0, 0};
+    const WSegB c0{buf, 5 * M, 0, row, M, 0, bufs}, c1{buf + row, 5 * M, 5 * M, row, M, 0, bufs}, c2{buf + 2 * row, 2 * M, 10 * M, row, M, 0, bufs};
+    const WSegB sctx{wctx, P, tp ? 2 * P : P, 0, 0, P, (long)maxp * P};
+    const WSegB stp{tp, P, 0, (long)W * P, P, 0, pris}, shp{hp, P, tp ? P : 0, (long)W * P, P, 0, pris};
+    const WSegB sh1{wh1, n0, 0, 0, 0, n0, (long)maxp * n0}, sh2{wh2, n1, 0, 0, 0, n1, (long)maxp * n1};
+    int t_prev = -1, steps = 0;               // the step whose symbols sit in the mailbox, not yet committed to buf
+    for (int t = 0; t < W + 3 * (H - 1); ++t) {
+        int h0, np;
+        wave_range_hd(t, H, W, h0, np);
+        if (np <= 0) continue;                   // W < 3: steps between two rows hold no position
+        const double ta = prof ? now() : 0;
+        const int total = G * np;
+        const int gy = total < WAVE_ROWS_B ? total : WAVE_ROWS_B;
+        if (t_prev >= 0) {
+            int hp0, npp;
+            wave_range_hd(t_prev, H, W, hp0, npp);
+            hipLaunchKernelGGL(ar_finish_decode_wave_batch_kernel, dim3(cdiv(G * npp * M, 256)), dim3(256), 0, st, wgp, gps, sym_host, boxs, buf, bufs, M,
+                               t_prev, H, W, Wp, pad, G);
+        }
+        hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(P, 4 * WAVE_R), gy), dim3(256), 0, st, w_ctx, ld_ctx, b_ctx, c0, c1, c2, wctx, P, (long)maxp * P, P,
+                           0, 0.f, t, H, W, G);
+        if (tp)
+            hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(n0, 4 * WAVE_R), gy), dim3(256), 0, st, w0, ld0, b0, stp, shp, sctx, wh1, n0, (long)maxp * n0, n0,
+                               (int)STEM_ACT_LRELU, slope, t, H, W, G);
+        else
+            hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(n0, 4 * WAVE_R), gy), dim3(256), 0, st, w0, ld0, b0, shp, sctx, none, wh1, n0, (long)maxp * n0, n0,
+                               (int)STEM_ACT_LRELU, slope, t, H, W, G);
+        hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(n1, 4 * WAVE_R), gy), dim3(256), 0, st, w1, ld1, b1, sh1, none, none, wh2, n1, (long)maxp * n1, n1,
+                           (int)STEM_ACT_LRELU, slope, t, H, W, G);
+        hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(P, 4 * WAVE_R), gy), dim3(256), 0, st, w2, ld2, b2, sh2, none, none, wgp, P, gps, P,
+                           0, 0.f, t, H, W, G);
+        hipLaunchKernelGGL(ar_index_wave_batch_kernel, dim3(cdiv(total * M, 256)), dim3(256), 0, st, wgp, gps, table, T, scale_bound, idx_host, boxs, M,
+                           t, H, W, G);
+        const double tb = prof ? now() : 0;
+        if (hipStreamSynchronize(st) != hipSuccess) {
+            stem_set_error("stem_ar_decode_wave_batch: device error at step %d: %s", t, hipGetErrorString(hipGetLastError()));
+            return -2;
+        }
+        const double tc = prof ? now() : 0;
+        for (int g = 0; g < G; ++g)
+            if (int rc = decode(decs[g], idx_host + (size_t)g * boxs, (size_t)np * M, cdfs, ncdf, cdf_stride, sizes, offsets, sym_host + (size_t)g * boxs)) {
+                stem_set_error("stem_ar_decode_wave_batch: host symbol decoder failed (%d) for image %d at step %d", rc, g, t);
+                return -3;
+            }
+        t_prev = t;
+        ++steps;
+        if (prof) {
+            const double td = now();
+            t_launch += tb - ta; t_wait += tc - tb; t_host += td - tc;
+        }
+    }
+    if (prof)
+        fprintf(stderr, "[ar decode wave batch] G=%d steps=%d positions=%d: launch %.1f us, wait %.1f us, host coder %.1f us per step\n", G, steps, H * W,
+                t_launch / steps, t_wait / steps, t_host / steps);
+    int hp0, npp;
+    wave_range_hd(t_prev, H, W, hp0, npp);
+    hipLaunchKernelGGL(ar_finish_decode_wave_batch_kernel, dim3(cdiv(G * npp * M, 256)), dim3(256), 0, st, wgp, gps, sym_host, boxs, buf, bufs, M, t_prev, H, W,
+                       Wp, pad, G);
+    STEM_LAUNCH_CHECK("ar_decode_wave_batch");
+    if (hipStreamSynchronize(st) != hipSuccess) {             // the last step read the mailbox: the caller may free it on return
+        stem_set_error("stem_ar_decode_wave_batch: device error after the last step: %s", hipGetErrorString(hipGetLastError()));
+        return -2;
+    }
     return 0;
 }

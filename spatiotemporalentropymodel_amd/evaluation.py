@@ -18,6 +18,8 @@ on the CPU and moves `y_conditioned` to the GPU for the P frames (:196-207); her
 (6 Y + U + V) / 8, the numbers video-coding papers tabulate, measured in the sample domain of the source: the decoded frame is
 quantised to planar 4:2:0 at the source's bit depth and compared with the source's integer planes (`_yuv_metrics`); `write_to=`
 appends each decoded frame to a raw .yuv file.  With yuv=False and no write_to nothing changes.
+`order="wavefront"` (not in the script): the y strings hold their symbols in wavefront order (codec.wave_order) and decode in
+W + 3(H-1) steps instead of H * W positions; reconstructions and PSNR are the raster run's, "bpp" is that of the frame's own strings.
 The script's last line reads out_dec["entropy_params"], a key the reference model's decompress() does not return
 (spatiotemporalpriors.py:1012 -> KeyError at :152 as shipped); the key is returned holding None.
 
@@ -152,6 +154,13 @@ def _sync(t):
         torch.cuda.synchronize(t.device)
 
 
+def _order_kw(order):
+    """what compress / decompress are passed on top of the script's arguments: nothing for the reference's order"""
+    from . import codec
+    codec._check_order(order)
+    return {} if order == "raster" else {"order": order}
+
+
 def _bpp_terms(out_enc, out_forward, num_pixels):
     bpp = sum(len(s[0]) for s in out_enc["strings"]) * 8.0 / num_pixels
     est = {k: float(torch.log(v.float()).sum() / (-math.log(2) * num_pixels)) for k, v in out_forward["likelihoods"].items()}
@@ -159,20 +168,22 @@ def _bpp_terms(out_enc, out_forward, num_pixels):
 
 
 @torch.no_grad()
-def inference_iframe(model, x, with_msssim=True, yuv=False, write_to=None):
+def inference_iframe(model, x, with_msssim=True, yuv=False, write_to=None, order="raster"):
     """x: one image [3,h,w] in [0,1].  Pad to multiples of 64 (centred), compress + forward (the rate estimate), decompress, crop.
-    `y_conditioned` is the DECODED latent of the padded image: what the next P frame is conditioned on.  yuv, write_to: `_yuv_metrics`."""
+    `y_conditioned` is the DECODED latent of the padded image: what the next P frame is conditioned on.  yuv, write_to: `_yuv_metrics`;
+    order: the symbol order of the y string ("raster" | "wavefront")."""
+    okw = _order_kw(order)
     frame, x = x, x.unsqueeze(0)
     h, w = x.size(2), x.size(3)
     x_padded = bitstream.pad(x, 64)
     _sync(x)
     start = time.time()
-    out_enc = model.compress(x_padded)
+    out_enc = model.compress(x_padded, **okw)
     out_forward = model(x_padded)
     _sync(x)
     enc_time = time.time() - start
     start = time.time()
-    out_dec = model.decompress(out_enc["strings"], out_enc["shape"])
+    out_dec = model.decompress(out_enc["strings"], out_enc["shape"], **okw)
     _sync(x)
     dec_time = time.time() - start
     x_hat = bitstream.crop(out_dec["x_hat"], (h, w))
@@ -188,9 +199,10 @@ def inference_iframe(model, x, with_msssim=True, yuv=False, write_to=None):
 
 
 @torch.no_grad()
-def inference_pframe(imodel, stem, x, y_conditioned, with_msssim=True, yuv=False, write_to=None):
+def inference_pframe(imodel, stem, x, y_conditioned, with_msssim=True, yuv=False, write_to=None, order="raster"):
     """x: one frame [3,h,w]; y_conditioned: the previous frame's decoded latents.  encode = getY + forward + compress, decode =
-    decompress + getX, timed as the script times them.  yuv, write_to: `_yuv_metrics`."""
+    decompress + getX, timed as the script times them.  yuv, write_to: `_yuv_metrics`; order: as in `inference_iframe`."""
+    okw = _order_kw(order)
     frame, x = x, x.unsqueeze(0)
     h, w = x.size(2), x.size(3)
     x_padded = bitstream.pad(x, 64)
@@ -198,11 +210,11 @@ def inference_pframe(imodel, stem, x, y_conditioned, with_msssim=True, yuv=False
     start = time.time()
     y_cur, _ = imodel.getY(x_padded)
     out_forward = stem(y_cur, y_conditioned)
-    out_enc = stem.compress(y_cur, y_conditioned)
+    out_enc = stem.compress(y_cur, y_conditioned, **okw)
     _sync(x)
     enc_time = time.time() - start
     start = time.time()
-    out_dec = stem.decompress(out_enc["strings"], out_enc["shape"], y_conditioned)
+    out_dec = stem.decompress(out_enc["strings"], out_enc["shape"], y_conditioned, **okw)
     y_hat = out_dec["y_hat"] if isinstance(out_dec, dict) else out_dec
     x_hat = imodel.getX(y_hat)
     _sync(x)
@@ -220,7 +232,7 @@ def inference_pframe(imodel, stem, x, y_conditioned, with_msssim=True, yuv=False
 
 
 @torch.no_grad()
-def eval_gop(imodel, stem, frames, gop=12, all_intra=False, with_msssim=True, yuv=False, write_to=None):
+def eval_gop(imodel, stem, frames, gop=12, all_intra=False, with_msssim=True, yuv=False, write_to=None, order="raster"):
     """frames: iterable of [3,h,w] images of ONE sequence, in display order (the script's f001.png, f002.png, ...).  Frame k
     (1-based) with k % gop == 1 is an I frame, every other one a P frame conditioned on the previous frame's decoded latents
     (stem/evalSTEM.py:186-209; gop = 12 for UVG, 10 for the HEVC classes).  Returns the per-frame dictionaries of the two
@@ -229,8 +241,10 @@ def eval_gop(imodel, stem, frames, gop=12, all_intra=False, with_msssim=True, yu
     and "psnr" of every frame from the HIP kernel instead (`_metrics`).  yuv=True adds "psnr_y", "psnr_u", "psnr_v", "psnr_yuv" to every
     frame (against the planes a data.YUVSequence frame carries, else against the frame quantised at 8 bits) and their averages
     "psnr_y_ave" ... "psnr_yuv_ave" to the result; write_to (a path or a binary file object) gets every decoded frame appended as raw
-    planar 4:2:0 at the source's bit depth."""
+    planar 4:2:0 at the source's bit depth.  order="wavefront": every frame's y string in wavefront symbol order (codec.wave_order), the
+    same reconstructions."""
     extra = {} if not yuv and write_to is None else {"yuv": yuv, "write_to": write_to}      # nothing new is passed through by default
+    extra.update(_order_kw(order))
     per_frame, y_cond = [], None
     for index, x in enumerate(frames, start=1):
         if all_intra or index % gop == 1 or y_cond is None:
@@ -290,7 +304,7 @@ class _InOrder:
 
 
 @torch.no_grad()
-def eval_sequence(imodel, stem, frames, gop=12, concurrent_gops=8, all_intra=False, with_msssim=True, yuv=False, write_to=None):
+def eval_sequence(imodel, stem, frames, gop=12, concurrent_gops=8, all_intra=False, with_msssim=True, yuv=False, write_to=None, order="raster"):
     """`eval_gop` with the sequence's GOPs coded side by side (`gop_schedule`): every GOP is an independent chain, and the raster-order
     coding loops -- launch- and latency-bound for one image -- advance up to `concurrent_gops` chains together (codec.iframe_*_each,
     codec.stem_*_each: one batched encoder queue, the concurrent / lockstep decoders).  Every transform still runs per chain at batch 1,
@@ -298,8 +312,9 @@ def eval_sequence(imodel, stem, frames, gop=12, concurrent_gops=8, all_intra=Fal
     frames: a sequence (indexable, with a length) or an iterable of [3,h,w] images of one size, in display order.  Returns what `eval_gop`
     returns: "frames" in display order, each with `eval_gop`'s keys and values, and the same averages.  Only the timing differs:
     "encoding_time" / "decoding_time" are the wall time of the frame's step divided by the number of chains in it, which the new key
-    "concurrent" holds.  write_to receives the frames in display order.  concurrent_gops=1: one chain per step."""
+    "concurrent" holds.  write_to receives the frames in display order.  concurrent_gops=1: one chain per step.  order: as in `eval_gop`."""
     from . import codec
+    okw = _order_kw(order)
     if not (hasattr(frames, "__getitem__") and hasattr(frames, "__len__")):
         frames = list(frames)
     writer = _InOrder(write_to) if write_to is not None else None
@@ -315,7 +330,7 @@ def eval_sequence(imodel, stem, frames, gop=12, concurrent_gops=8, all_intra=Fal
         _sync(xs[0])
         start = time.time()
         if ipos:
-            for k, e in zip(ipos, codec.iframe_compress_each(imodel, [padded[k] for k in ipos])):
+            for k, e in zip(ipos, codec.iframe_compress_each(imodel, [padded[k] for k in ipos], **okw)):
                 enc[k] = e
                 fwd[k] = imodel(padded[k])
         if ppos:
@@ -323,16 +338,16 @@ def eval_sequence(imodel, stem, frames, gop=12, concurrent_gops=8, all_intra=Fal
             y_curs = [imodel.getY(padded[k])[0] for k in ppos]
             for k, y_cur, c in zip(ppos, y_curs, conds):
                 fwd[k] = stem(y_cur, c)
-            for k, e in zip(ppos, codec.stem_compress_each(stem, y_curs, conds)):
+            for k, e in zip(ppos, codec.stem_compress_each(stem, y_curs, conds, **okw)):
                 enc[k] = e
         _sync(xs[0])
         enc_time = (time.time() - start) / len(step)
         start = time.time()
         if ipos:
-            for k, d in zip(ipos, codec.iframe_decompress_each(imodel, [enc[k]["strings"] for k in ipos], [enc[k]["shape"] for k in ipos])):
+            for k, d in zip(ipos, codec.iframe_decompress_each(imodel, [enc[k]["strings"] for k in ipos], [enc[k]["shape"] for k in ipos], **okw)):
                 dec[k], y_hat[k], x_hat[k] = d, d["y_hat"], d["x_hat"]
         if ppos:
-            outs = codec.stem_decompress_each(stem, [enc[k]["strings"] for k in ppos], [enc[k]["shape"] for k in ppos], conds)
+            outs = codec.stem_decompress_each(stem, [enc[k]["strings"] for k in ppos], [enc[k]["shape"] for k in ppos], conds, **okw)
             for k, y in zip(ppos, outs):
                 dec[k] = {"y_hat": y} if stem.DECOMPRESS_RETURNS_DICT else y
                 y_hat[k] = y

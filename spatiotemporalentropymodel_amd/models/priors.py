@@ -111,17 +111,17 @@ class JointAutoregressiveHierarchicalPriors(CompressionModel):
         return {"y": y, "y_hat": y_hat, "x_hat": x_hat, "likelihoods": {"y": y_likelihoods, "z": z_likelihoods},
                 "entropy_params": {"scales_hat": scales_hat, "means_hat": means_hat}}
 
-    def compress(self, x):
-        """priors.py:544-584 -> {"strings": [y_strings, z_strings], "shape": z.shape[-2:]}"""
+    def compress(self, x, order="raster"):
+        """priors.py:544-584 -> {"strings": [y_strings, z_strings], "shape": z.shape[-2:]}; order="wavefront" (codec.wave_order) adds "order" to it"""
         from ..codec import iframe_compress
         with torch.no_grad():
-            return iframe_compress(self, x)
+            return iframe_compress(self, x, order=order)
 
-    def decompress(self, strings, shape):
+    def decompress(self, strings, shape, order="raster"):
         """priors.py:633-674 -> {"x_hat", "y_hat"}"""
         from ..codec import iframe_decompress
         with torch.no_grad():
-            return iframe_decompress(self, strings, shape)
+            return iframe_decompress(self, strings, shape, order=order)
 
     def update(self, scale_table=None, force=False):
         """the Gaussian tables next to the bottleneck's (priors.py's MeanScaleHyperprior.update, which mbt2018 inherits)"""

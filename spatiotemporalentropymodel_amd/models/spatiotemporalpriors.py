@@ -96,14 +96,15 @@ class _StemBase(CompressionModel):
         return {"y_hat": y_hat, "likelihoods": {"y": lik_y, "z": lik_z}}
 
     # ---- bitstream side ----------------------------------------------------------------------
-    def compress(self, y_cur, y_conditioned):
+    def compress(self, y_cur, y_conditioned, order="raster"):
+        """order: "raster" (the reference's) or "wavefront" (codec.wave_order; the result then carries "order")"""
         from ..codec import stem_compress
-        return stem_compress(self, y_cur, y_conditioned)
+        return stem_compress(self, y_cur, y_conditioned, order=order)
 
-    def decompress(self, strings, shape, y_conditioned):
+    def decompress(self, strings, shape, y_conditioned, order="raster"):
         from ..codec import stem_decompress
         assert isinstance(strings, list) and len(strings) == 2
-        y_hat = stem_decompress(self, strings, shape, y_conditioned)
+        y_hat = stem_decompress(self, strings, shape, y_conditioned, order=order)
         return {"y_hat": y_hat} if self.DECOMPRESS_RETURNS_DICT else y_hat
 
     def load_state_dict(self, state_dict, strict=True):
