@@ -5,6 +5,21 @@
  * Same conventions as stem_hip.h (device pointers owned by the caller, asynchronous on `stream`, 0 on success, stem_last_error()
  * on failure).  The entry points here are not launch-tape entries (csrc/tape_entries.inc lists stem_hip.h's): the coding loops
  * are queued by one call each and are not part of a recorded training step.
+ *
+ * ---- the canonical product ---------------------------------------------------------------------------------------------------
+ * Every entropy parameter of the coding loops is specified to the bit: a mean that differs by an ulp moves y_hat and with it every
+ * later context, a scale on the other side of a table entry corrupts the stream.  Every product of these loops -- stem_gemv3,
+ * stem_gemv3_decode, stem_gemv3_wave, the batched products of stem_ar_encode_batch / stem_ar_decode_batch /
+ * stem_ar_decode_wave_batch and the persistent decoder, whose partial sums continue once the symbols arrive -- computes, per output
+ * row n, in float32 without fused multiply-add (every product and every sum rounded):
+ *   - 64 lane accumulators, 0.0f each;
+ *   - the segments in argument order; within a segment lane l takes the columns k = 4l, 4l + 256, ... while k < len, and each step
+ *     adds ((x[k] W[n][woff+k] + x[k+1] W[n][woff+k+1]) + x[k+2] W[n][woff+k+2]) + x[k+3] W[n][woff+k+3] to the lane's accumulator;
+ *   - the xor butterfly acc += acc[lane ^ off] for off = 32, 16, 8, 4, 2, 1; lane 0's value is the sum;
+ *   - y[n] = sum + bias[n] (+ 0.0f without a bias), then v > 0 ? v : v * slope for STEM_ACT_LRELU.
+ * The scale-to-index search is T - 1 - #{t < T - 1 : max(scale, scale_bound) <= table[t]}, the quantisation q = rintf(pix - mean)
+ * (ties to even), pix <- q + mean, symbol = (int32_t)q; the decoder's pix <- (float)symbol + mean is the same float.
+ * tests/ar_ref.py states all of this in numpy and tests/test_hip_ar_ops.py holds every kernel form to it bit for bit.
  */
 #ifndef STEM_AR_BATCH_H
 #define STEM_AR_BATCH_H

@@ -559,7 +559,8 @@ int stem_bias_grad(const float *dy, int lddy, long npix, int K, float *scratch, 
 
 /* Wavefront-parallel encoder: all latent positions with the same t = w + 3h are independent under the 5x5
  * type-A mask, so a H x W frame is coded in W + 3(H-1) batched steps instead of H*W sequential ones.  Input
- * segment of position p at (h, w): x + sh*h + sw*w + sp*p (element offsets); output y[p*ldy + n].            */
+ * segment of position p at (h, w): x + sh*h + sw*w + sp*p (element offsets); output y[p*ldy + n].  As for
+ * stem_gemv3: W and every segment base 16-byte aligned, ldw, lengths, offsets and strides multiples of 4 floats. */
 typedef struct {
     const float *x;
     int len, woff;

@@ -18,7 +18,9 @@
 // Encoder and decoder must produce the SAME floats for every entropy parameter (a mean that differs in the last bit
 // shifts y_hat, which feeds later contexts; a scale on the other side of a table entry desynchronises the coder), and the
 // encoder's wavefront kernels, the one-image decoder and the lockstep decoder are different kernels.  Their dot products
-// are therefore written once (dot4) and compiled without FMA contraction: products rounded, then added left to right.
+// are therefore all the CANONICAL PRODUCT that include/stem_ar_batch.h states (lane partials over columns 4 lane + 256 j, segment after
+// segment, each 16-byte step summed left to right, xor-shuffle reduction, bias, activation), compiled without FMA contraction: products
+// rounded, then added.  tests/ar_ref.py emulates that order in float32; tests/test_hip_ar_ops.py holds every form below to it bit for bit.
 #pragma clang fp contract(off)
 
 namespace {
@@ -313,13 +315,16 @@ __global__ void ar_finish_encode_wave_kernel(const float *gp, const float *table
 STEM_EXPORT int stem_gemv3_wave(const float *W, int ldw, const float *bias, const stem_wave_seg *segs, float *y, int ldy, int N,
                                 int act, float slope, int t, int H, int Wd, void *stream)
 {
-    STEM_CHECK_ARG(W && segs && y && N > 0 && ldw % 4 == 0, "stem_gemv3_wave: bad arguments");
+    // the kernel loads 16 bytes at a time from W + n * ldw + woff + k and from x + sh * h + sw * w + sp * p + k: what stem_gemv3 asks of
+    // its weight and segments, plus strides that keep every position's segment aligned
+    STEM_CHECK_ARG(W && segs && y && N > 0 && H > 0 && Wd > 0 && ldw % 4 == 0 && (((uintptr_t)W & 15) == 0), "stem_gemv3_wave: bad arguments");
     WSeg s[3];
     for (int i = 0; i < 3; ++i) {
         s[i].x = segs[i].x; s[i].len = segs[i].len; s[i].woff = segs[i].woff;
         s[i].sh = segs[i].sh; s[i].sw = segs[i].sw; s[i].sp = segs[i].sp;
-        STEM_CHECK_ARG(s[i].len == 0 || (s[i].x && s[i].len % 4 == 0 && s[i].woff % 4 == 0 && s[i].sh % 4 == 0 && s[i].sw % 4 == 0 && s[i].sp % 4 == 0),
-                       "stem_gemv3_wave: segment %d is not 16-byte granular", i);
+        STEM_CHECK_ARG(s[i].len == 0 || (s[i].x && (((uintptr_t)s[i].x & 15) == 0) && s[i].len % 4 == 0 && s[i].woff % 4 == 0 && s[i].sh % 4 == 0 &&
+                                         s[i].sw % 4 == 0 && s[i].sp % 4 == 0),
+                       "stem_gemv3_wave: segment %d is not a 16-byte aligned multiple of 4 floats with strides of multiples of 4 floats", i);
     }
     const int maxp = H < (Wd + 2) / 3 ? H : (Wd + 2) / 3;
     hipLaunchKernelGGL(gemv3_wave_kernel, dim3(cdiv(N, 4), maxp < WAVE_ROWS ? maxp : WAVE_ROWS), dim3(256), 0, (hipStream_t)stream, W, ldw, bias,
@@ -473,8 +478,8 @@ struct DecodeExtraB {
 // One wavefront per output row (the products are latency-bound: what counts is how many independent loads are in flight,
 // row-blocked variants with fewer wavefronts were 2x slower).  G is a template parameter and each segment is walked in up to
 // MAXS fully unrolled 256-column steps, so that the weight loads of a segment, then each image's x loads, are issued back to
-// back instead of one exposed latency per step.  Every (row, image) sum accumulates its steps in ascending k: the order --
-// and therefore the bits -- of gemv3_decode_kernel.
+// back instead of one exposed latency per step.  Every (row, image) sum accumulates its steps in ascending k: the canonical
+// product of include/stem_ar_batch.h -- the order, and therefore the bits, of gemv3_decode_kernel.
 constexpr int MAXS = 4;          // segments of up to 1024 floats (5 M = 960 for M = 192, n0 = 768)
 template <int G>
 __global__ __launch_bounds__(256) void gemv3b_decode_kernel(const float *W, int ldw, const float *bias, SegB s0, SegB s1, SegB s2,
@@ -644,8 +649,8 @@ STEM_EXPORT int stem_ar_decode_batch(const float *w_ctx, int ld_ctx, const float
 // step t.  The image index is folded into the position loop (j = g * np + p), every wavefront still spreads each dot product over its 64 lanes, and
 // a wavefront takes WAVE_R rows and up to WAVE_U positions at once: a register tile of WAVE_R * WAVE_U dot products fed by
 // WAVE_R + WAVE_U loads per k step.  Every (image, position, row) sum is accumulated exactly as
-// gemv3_wave_kernel does it -- k = lane * 4, += 256, segment after segment, xor-shuffle reduction -- so each image's floats,
-// symbols and indexes are those of stem_ar_encode_image.
+// gemv3_wave_kernel does it -- k = lane * 4, += 256, segment after segment, xor-shuffle reduction: the canonical product of
+// include/stem_ar_batch.h -- so each image's floats, symbols and indexes are those of stem_ar_encode_image.
 namespace {
 
 struct WSegB {

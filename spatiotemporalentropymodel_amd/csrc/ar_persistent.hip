@@ -17,7 +17,8 @@
 //     Every wait is bounded; a timeout raises an abort word that ends the kernel (the caller then decodes with the loop).
 //
 // Arithmetic: every output row is one wavefront's dot product in the order of gemv3_decode_kernel (segments in order, columns
-// lane * 4 + 256 t ascending, xor-shuffle reduction, bias, leaky ReLU), compiled without FMA contraction like ar.hip -- the
+// lane * 4 + 256 t ascending, xor-shuffle reduction, bias, leaky ReLU: the canonical product stated in
+// include/stem_ar_batch.h), compiled without FMA contraction like ar.hip -- the
 // entropy parameters, hence symbols and bytes, are those of the per-position loop and of the encoder.
 #include <chrono>
 #include <mutex>
@@ -70,8 +71,8 @@ __device__ inline void st_agent(float *p, float v) { *reinterpret_cast<volatile 
 // xor-shuffle reduction): the lane partials after the leading segments are a well-defined intermediate state.  So
 //   * while the host decodes the symbols of position p, every wavefront computes the lane partials of position p + 1 over the
 //     segments that are already known (rows above: complete since the previous image row; tp, hp: inputs);
-//   * once the symbols are in, it CONTINUES those sums with the new segment -- same additions in the same order, hence the same
-//     floats as gemv3_decode_kernel (ar.hip) and as the encoder, bit for bit;
+//   * once the symbols are in, it CONTINUES those sums with the new segment -- same additions in the same order (the canonical
+//     product of include/stem_ar_batch.h), hence the same floats as gemv3_decode_kernel (ar.hip) and as the encoder, bit for bit;
 //   * each global wavefront g owns output rows g, g + 256, ... of every product for the whole image and keeps the weights it needs
 //     on the dependent path in REGISTERS (148 VGPRs at M = 192: the last segment of its ctx rows, its EPM.0 / EPM.2 / EPM.4 rows)
 //     and the weights of the rows-above part of its ctx rows in LDS (16 KB per wavefront): nothing but the 384..768-float
