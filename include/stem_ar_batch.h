@@ -82,6 +82,26 @@ int stem_ar_decode_wave_batch(const float *w_ctx, int ld_ctx, const float *b_ctx
                               int32_t *idx_host, int32_t *sym_host, stem_wave_symbol_decoder_fn decode, void *const *decs,
                               const int32_t *cdfs, int ncdf, int cdf_stride, const int32_t *sizes, const int32_t *offsets, void *stream);
 
+/* ---- one-shot coding calls ----------------------------------------------------------------------------------------------------
+ * A model without a spatial prior codes a whole frame's symbols in one host call.  These two launches are the device side of that
+ * call: y, means, scales and y_hat are NHWC with a pixel pitch (ld >= C; the channel slices of an entropy-parameter output go in
+ * as they are), sym and idx are dense [B][C][H][W], the order in which the reference flattens and stem_rans_encode /
+ * stem_rans_decode read.  The transpose goes through an LDS tile of 64 pixels x 64 channels.  No atomics, no workspace. */
+
+/* sym = (int32_t)rintf(y - m) with m = means[b,h,w,c], else chan_means[c] (a bottleneck's medians), else sym = (int32_t)rintf(y):
+ * the subtraction and the rounding (ties to even) are two fp32 operations, never contracted.  idx = the scale-to-index search
+ * T - 1 - #{t < T - 1 : max(scales[b,h,w,c], scale_bound) <= table[t]}; with scales == NULL idx = c (the bottleneck's indexes; table
+ * and T are not read).  y == NULL (then sym == NULL, and no means) writes only idx: the decoder's call.  idx == NULL (then no scales)
+ * writes only sym.  At most one of means / chan_means.  Null or contradictory arguments, a pitch below C and non-positive sizes
+ * return non-zero before any launch. */
+int stem_symbols_pack(const float *y, int ldy, const float *means, int ldm, const float *chan_means,
+                      const float *scales, int lds, const float *table, int T, float scale_bound,
+                      int32_t *sym, int32_t *idx, int B, int H, int W, int C, void *stream);
+
+/* y_hat[b,h,w,c] = (float)sym[b][c][h][w] + m, one rounding (m as above; without means the converted symbol itself). */
+int stem_symbols_unpack(const int32_t *sym, const float *means, int ldm, const float *chan_means,
+                        float *y_hat, int ldo, int B, int H, int W, int C, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,14 +100,14 @@ def _hyper(model, y_cur, y_cond, strings_z=None, shape=None):
 
 
 def _one_shot(model, hp, tp):
-    """no spatial prior: EPM on the concatenated priors (dense NHWC) -> gp = scales | means, returned as the Gaussians' (indexes, means)"""
+    """no spatial prior: EPM on the concatenated priors (dense NHWC) -> gp = scales | means, returned as the two channel slices (scales, means)"""
     priors = [p for p in (tp, hp) if p is not None]
     B, P, H, W = hp.shape
     epm_in = F.empty_nhwc(B, P * len(priors), H, W, hp.device)
     for i, p in enumerate(priors):
         F.copy_channels(p, epm_in[:, i * P:(i + 1) * P])
     gp = _chain(model.engine().EPM, epm_in)
-    return model.gaussian_conditional.build_indexes(gp[:, :P // 2]), gp[:, P // 2:]
+    return gp[:, :P // 2], gp[:, P // 2:]
 
 
 class _ARContext:
@@ -261,8 +261,8 @@ def stem_compress(model, y_cur, y_cond, order="raster"):
     yc, yd = F.to_nhwc(y_cur.detach()), F.to_nhwc(y_cond.detach())
     target = F.sub(_dense(yc), _dense(yd)) if model.RESIDUAL else _dense(yc)
     if not model.HAS_SPM:
-        indexes, means = _one_shot(model, hp, tp)
-        y_strings = model.gaussian_conditional.compress(target, indexes, means=means)
+        scales, means = _one_shot(model, hp, tp)
+        y_strings = model.gaussian_conditional.compress(target, None, means=means, scales=scales)
     else:
         y_strings = _encode_latents(model, target, hp, tp, order)
     return _result(y_strings, z_strings, zshape, order)
@@ -327,8 +327,8 @@ def stem_decompress(model, strings, shape, y_cond, order="raster"):
     _, _, hp, tp = _hyper(model, None, y_cond, strings_z=strings[1], shape=shape)
     yd = F.to_nhwc(y_cond.detach())
     if not model.HAS_SPM:
-        indexes, means = _one_shot(model, hp, tp)
-        return model.gaussian_conditional.decompress(strings[0], indexes, means=means)
+        scales, means = _one_shot(model, hp, tp)
+        return model.gaussian_conditional.decompress(strings[0], None, means=means, scales=scales)
     out = _decode_latents(model, strings[0], hp, tp, order=order)
     if model.RESIDUAL:
         out = F.add(out, _dense(yd))

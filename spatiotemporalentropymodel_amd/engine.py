@@ -587,14 +587,16 @@ class StemEngine:
             self._checked = False
 
     @staticmethod
-    def _chain_forward(layers, a, out=None):
+    def _chain_forward(layers, a, out=None, planes=True):
         """a chain of convolutions with leaky ReLUs between them over the _Act `a`; the last one writes `out` (a channel slice of
-        the EPM input) if given.  -> [a, output of layer 0, ...]: an epilogue writes planes when the next layer reads them"""
+        the EPM input) if given.  -> [a, output of layer 0, ...]: an epilogue writes planes when the next layer reads them.
+        planes=False: no epilogue writes planes, every layer splits its fp32 input itself, which is codec._chain's arithmetic
+        (an epilogue scales its planes by a bound of |output|, a split by the measured maximum: the low planes differ)"""
         acts = [a]
         for i, l in enumerate(layers):
             nxt = layers[i + 1] if i + 1 < len(layers) else None
             acts.append(l.forward(acts[-1], F.ACT_LRELU if nxt else F.ACT_NONE, out=None if nxt else out,
-                                  planes=nxt is not None and nxt.faces[0].kind != "f32"))
+                                  planes=planes and nxt is not None and nxt.faces[0].kind != "f32"))
         return acts
 
     @staticmethod
@@ -624,6 +626,9 @@ class StemEngine:
         assert not fused or training, "the fused glue is the TRAINING forward"
         k = {}
         target = t_hat = y_hat = None
+        # the eval forward of a model WITHOUT a spatial prior returns y_hat = round(y - means) + means, the very tensor its decoder
+        # rebuilds (codec.stem_decompress): its chains run codec._chain's arithmetic so that the two means are the same floats
+        ep = training or self.has_spm
         rec = {}    # scale records left by the producers of fp32 tensors that are split for the fp16 kernels below
         if fused:
             # one kernel: he_in = [y_cur | y_cond], target, t_hat = target + noise, y_hat = t_hat (+ y_cond); it also records
@@ -671,10 +676,10 @@ class StemEngine:
         # the TPM chain is enqueued ahead of the hyper branch's ~14 launches: it is the forward's critical path
         tp0 = tp2 = None
         if self.has_tpm:
-            _, acts["tp0"], acts["tp2"], _ = self._chain_forward(self.TPM, acts["yd"], out=epm_in[:, o_tp:o_tp + P])
+            _, acts["tp0"], acts["tp2"], _ = self._chain_forward(self.TPM, acts["yd"], out=epm_in[:, o_tp:o_tp + P], planes=ep)
             tp0, tp2 = acts["tp0"].x, acts["tp2"].x
         with F.on_stream(bs):
-            _, acts["he0"], acts["he2"], z = self._chain_forward(self.HE, acts["he_in"])
+            _, acts["he0"], acts["he2"], z = self._chain_forward(self.HE, acts["he_in"], planes=ep)
             z = z.x
             pack = F.eb_pack(eb._tensors14())
             if fused:
@@ -688,7 +693,7 @@ class StemEngine:
             else:
                 z_hat, lik_z = F.eb_forward(z, pack, medians=eb._medians_vec())
             # hyper decoder; its last conv writes the `hp` slice of the EPM input
-            acts["z_hat"], acts["hd0"], acts["hd2"], _ = self._chain_forward(self.HD, _Act(z_hat, rec=rec.get("z_hat")), out=epm_in[:, o_hp:o_hp + P])
+            acts["z_hat"], acts["hd0"], acts["hd2"], _ = self._chain_forward(self.HD, _Act(z_hat, rec=rec.get("z_hat")), out=epm_in[:, o_hp:o_hp + P], planes=ep)
         if not fused:
             target = F.sub(yc, yd) if self.residual else (yc if F.nhwc_ld(yc) == Cin else F.copy_channels(yc, F.empty_nhwc(B, Cin, H, W, dev)))
         if self.has_spm:
@@ -703,7 +708,7 @@ class StemEngine:
             self.CTX.forward(acts["t_hat"], out=epm_in[:, o_ctx:o_ctx + P])
         if bs is not None:
             F.stream_wait(main, bs)
-        acts["epm_in"], acts["e0"], acts["e2"], gp = self._chain_forward(self.EPM, _Act(epm_in))
+        acts["epm_in"], acts["e0"], acts["e2"], gp = self._chain_forward(self.EPM, _Act(epm_in), planes=ep)
         gp = gp.x                                                    # [B, 2*Cin, H, W] = scales | means
         scales, means = gp[:, :Cin], gp[:, Cin:]
         if fused:

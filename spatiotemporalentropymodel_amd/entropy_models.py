@@ -342,18 +342,49 @@ class EntropyModel(nn.Module):
             self._tables = (key, _Tables(self._quantized_cdf, self._cdf_length, self._offset))
         return self._tables[1]
 
-    def compress(self, inputs, indexes, means=None):
-        """symbols = round(inputs - means) coded with the host rANS, one string per batch element (:201-233)."""
-        if len(inputs.size()) != 4:
-            raise ValueError("Invalid `inputs` size. Expected a 4-D tensor.")
-        if inputs.size() != indexes.size():
-            raise ValueError("`inputs` and `indexes` should have the same size.")
-        symbols = self.quantize(inputs, "symbols", means)
+    def _scale_index_args(self):
+        """(scale table, scale bound) of the in-kernel scale-to-index search; only a model with a scale table has them"""
+        raise ValueError(f"{type(self).__name__} has no scale table: `scales` cannot be turned into indexes")
+
+    @staticmethod
+    def _elementwise_means(means, shape):
+        """means of `shape` or one value per (batch, channel) -> NHWC-memory tensor of `shape` (None stays None)"""
+        if means is None:
+            return None
+        means = means.detach()
+        if tuple(means.shape) != tuple(shape):
+            means = means.expand(shape).contiguous()
+        return F.to_nhwc(means)
+
+    def _compress(self, inputs, indexes=None, means=None, chan_means=None, scales=None):
+        """One stem_symbols_pack launch -> symbols (and, with indexes=None, the indexes: of `scales`, else the channel numbers) in
+        the reference's flattening order, one copy to the host, the host coder once per batch element."""
+        x = F.to_nhwc(inputs.detach())
+        m = self._elementwise_means(means, inputs.shape)
         t = self.host_tables()
-        sym = symbols.cpu().contiguous().numpy()          # logical NCHW order, as the reference flattens
-        idx = indexes.int().cpu().contiguous().numpy()
+        if indexes is None:
+            table, bound = self._scale_index_args() if scales is not None else (None, 0.0)
+            sc = F.to_nhwc(scales.detach()) if scales is not None else None
+            sym, idx = F.symbols_pack(x, m, chan_means, sc, table, bound).cpu().numpy()
+        else:
+            sym = F.symbols_pack(x, m, chan_means, want_indexes=False)[0].cpu().numpy()
+            idx = indexes.int().cpu().contiguous().numpy()
         enc = RansEncoder()
         return [enc.encode_with_indexes(sym[i], idx[i], t) for i in range(sym.shape[0])]
+
+    def compress(self, inputs, indexes, means=None, scales=None):
+        """symbols = round(inputs - means) coded with the host rANS, one string per batch element (:201-233).  indexes=None with
+        `scales` (not in the reference): the indexes build_indexes(scales) would give are computed by the launch that quantises."""
+        if len(inputs.size()) != 4:
+            raise ValueError("Invalid `inputs` size. Expected a 4-D tensor.")
+        if indexes is None:
+            if scales is None or scales.size() != inputs.size():
+                raise ValueError("`inputs` and `scales` should have the same size.")
+        elif scales is not None:
+            raise ValueError("`indexes` and `scales` are alternatives.")
+        elif inputs.size() != indexes.size():
+            raise ValueError("`inputs` and `indexes` should have the same size.")
+        return self._compress(inputs, indexes, means=means, scales=scales)
 
     @staticmethod
     def _check_decompress_args(strings, indexes, means):
@@ -374,15 +405,37 @@ class EntropyModel(nn.Module):
         if tuple(means.shape) != tuple(indexes.shape) and not per_channel:
             raise ValueError("Invalid means parameters")
 
-    def decompress(self, strings, indexes, means=None):
-        """one string per batch element -> dequantised values (:235-279); argument errors are ValueError as upstream"""
-        self._check_decompress_args(strings, indexes, means)
+    def _decompress(self, strings, shape, indexes=None, means=None, chan_means=None, scales=None, device=None):
+        """indexes (given, or by stem_symbols_pack without y: of `scales`, else the channel numbers) -> the host decoder once per
+        batch element -> one copy up -> stem_symbols_unpack: NHWC-memory values of `shape`"""
         t = self.host_tables()
-        idx = indexes.int().cpu().contiguous().numpy()
+        shape = tuple(int(s) for s in shape)
+        if indexes is None and scales is None:
+            # the channel numbers depend on nothing the device holds: stated on the host, no launch and no copy
+            idx = np.broadcast_to(np.arange(shape[1], dtype=np.int32)[None, :, None, None], shape)
+        elif indexes is None:
+            table, bound = self._scale_index_args()
+            idx = F.symbols_pack(None, scales=F.to_nhwc(scales.detach()), table=table, scale_bound=bound)[1].cpu().numpy()
+        else:
+            idx = indexes.int().cpu().contiguous().numpy()
         dec = RansDecoder()
         vals = np.stack([dec.decode_with_indexes_np(s, idx[i], t).reshape(idx[i].shape) for i, s in enumerate(strings)])
-        outputs = torch.from_numpy(vals).to(indexes.device)
-        return self.dequantize(outputs, means)
+        sym = torch.from_numpy(vals).to(device)
+        return F.symbols_unpack(sym, self._elementwise_means(means, shape), chan_means)
+
+    def decompress(self, strings, indexes, means=None, scales=None):
+        """one string per batch element -> dequantised values (:235-279); argument errors are ValueError as upstream.
+        indexes=None with `scales`: as in compress.  The result has NHWC memory."""
+        if indexes is None:
+            if scales is None:
+                raise ValueError("Invalid `indexes` parameter: give indexes or scales.")
+            like = scales
+        elif scales is not None:
+            raise ValueError("`indexes` and `scales` are alternatives.")
+        else:
+            like = indexes
+        self._check_decompress_args(strings, like, means)
+        return self._decompress(strings, like.shape, indexes, means=means, scales=scales, device=like.device)
 
 
 class EntropyBottleneck(EntropyModel):
@@ -488,15 +541,16 @@ class EntropyBottleneck(EntropyModel):
         return indexes.int().repeat(N, 1, H, W)
 
     def compress(self, x):
-        indexes = self._build_indexes(x.size()).to(x.device)
-        medians = self._get_medians().detach().expand(x.size(0), -1, 1, 1)
-        return super().compress(x, indexes, medians)
+        """the medians go in as one value per channel and the indexes are the channel numbers (`_build_indexes`), both inside the launch"""
+        if len(x.size()) != 4:
+            raise ValueError("Invalid `inputs` size. Expected a 4-D tensor.")
+        return self._compress(x, chan_means=self._medians_vec())
 
     def decompress(self, strings, size):
+        if not isinstance(strings, (tuple, list)):
+            raise ValueError("Invalid `strings` parameter type.")
         output_size = (len(strings), self._quantized_cdf.size(0), size[0], size[1])
-        indexes = self._build_indexes(output_size).to(self._quantized_cdf.device)
-        medians = self._get_medians().detach().expand(len(strings), -1, 1, 1)
-        return super().decompress(strings, indexes, medians)
+        return self._decompress(strings, output_size, chan_means=self._medians_vec(), device=self._quantized_cdf.device)
 
 
 class _EBAuxFunction(torch.autograd.Function):
@@ -584,3 +638,6 @@ class GaussianConditional(EntropyModel):
 
     def build_indexes(self, scales):
         return F.build_indexes(F.to_nhwc(scales.detach()), self.scale_table, self._scale_bound)
+
+    def _scale_index_args(self):
+        return self.scale_table, self._scale_bound

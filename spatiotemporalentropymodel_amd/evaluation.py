@@ -23,6 +23,20 @@ W + 3(H-1) steps instead of H * W positions; reconstructions and PSNR are the ra
 The script's last line reads out_dec["entropy_params"], a key the reference model's decompress() does not return
 (spatiotemporalpriors.py:1012 -> KeyError at :152 as shipped); the key is returned holding None.
 
+The pixel-domain models (models/stem_roi.py: stem_baseline, stem_baselinev2, stem_roi, stem_roi_wo_gsc, stem_roi_i) have the loop of
+stem_roi/eval_stem_roi.py and stem_roi/eval_stem_baseline.py:
+
+    quality_map(kind, h, w, level)                 the test-time maps of STEMTestDataset_Qmap, eval_stem_roi.py:77-93
+    inference_pixel_i(model_i, x, qmap)            eval_stem_roi.py:112-166 / eval_stem_baseline.py:83-132  (inference_i)
+    inference_pixel_p(model_p, x, x_cond, qmap)    eval_stem_roi.py:169-227 / eval_stem_baseline.py:134-187 (inference_p)
+    eval_gop_pixel(model_i, model_p, frames, ...)  the frame loops, eval_stem_roi.py:230-354: a P frame is conditioned on the previous
+                                                   frame's cropped reconstruction
+    eval_levels(model_i, model_p, frames, levels)  the sweep over uniform levels of eval_rc, eval_stem_roi.py:368-375
+
+These are pinned by tests/golden/pixel_eval_roi.npz and pixel_eval_baseline.npz (tests/golden/make_golden_pixel_eval.py runs the two
+scripts' own functions) through
+tests/test_hip_pixel_eval.py.
+
 Pinned by tests/golden/eval_gop.npz (tests/golden/make_golden.py:gen_eval_gop runs the reference's two functions themselves on
 an I + 2 P chain) through tests/test_hip_codec.py::test_eval_gop_chain_matches_reference.
 """
@@ -384,3 +398,168 @@ def eval_sequence(imodel, stem, frames, gop=12, concurrent_gops=8, all_intra=Fal
         for k in ("psnr_y", "psnr_u", "psnr_v", "psnr_yuv"):
             res[k + "_ave"] = sum(f[k] for f in per_frame) / n
     return res
+
+
+# ----------------------------------------------------------------------------- pixel-domain models (stem_roi/eval_stem_*.py)
+def quality_map(kind, h, w, level=0, level_range=(0, 100)):
+    """A test-time quality map [1,1,h,w] float32 (host tensor), values in [0, 1] (eval_stem_roi.py:77-93):
+        "uniform"     level / level_range[1] everywhere
+        "horizontal"  np.linspace(0, 1, w) in every row
+        "vertical"    np.linspace(0, 1, h) in every column
+    computed in float64 with numpy, then cast, as the script does.  The script's vertical branch tiles linspace(0, 1, h) into a
+    (1, h * w) array, which no model accepts; what is built here is its evident intent, the transpose of the horizontal map.
+    A tensor [h,w] / [1,h,w] / [1,1,h,w] (an ROI mask) is returned as [1,1,h,w] float32 with its values untouched."""
+    import numpy as np
+    if torch.is_tensor(kind):
+        if tuple(kind.shape[-2:]) != (h, w) or kind.dim() not in (2, 3, 4) or any(d != 1 for d in kind.shape[:-2]):
+            raise ValueError(f"a quality map for a {h} x {w} frame is [h,w], [1,h,w] or [1,1,h,w], got {tuple(kind.shape)}")
+        return kind.reshape(1, 1, h, w).float()
+    if kind == "uniform":
+        q = np.full((h, w), float(level) / float(level_range[1]), dtype=np.float64)
+    elif kind == "horizontal":
+        q = np.tile(np.linspace(0, 1, w), (h, 1))
+    elif kind == "vertical":
+        q = np.tile(np.linspace(0, 1, h)[:, None], (1, w))
+    else:
+        raise ValueError(f'quality_map kind is "uniform", "horizontal", "vertical" or a tensor, got {kind!r}')
+    return torch.from_numpy(q.astype(np.float32)).reshape(1, 1, h, w)
+
+
+def _takes_qmap(model):
+    return bool(getattr(model, "QMAP", False))
+
+
+def psnr_roi(x, x_hat, weight):
+    """-10 log10(sum w (x - x_hat)^2 / (3 sum w)) of one frame [1,3,h,w] under the weight map [1,1,h,w]: the weighted squared error by
+    the HIP reduction (functional.weighted_sqerr_sum, accumulated in float64), sum w in float64.  None when sum w == 0."""
+    from . import functional
+    if tuple(weight.shape) != (x.shape[0], 1, x.shape[2], x.shape[3]):
+        raise ValueError(f"roi_weight for a frame {tuple(x.shape)} is [B,1,h,w], got {tuple(weight.shape)}")
+    if not (x.is_cuda and x_hat.is_cuda and weight.is_cuda):
+        raise RuntimeError("psnr_roi runs the HIP reduction: the frame, its reconstruction and the weight map must be device tensors")
+    total = float(weight.double().sum())
+    if total == 0:
+        return None
+    sse = float(functional.weighted_sqerr_sum(x_hat.float().contiguous(), x.float().contiguous(), weight.contiguous()))
+    return -10 * math.log10(sse / (x.shape[1] * total)) if sse > 0 else float("inf")
+
+
+def _pixel_frame(model, x, x_conditioned, qmap, with_msssim, roi_weight):
+    """inference_i / inference_p of the two scripts: one body, the condition and the map passed where the model takes them"""
+    x = x.unsqueeze(0) if x.dim() == 3 else x
+    h, w = x.size(2), x.size(3)
+    if qmap is not None:
+        qmap = quality_map(qmap, h, w).to(x.device)
+    if roi_weight is None:
+        roi_weight = qmap
+    elif roi_weight is False:
+        roi_weight = None
+    else:
+        roi_weight = quality_map(roi_weight, h, w).to(x.device)
+    ins = [bitstream.pad(x, 64)]
+    cond = None
+    if x_conditioned is not None:
+        cond = bitstream.pad(x_conditioned.unsqueeze(0) if x_conditioned.dim() == 3 else x_conditioned, 64)
+        ins.append(cond)
+    if _takes_qmap(model):
+        if qmap is None:
+            raise ValueError(f"{type(model).__name__} takes a quality map")
+        ins.append(bitstream.pad(qmap, 64))
+    _sync(x)
+    start = time.time()
+    out_enc = model.compress(*ins)
+    out_forward = model(*ins)
+    _sync(x)
+    enc_time = time.time() - start
+    start = time.time()
+    out_dec = model.decompress(out_enc["strings"], out_enc["shape"], *([cond] if cond is not None else []))
+    _sync(x)
+    dec_time = time.time() - start
+    x_hat = bitstream.crop(out_dec["x_hat"], (h, w))
+    num_pixels = x.size(0) * h * w
+    bpp, est = _bpp_terms(out_enc, out_forward, num_pixels)
+    quality = _metrics(x, x_hat, with_msssim)
+    out = {"psnr": quality[0], "ms-ssim": quality[1], "bpp": bpp, "bits": sum(len(s[0]) for s in out_enc["strings"]) * 8.0, "estimate_bpp": sum(est.values()),
+           "estimate_y_bpp": est.get("y"), "estimate_z_bpp": est.get("z"), "y_bpp": len(out_enc["strings"][0][0]) * 8.0 / num_pixels,
+           "z_bpp": len(out_enc["strings"][1][0]) * 8.0 / num_pixels, "encoding_time": enc_time, "decoding_time": dec_time,
+           "strings": out_enc["strings"], "shape": tuple(out_enc["shape"]), "x_hat": x_hat}
+    if roi_weight is not None:
+        out["psnr_roi"] = psnr_roi(x, x_hat, roi_weight)
+    return out
+
+
+@torch.no_grad()
+def inference_pixel_i(model_i, x, qmap=None, with_msssim=True, roi_weight=None):
+    """x: one image [3,h,w] in [0,1]; qmap: what `quality_map` passes through, or None.  The frame and the map are zero-padded to
+    multiples of 64 (centred), then compress + forward (the rate estimate), decompress, crop (eval_stem_roi.py:112-166,
+    eval_stem_baseline.py:83-132).  The map goes to the models that take one (stem_roi_i); every I-frame model whose compress /
+    decompress return "strings", "shape" and "x_hat" is accepted (MeanScaleHyperprior, mbt2018).  Keys as `inference_iframe`, plus
+    "bits"; with a weight map -- roi_weight, by default the quality map, False for none -- also "psnr_roi" (`psnr_roi`)."""
+    return _pixel_frame(model_i, x, None, qmap, with_msssim, roi_weight)
+
+
+@torch.no_grad()
+def inference_pixel_p(model_p, x, x_conditioned, qmap=None, with_msssim=True, roi_weight=None):
+    """`inference_pixel_i` for a P-frame model: x_conditioned [3,h,w] or [1,3,h,w], the previous frame's reconstruction at the
+    frame's own size, is zero-padded like the frame (eval_stem_roi.py:169-227, eval_stem_baseline.py:134-187)."""
+    return _pixel_frame(model_p, x, x_conditioned, qmap, with_msssim, roi_weight)
+
+
+def _per_frame_maps(qmaps):
+    """the four forms of eval_gop_pixel's `qmaps` -> a function (index, h, w) -> map or None"""
+    if qmaps is None:
+        return lambda index, h, w: None
+    if callable(qmaps):
+        return qmaps
+    if torch.is_tensor(qmaps):
+        return lambda index, h, w: qmaps
+    it = iter(qmaps)
+
+    def following(index, h, w):
+        try:
+            return next(it)
+        except StopIteration:
+            raise ValueError(f"qmaps ran out at frame {index}: an iterable of maps is parallel to the frames") from None
+
+    return following
+
+
+@torch.no_grad()
+def eval_gop_pixel(model_i, model_p, frames, qmaps=None, gop=12, all_intra=False, with_msssim=True, roi_weight=None):
+    """The frame loop of the two scripts (eval_stem_roi.py:230-354) over ONE sequence.  frames: iterable of [3,h,w] images in display
+    order.  Frame k (1-based) with k % gop == 1 is an I frame (model_i), every other one a P frame (model_p) conditioned on the previous
+    frame's CROPPED x_hat, which is zero-padded again: the border of the condition is zero, not the decoder's padded reconstruction
+    (:237-242).  With gop == 1 that rule never fires after the first frame (k % 1 == 0): the sequence is coded I P P P ..., as `eval_gop`
+    does, where the script's loader (eval_stem_roi.py:96, index % gop == 0) would make every frame intra -- ask for that with all_intra.
+    qmaps: None; one map for every frame; an iterable of maps parallel to `frames`; or a callable (index, h, w) -> map
+    with the 0-based frame index.  A map is anything `quality_map` passes through.  roi_weight: as in `inference_pixel_i`, one for every
+    frame.  -> {"frames": the per-frame dictionaries plus "type", "psnr_ave", "msssim_ave", "bpp_ave", "bits_ave", "estimate_bpp_ave",
+    "psnr_roi_ave"}; the last is the mean over the frames that have a finite "psnr_roi", None without any."""
+    map_of = _per_frame_maps(qmaps)
+    per_frame, x_cond = [], None
+    for index, x in enumerate(frames):
+        q = map_of(index, x.size(-2), x.size(-1))
+        if all_intra or (index + 1) % gop == 1 or x_cond is None:
+            out = inference_pixel_i(model_i, x, q, with_msssim, roi_weight)
+            out["type"] = "I"
+        else:
+            out = inference_pixel_p(model_p, x, x_cond, q, with_msssim, roi_weight)
+            out["type"] = "P"
+        x_cond = out["x_hat"]
+        per_frame.append(out)
+    n = max(1, len(per_frame))
+    ms = [f["ms-ssim"] for f in per_frame if f["ms-ssim"] is not None]
+    roi = [f["psnr_roi"] for f in per_frame if f.get("psnr_roi") is not None and math.isfinite(f["psnr_roi"])]
+    return {"frames": per_frame, "psnr_ave": sum(f["psnr"] for f in per_frame) / n, "msssim_ave": (sum(ms) / len(ms)) if ms else None,
+            "bpp_ave": sum(f["bpp"] for f in per_frame) / n, "bits_ave": sum(f["bits"] for f in per_frame) / n,
+            "estimate_bpp_ave": sum(f["estimate_bpp"] for f in per_frame) / n, "psnr_roi_ave": (sum(roi) / len(roi)) if roi else None}
+
+
+def eval_levels(model_i, model_p, frames, levels=(0.30, 0.45, 0.55, 0.70), gop=12, level_range=(0, 1), **kwargs):
+    """The rate sweep of eval_rc / _eval_stem_roi_seq_rc (eval_stem_roi.py:307-375): one `eval_gop_pixel` per level with the uniform
+    map level / level_range[1] on every frame.  frames must be re-iterable (a list, a data.YUVSequence): every level reads it again.
+    kwargs: `eval_gop_pixel`'s (all_intra, with_msssim, roi_weight).  -> {level: result}."""
+    if iter(frames) is frames:
+        raise ValueError("eval_levels reads the frames once per level: pass a list or another re-iterable sequence, not an iterator")
+    return {level: eval_gop_pixel(model_i, model_p, frames, qmaps=lambda index, h, w, level=level: quality_map("uniform", h, w, level, level_range),
+                                  gop=gop, **kwargs) for level in levels}

@@ -1441,7 +1441,69 @@ def build_indexes(scales, table, scale_bound=0.11):
     return idx
 
 
-SUMSQ_SCRATCH = 2048          # include/stem_hip.h: `acc` holds 1 + SUMSQ_SCRATCH doubles, acc[0] is the running sum
+def _pitch(t, name, shape):
+    """pixel pitch of an NHWC-memory fp32 device tensor of logical `shape`, for the one-shot coding calls"""
+    _require_cuda(t)
+    ld = nhwc_ld(t)
+    if tuple(t.shape) != tuple(shape) or ld is None:
+        raise ValueError(f"{name}: expected an NHWC-memory tensor of shape {tuple(shape)}, got {tuple(t.shape)} with strides {t.stride()}")
+    return ld
+
+
+def _chan_vec(v, Cc, name):
+    _require_cuda(v)
+    if v.dim() != 1 or v.numel() != Cc or not v.is_contiguous():
+        raise ValueError(f"{name}: expected a dense vector of {Cc} values, got {tuple(v.shape)}")
+    return v
+
+
+def symbols_pack(y=None, means=None, chan_means=None, scales=None, table=None, scale_bound=0.11, want_indexes=True, out=None):
+    """The encoder's (and, with y=None, the decoder's) device side of a one-shot coding call: stem_symbols_pack.
+    y / means / scales: NHWC-memory [B,C,H,W] (channel slices allowed); chan_means: [C] (a bottleneck's medians); table: the scale
+    table of `scales`; without scales the indexes are the channel numbers.  -> int32 [2,B,C,H,W], dense: [0] = symbols
+    rint(y - m), [1] = indexes.  y=None leaves [0] unwritten, want_indexes=False leaves [1] unwritten.  One of y / scales is given:
+    it names B,C,H,W and the device."""
+    ref = y if y is not None else scales
+    if ref is None:
+        raise ValueError("symbols_pack: one of y / scales is needed (channel-number indexes alone need no device)")
+    shape = tuple(ref.shape)
+    B, Cc, H, W = (int(s) for s in shape)
+    device = ref.device
+    if scales is not None and table is None:
+        raise ValueError("symbols_pack: scales need their table")
+    si = out if out is not None else torch.empty((2, B, Cc, H, W), device=device, dtype=torch.int32)
+    assert si.dtype == torch.int32 and si.is_contiguous() and tuple(si.shape) == (2, B, Cc, H, W)
+    ldy = _pitch(y, "y", shape) if y is not None else 0
+    ldm = _pitch(means, "means", shape) if means is not None else 0
+    lds = _pitch(scales, "scales", shape) if scales is not None else 0
+    if chan_means is not None:
+        _chan_vec(chan_means, Cc, "chan_means")
+    if table is not None:
+        _require_cuda(table)
+        assert table.is_contiguous()
+    _chk(_lib.hip().stem_symbols_pack(_ptr(y), ldy, _ptr(means), ldm, _ptr(chan_means), _ptr(scales), lds,
+                                      _ptr(table) if scales is not None else 0, table.numel() if scales is not None else 0,
+                                      float(scale_bound), si[0].data_ptr() if y is not None else 0,
+                                      si[1].data_ptr() if want_indexes else 0, B, H, W, Cc, _stream()))
+    return si
+
+
+def symbols_unpack(sym, means=None, chan_means=None, out=None):
+    """stem_symbols_unpack: sym int32 dense [B,C,H,W] (device) -> y_hat = float(sym) + m, NHWC-memory [B,C,H,W]
+    (EntropyModel.dequantize as one launch, with the layout change).  means: NHWC-memory [B,C,H,W]; chan_means: [C]."""
+    if not sym.is_cuda or sym.dtype != torch.int32 or sym.dim() != 4 or not sym.is_contiguous():
+        raise RuntimeError("symbols_unpack expects a dense int32 [B,C,H,W] device tensor (no CPU fallback exists)")
+    B, Cc, H, W = sym.shape
+    ldm = _pitch(means, "means", sym.shape) if means is not None else 0
+    if chan_means is not None:
+        _chan_vec(chan_means, Cc, "chan_means")
+    y_hat = out if out is not None else empty_nhwc(B, Cc, H, W, sym.device)
+    ldo = _pitch(y_hat, "out", sym.shape)
+    _chk(_lib.hip().stem_symbols_unpack(sym.data_ptr(), _ptr(means), ldm, _ptr(chan_means), y_hat.data_ptr(), ldo, B, H, W, Cc, _stream()))
+    return y_hat
+
+
+SUMSQ_SCRATCH = 2048         # include/stem_hip.h: `acc` holds 1 + SUMSQ_SCRATCH doubles, acc[0] is the running sum
 
 
 def sumsq_accumulator(device):

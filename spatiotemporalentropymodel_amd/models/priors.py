@@ -1,5 +1,6 @@
-"""CompressionModel base class and the I-frame transforms of JointAutoregressiveHierarchicalPriors
-("mbt2018": compressai/models/priors.py:42-106, 406-694).
+"""CompressionModel base class, the I-frame transforms of JointAutoregressiveHierarchicalPriors
+("mbt2018": compressai/models/priors.py:42-106, 406-694) and MeanScaleHyperprior ("mbt2018-mean": priors.py:196-402), the I-frame
+model stem_roi/eval_stem_baseline.py pairs with stem_baseline.
 
 On the STEM training path only g_a / g_s (getY / getX) are executed.  The evaluation loop also codes its I frames with this
 model (stem/evalSTEM.py:54-59: compress / decompress; priors.py:476-716): forward (inference), compress and decompress run the
@@ -14,7 +15,7 @@ from ..entropy_models import EntropyBottleneck, GaussianConditional
 from ..layers import GDN, Conv2d, ConvTranspose2d, FusedSequential, LeakyReLU, MaskedConv2d, cat, conv, deconv
 from .utils import update_registered_buffers
 
-__all__ = ["CompressionModel", "JointAutoregressiveHierarchicalPriors"]
+__all__ = ["CompressionModel", "JointAutoregressiveHierarchicalPriors", "MeanScaleHyperprior"]
 
 
 class CompressionModel(nn.Module):
@@ -125,6 +126,92 @@ class JointAutoregressiveHierarchicalPriors(CompressionModel):
 
     def update(self, scale_table=None, force=False):
         """the Gaussian tables next to the bottleneck's (priors.py's MeanScaleHyperprior.update, which mbt2018 inherits)"""
+        from .spatiotemporalpriors import get_scale_table
+        if scale_table is None:
+            scale_table = get_scale_table()
+        updated = self.gaussian_conditional.update_scale_table(scale_table, force=force)
+        updated |= super().update(force=force)
+        return updated
+
+    def load_state_dict(self, state_dict, strict=True):
+        update_registered_buffers(self.gaussian_conditional, "gaussian_conditional",
+                                  ["_quantized_cdf", "_offset", "_cdf_length", "scale_table"], state_dict)
+        return super().load_state_dict(state_dict, strict=strict)
+
+
+class MeanScaleHyperprior(CompressionModel):
+    """Hyper-prior with a mean and a scale per latent and no spatial prior (priors.py:316-402, on ScaleHyperprior's g_a / g_s,
+    :196-250): a whole frame's latents are coded in one host call (EntropyModel.compress / decompress on stem_symbols_pack /
+    stem_symbols_unpack).  Module names and state-dict keys are the reference's."""
+
+    def __init__(self, N, M, **kwargs):
+        super().__init__(entropy_bottleneck_channels=N, **kwargs)
+        self.g_a = FusedSequential(conv(3, N), GDN(N), conv(N, N), GDN(N), conv(N, N), GDN(N), conv(N, M))
+        self.g_s = FusedSequential(deconv(M, N), GDN(N, inverse=True), deconv(N, N), GDN(N, inverse=True),
+                                   deconv(N, N), GDN(N, inverse=True), deconv(N, 3))
+        self.h_a = FusedSequential(conv(M, N, stride=1, kernel_size=3), LeakyReLU(inplace=True),
+                                   conv(N, N), LeakyReLU(inplace=True), conv(N, N))
+        self.h_s = FusedSequential(deconv(N, M), LeakyReLU(inplace=True),
+                                   deconv(M, M * 3 // 2), LeakyReLU(inplace=True),
+                                   conv(M * 3 // 2, M * 2, stride=1, kernel_size=3))
+        self.gaussian_conditional = GaussianConditional(None)
+        self.N, self.M = int(N), int(M)
+
+    @property
+    def downsampling_factor(self) -> int:
+        return 2 ** (4 + 2)
+
+    def _gaussian_params(self, z_hat):
+        return self.h_s(z_hat).chunk(2, 1)
+
+    def forward(self, x):
+        """priors.py:347-362 -> {"y", "y_hat", "x_hat", "likelihoods": {"y", "z"}}"""
+        y = self.g_a(x)
+        z = self.h_a(y)
+        z_hat, z_likelihoods = self.entropy_bottleneck(z)
+        scales_hat, means_hat = self._gaussian_params(z_hat)
+        y_hat, y_likelihoods = self.gaussian_conditional(y, scales_hat, means=means_hat)
+        x_hat = self.g_s(y_hat)
+        return {"y": y, "y_hat": y_hat, "x_hat": x_hat, "likelihoods": {"y": y_likelihoods, "z": z_likelihoods}}
+
+    def compress(self, x):
+        """priors.py:364-376 -> {"strings": [y_strings, z_strings], "shape": z.shape[-2:]}"""
+        with torch.no_grad():
+            y = self.g_a(x)
+            z = self.h_a(y)
+            z_strings = self.entropy_bottleneck.compress(z)
+            z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
+            scales_hat, means_hat = self._gaussian_params(z_hat)
+            y_strings = self.gaussian_conditional.compress(y, None, means=means_hat, scales=scales_hat)
+        return {"strings": [y_strings, z_strings], "shape": z.size()[-2:]}
+
+    def decompress(self, strings, shape):
+        """priors.py:378-388 -> {"x_hat", "y_hat"}"""
+        assert isinstance(strings, list) and len(strings) == 2
+        with torch.no_grad():
+            z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
+            scales_hat, means_hat = self._gaussian_params(z_hat)
+            y_hat = self.gaussian_conditional.decompress(strings[0], None, means=means_hat, scales=scales_hat)
+            x_hat = F.to_nchw(self.g_s(y_hat), clamp01=True)
+        return {"x_hat": x_hat, "y_hat": y_hat}
+
+    def getY(self, x):
+        """-> (y, quantised y): noise in training mode, ROUNDED in eval mode (priors.py:390-395), unlike mbt2018's getY"""
+        y = self.g_a(x)
+        return y, self.gaussian_conditional.quantize(y, "noise" if self.training else "dequantize")
+
+    def getX(self, y_hat):
+        """g_s + clamp(0,1); returns a contiguous NCHW image batch (priors.py:397-402)"""
+        return F.to_nchw(self.g_s(y_hat), clamp01=True)
+
+    @classmethod
+    def from_state_dict(cls, state_dict):
+        """a new model sized by, and loaded from, `state_dict` (priors.py:278-285)"""
+        net = cls(state_dict["g_a.0.weight"].size(0), state_dict["g_a.6.weight"].size(0))
+        net.load_state_dict(state_dict)
+        return net
+
+    def update(self, scale_table=None, force=False):
         from .spatiotemporalpriors import get_scale_table
         if scale_table is None:
             scale_table = get_scale_table()

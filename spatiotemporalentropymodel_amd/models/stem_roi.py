@@ -133,8 +133,7 @@ class _PixelStem(CompressionModel):
         z_strings = self.entropy_bottleneck.compress(z)
         z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
         scales_hat, means_hat = self._gaussian_params(z_hat, y_conditioned).chunk(2, 1)
-        indexes = self.gaussian_conditional.build_indexes(scales_hat)
-        y_strings = self.gaussian_conditional.compress(y_cur, indexes, means=means_hat)
+        y_strings = self.gaussian_conditional.compress(y_cur, None, means=means_hat, scales=scales_hat)
         return {"strings": [y_strings, z_strings], "shape": z.size()[-2:]}
 
     def decompress(self, strings, shape, x_conditioned=None):
@@ -144,8 +143,7 @@ class _PixelStem(CompressionModel):
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
         y_conditioned = self._condition(x_conditioned) if self.TEMPORAL else None
         scales_hat, means_hat = self._gaussian_params(z_hat, y_conditioned).chunk(2, 1)
-        indexes = self.gaussian_conditional.build_indexes(scales_hat)
-        y_hat = self.gaussian_conditional.decompress(strings[0], indexes, means=means_hat)
+        y_hat = self.gaussian_conditional.decompress(strings[0], None, means=means_hat, scales=scales_hat)
         x_hat = F.to_nchw(self._synthesis(y_hat, z_hat), clamp01=True)
         return {"x_hat": x_hat, "y_hat": y_hat, "entropy_params": {"scales_hat": scales_hat, "means_hat": means_hat}}
 
