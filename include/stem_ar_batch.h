@@ -19,6 +19,7 @@
  *   - y[n] = sum + bias[n] (+ 0.0f without a bias), then v > 0 ? v : v * slope for STEM_ACT_LRELU.
  * The scale-to-index search is T - 1 - #{t < T - 1 : max(scale, scale_bound) <= table[t]}, the quantisation q = rintf(pix - mean)
  * (ties to even), pix <- q + mean, symbol = (int32_t)q; the decoder's pix <- (float)symbol + mean is the same float.
+ * csrc/ar_canon.h is the device statement of all of this: the one header in which the kernels' leaf arithmetic is written.
  * tests/ar_ref.py states all of this in numpy and tests/test_hip_ar_ops.py holds every kernel form to it bit for bit.
  */
 #ifndef STEM_AR_BATCH_H
@@ -49,7 +50,7 @@ int stem_ar_encode_batch(const float *w_ctx, int ld_ctx, const float *b_ctx, con
  * M channels like this:
  *   - steps run t = 0 .. W + 3(H-1) - 1;
  *   - within a step, rows run h = h0(t) .. h0(t) + np(t) - 1 in ascending order, with w = t - 3h, where
- *     h0(t) = max(0, ceil((t - (W-1)) / 3)) and np(t) = min(H-1, floor(t / 3)) - h0(t) + 1  (wave_range of csrc/ar.hip; np(t) = 0 for
+ *     h0(t) = max(0, ceil((t - (W-1)) / 3)) and np(t) = min(H-1, floor(t / 3)) - h0(t) + 1  (wave_range of csrc/ar_canon.h; np(t) = 0 for
  *     the steps between two rows of a latent with W < 3);
  *   - within a position, channels run c = 0 .. M-1.
  * The rank of (h, w, c) is therefore M * (sum over t' < t of np(t')) + (h - h0(t)) * M + c.  codec.wave_order(H, W) states the same

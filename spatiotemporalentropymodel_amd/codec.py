@@ -53,7 +53,7 @@ def _check_order(order, model=None):
 
 def wave_order(H, W):
     """The wavefront symbol order of an H x W latent (pure: numpy only).  Steps run t = 0 .. W + 3(H-1) - 1; within a step rows run
-    h = h0(t) .. h0(t) + np(t) - 1 ascending with w = t - 3h (h0, np: wave_range of csrc/ar.hip); within a position the channels run
+    h = h0(t) .. h0(t) + np(t) - 1 ascending with w = t - 3h (h0, np: wave_range of csrc/ar_canon.h); within a position the channels run
     0 .. M-1.  -> (the raster indices h * W + w in wavefront order, int64 [H*W]; the step sizes np(t), int64 [W + 3(H-1)])"""
     if H < 1 or W < 1:
         raise ValueError(f"wave_order: a latent has at least one position, got {H} x {W}")
@@ -277,49 +277,28 @@ def _encode_latents(model, target, hp, tp, order="raster"):
     dev = target.device
     ar = _ARContext(model, dev)
     tables = model.gaussian_conditional.host_tables()
-    if order == "wavefront":
-        # the existing encoder (one image or the batch), one launch that gathers symbols and indexes into step order, one copy
-        si = torch.empty((2, B, H * W, M), device=dev, dtype=torch.int32)
-        if B > 1 and not _config.runtime().ar_stepwise:
-            buf = torch.zeros((B, H + 2 * _P, W + 2 * _P, M), device=dev, dtype=torch.float32)
-            buf[:, _P:_P + H, _P:_P + W].permute(0, 3, 1, 2).copy_(target)
-            ar.encode_batch(buf, B, H, W, *_prior_addrs(tp, hp, 0, H, W, M), si[0], si[1])
-        else:
-            for b in range(B):
-                ar.encode_wavefront(_padded(target[b:b + 1], H, W, M, dev), H, W, *_prior_addrs(tp, hp, b, H, W, M), si[0, b], si[1, b])
-        sw = torch.empty_like(si)
-        F._chk(_lib.hip().stem_ar_to_wave_order(si[0].data_ptr(), si[1].data_ptr(), sw[0].data_ptr(), sw[1].data_ptr(), B, H, W, M, F._stream()))
-        sym, idx = sw.cpu().numpy()
-
-        def code_wave(b):
-            enc = BufferedRansEncoder()
-            enc.encode_with_indexes(sym[b], idx[b], tables)                        # one host call per image
-            return enc.flush()
-
-        return list(_POOL.map(code_wave, range(B))) if B > 1 else [code_wave(0)]
+    si = torch.empty((2, B, H * W, M), device=dev, dtype=torch.int32)             # symbols | indexes of the batch, raster order per image
     if B > 1 and not _config.runtime().ar_stepwise:
-        # one queue of wavefront steps for the whole batch, one copy of all symbols and indexes, the host coder once per image on the pool
+        # one queue of wavefront steps for the whole batch
         buf = torch.zeros((B, H + 2 * _P, W + 2 * _P, M), device=dev, dtype=torch.float32)
         buf[:, _P:_P + H, _P:_P + W].permute(0, 3, 1, 2).copy_(target)
-        si = torch.empty((2, B, H * W, M), device=dev, dtype=torch.int32)
         ar.encode_batch(buf, B, H, W, *_prior_addrs(tp, hp, 0, H, W, M), si[0], si[1])
-        sym, idx = si.cpu().numpy()
+    else:
+        for b in range(B):
+            ar.encode_wavefront(_padded(target[b:b + 1], H, W, M, dev), H, W, *_prior_addrs(tp, hp, b, H, W, M), si[0, b], si[1, b])
+    if order == "wavefront":
+        # one launch gathers symbols and indexes into step order
+        sw = torch.empty_like(si)
+        F._chk(_lib.hip().stem_ar_to_wave_order(si[0].data_ptr(), si[1].data_ptr(), sw[0].data_ptr(), sw[1].data_ptr(), B, H, W, M, F._stream()))
+        si = sw
+    sym, idx = si.cpu().numpy()                                                   # one copy of all symbols and indexes
 
-        def code(b):
-            enc = BufferedRansEncoder()
-            enc.encode_with_indexes(sym[b], idx[b], tables)                        # ctypes releases the GIL for the call
-            return enc.flush()
-
-        return list(_POOL.map(code, range(B)))
-    y_strings = []
-    for b in range(B):
-        buf = _padded(target[b:b + 1], H, W, M, dev)
-        sym, idx = (torch.empty((H * W, M), device=dev, dtype=torch.int32) for _ in range(2))
-        ar.encode_wavefront(buf, H, W, *_prior_addrs(tp, hp, b, H, W, M), sym, idx)
+    def code(b):
         enc = BufferedRansEncoder()
-        enc.encode_with_indexes(sym.cpu().numpy(), idx.cpu().numpy(), tables)      # one host call per image (:955-959)
-        y_strings.append(enc.flush())
-    return y_strings
+        enc.encode_with_indexes(sym[b], idx[b], tables)                        # one host call per image (:955-959); ctypes releases the GIL
+        return enc.flush()
+
+    return list(_POOL.map(code, range(B))) if B > 1 else [code(0)]
 
 
 def stem_decompress(model, strings, shape, y_cond, order="raster"):
@@ -487,39 +466,32 @@ class _Decode:
         self.idx_host, self.sym_host = (torch.empty(self.M, dtype=torch.int32).pin_memory() for _ in range(2))
         self.decode_fn = C.cast(_lib.rans().stem_rans_decoder_decode, C.c_void_p).value      # host symbol decoder, injected as a C pointer
 
+    def _batched(self, entry, lead):
+        """Up to eight images per call of `entry`, a batched decoder of csrc/ar.hip: a zeroed buf, one decoder per image, scratch
+        [G, *lead, n] for the four products, pinned mailboxes [G, *lead, M], and the decoded interior into `self.out`."""
+        ar, B, H, W, M, dev = self.ar, self.B, self.H, self.W, self.M, self.dev
+        for b0 in range(0, B, 8):
+            G = min(8, B - b0)
+            buf = torch.zeros((G, H + 2 * _P, W + 2 * _P, M), device=dev, dtype=torch.float32)
+            scratch = [torch.empty((G, *lead, n), device=dev, dtype=torch.float32) for n in (2 * M, ar.w0.shape[0], ar.w1.shape[0], 2 * M)]
+            idx_g, sym_g = (torch.empty((G, *lead, M), dtype=torch.int32).pin_memory() for _ in range(2))
+            decs = [_decoder_on(s) for s in self.strings[b0:b0 + G]]
+            handles = (C.c_void_p * G)(*[d._h for d in decs])
+            F._chk(entry(*ar.net_args(), buf.data_ptr(), G, H, W, M, _P, *_prior_addrs(self.tp, self.hp, b0, H, W, M),
+                         *[t.data_ptr() for t in scratch], *ar.table_args(), idx_g.data_ptr(), sym_g.data_ptr(),
+                         self.decode_fn, C.addressof(handles), *self.tables.args(), F._stream()))
+            self.out[b0:b0 + G].copy_(buf[:, _P:_P + H, _P:_P + W].permute(0, 3, 1, 2))
+
     def lockstep(self):
         """Independent images advance together (csrc/ar.hip: stem_ar_decode_batch): the loop is bound by the latency of one
         position (4 dependent launches + a host round trip), which G images share; each image's arithmetic is unchanged."""
-        ar, B, H, W, M, dev = self.ar, self.B, self.H, self.W, self.M, self.dev
-        for b0 in range(0, B, 8):                            # up to eight images per call
-            G = min(8, B - b0)
-            buf = torch.zeros((G, H + 2 * _P, W + 2 * _P, M), device=dev, dtype=torch.float32)
-            scratch = [torch.empty((G, n), device=dev, dtype=torch.float32) for n in (2 * M, ar.w0.shape[0], ar.w1.shape[0], 2 * M)]
-            idx_g, sym_g = (torch.empty((G, M), dtype=torch.int32).pin_memory() for _ in range(2))
-            decs = [_decoder_on(s) for s in self.strings[b0:b0 + G]]
-            handles = (C.c_void_p * G)(*[d._h for d in decs])
-            F._chk(self.lib.stem_ar_decode_batch(*ar.net_args(), buf.data_ptr(), G, H, W, M, _P, *_prior_addrs(self.tp, self.hp, b0, H, W, M),
-                                                 *[t.data_ptr() for t in scratch], *ar.table_args(), idx_g.data_ptr(), sym_g.data_ptr(),
-                                                 self.decode_fn, C.addressof(handles), *self.tables.args(), F._stream()))
-            self.out[b0:b0 + G].copy_(buf[:, _P:_P + H, _P:_P + W].permute(0, 3, 1, 2))
+        self._batched(self.lib.stem_ar_decode_batch, ())
 
     def wave(self):
         """Wavefront-ordered strings (csrc/ar.hip: stem_ar_decode_wave_batch): W + 3(H-1) steps instead of H * W positions.  A step is
         the encoder's four batched products over the step's positions of up to eight images, one stream synchronisation and one call
         of the host coder per image for the step's np * M symbols, through mailboxes of the largest step's size."""
-        ar, B, H, W, M, dev = self.ar, self.B, self.H, self.W, self.M, self.dev
-        npmax = min(H, (W + 2) // 3)
-        for b0 in range(0, B, 8):                            # up to eight images per call
-            G = min(8, B - b0)
-            buf = torch.zeros((G, H + 2 * _P, W + 2 * _P, M), device=dev, dtype=torch.float32)
-            scratch = [torch.empty((G, npmax, n), device=dev, dtype=torch.float32) for n in (2 * M, ar.w0.shape[0], ar.w1.shape[0], 2 * M)]
-            idx_g, sym_g = (torch.empty((G, npmax, M), dtype=torch.int32).pin_memory() for _ in range(2))
-            decs = [_decoder_on(s) for s in self.strings[b0:b0 + G]]
-            handles = (C.c_void_p * G)(*[d._h for d in decs])
-            F._chk(self.lib.stem_ar_decode_wave_batch(*ar.net_args(), buf.data_ptr(), G, H, W, M, _P, *_prior_addrs(self.tp, self.hp, b0, H, W, M),
-                                                      *[t.data_ptr() for t in scratch], *ar.table_args(), idx_g.data_ptr(), sym_g.data_ptr(),
-                                                      self.decode_fn, C.addressof(handles), *self.tables.args(), F._stream()))
-            self.out[b0:b0 + G].copy_(buf[:, _P:_P + H, _P:_P + W].permute(0, 3, 1, 2))
+        self._batched(self.lib.stem_ar_decode_wave_batch, (min(self.H, (self.W + 2) // 3),))
 
     def stepwise(self, b):
         """The loop of stem_ar_decode_image written with the single-step C-ABI entry points (stem_gemv3_decode, stem_gemv3, stem_ar_finish_decode)

@@ -12,15 +12,17 @@
 // contiguous segments so neither the 5x5 window nor cat(tp, hp, ctx) is ever materialised.
 #include <chrono>
 
-#include "stem_common.h"
+#include "ar_canon.h"
 #include "../../include/stem_ar_batch.h"
 
 // Encoder and decoder must produce the SAME floats for every entropy parameter (a mean that differs in the last bit
 // shifts y_hat, which feeds later contexts; a scale on the other side of a table entry desynchronises the coder), and the
 // encoder's wavefront kernels, the one-image decoder and the lockstep decoder are different kernels.  Their dot products
 // are therefore all the CANONICAL PRODUCT that include/stem_ar_batch.h states (lane partials over columns 4 lane + 256 j, segment after
-// segment, each 16-byte step summed left to right, xor-shuffle reduction, bias, activation), compiled without FMA contraction: products
-// rounded, then added.  tests/ar_ref.py emulates that order in float32; tests/test_hip_ar_ops.py holds every form below to it bit for bit.
+// segment, each 16-byte step summed left to right, xor-shuffle reduction, bias, activation).  Its arithmetic is written once, in
+// ar_canon.h (dot4, wave_sum, finish, scale_index, quantise / dequantise, wave_range): the kernels below own their loops, loads and
+// grids -- each measured into its form -- and call those leaves.  Everything is compiled without FMA contraction: products rounded, then
+// added.  tests/ar_ref.py emulates that order in float32; tests/test_hip_ar_ops.py holds every form below to it bit for bit.
 #pragma clang fp contract(off)
 
 namespace {
@@ -46,16 +48,11 @@ __global__ __launch_bounds__(256) void gemv3_kernel(const float *W, int ldw, con
         for (int k = lane * 4; k < s.len; k += 256) {
             const f32x4 xv = *reinterpret_cast<const f32x4 *>(s.x + k);
             const f32x4 wv = *reinterpret_cast<const f32x4 *>(wr + s.woff + k);
-            acc += xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
+            acc += dot4(xv, wv);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    if (lane == 0) {
-        float v = acc + (bias ? bias[n] : 0.f);
-        if (act == STEM_ACT_LRELU) v = v > 0.f ? v : v * slope;
-        y[n] = v;
-    }
+    acc = wave_sum(acc);
+    if (lane == 0) y[n] = finish(acc, bias ? bias[n] : 0.f, act, slope);
 }
 
 // Decoder variants of the product (two launches fewer per position):
@@ -80,7 +77,7 @@ __global__ __launch_bounds__(256) void gemv3_decode_kernel(const float *W, int l
     const int lane = threadIdx.x & 63;
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (e.sym_prev && blockIdx.x == 0)
-        for (int c = threadIdx.x; c < e.M; c += 256) e.pix_prev[c] = (float)e.sym_prev[c] + e.mean_prev[c];
+        for (int c = threadIdx.x; c < e.M; c += 256) e.pix_prev[c] = dequantise(e.sym_prev[c], e.mean_prev[c]);
     if (n >= N) return;
     const float *wr = W + (size_t)n * ldw;
     float acc = 0.f;
@@ -93,26 +90,19 @@ __global__ __launch_bounds__(256) void gemv3_decode_kernel(const float *W, int l
             f32x4 xv;
             if (subst && k >= e.M) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) xv[j] = (float)e.sym_prev[k - e.M + j] + e.mean_prev[k - e.M + j];
+                for (int j = 0; j < 4; ++j) xv[j] = dequantise(e.sym_prev[k - e.M + j], e.mean_prev[k - e.M + j]);
             } else {
                 xv = *reinterpret_cast<const f32x4 *>(s.x + k);
             }
             const f32x4 wv = *reinterpret_cast<const f32x4 *>(wr + s.woff + k);
-            acc += xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
+            acc += dot4(xv, wv);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    acc = wave_sum(acc);
     if (lane == 0) {
-        float v = acc + (bias ? bias[n] : 0.f);
-        if (act == STEM_ACT_LRELU) v = v > 0.f ? v : v * slope;
+        const float v = finish(acc, bias ? bias[n] : 0.f, act, slope);
         y[n] = v;
-        if (e.table && n < e.M) {
-            const float sc = fmaxf(v, e.bound);
-            int k = e.T - 1;
-            for (int t = 0; t < e.T - 1; ++t) k -= (sc <= e.table[t]) ? 1 : 0;
-            e.idx[n] = k;
-        }
+        if (e.table && n < e.M) e.idx[n] = scale_index(v, e.bound, e.table, e.T);
     }
 }
 
@@ -122,11 +112,10 @@ __global__ void ar_finish_encode_kernel(const float *gp, const float *table, int
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= M) return;
-    const float s = fmaxf(gp[c], scale_bound), mu = gp[M + c];
-    int k = T - 1;
-    for (int t = 0; t < T - 1; ++t) k -= (s <= table[t]) ? 1 : 0;
-    const float q = rintf(pix[c] - mu);
-    pix[c] = q + mu;
+    const float mu = gp[M + c];
+    const int k = scale_index(gp[c], scale_bound, table, T);
+    float q;
+    pix[c] = quantise(pix[c], mu, q);
     sym[c] = (int32_t)q;
     idx[c] = k;
 }
@@ -134,17 +123,14 @@ __global__ void ar_index_kernel(const float *gp, const float *table, int T, floa
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= M) return;
-    const float s = fmaxf(gp[c], scale_bound);
-    int k = T - 1;
-    for (int t = 0; t < T - 1; ++t) k -= (s <= table[t]) ? 1 : 0;
-    idx[c] = k;
+    idx[c] = scale_index(gp[c], scale_bound, table, T);
 }
 // decode side: buffer <- symbol + mean  (EntropyModel.dequantize, entropy_models.py:156-163)
 __global__ void ar_finish_decode_kernel(const float *gp, const int32_t *sym, float *pix, int M)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= M) return;
-    pix[c] = (float)sym[c] + gp[M + c];
+    pix[c] = dequantise(sym[c], gp[M + c]);
 }
 
 // masked conv weight [2M][M][5][5] -> [2M][12 live taps][M]  (live taps of the type-A mask: rows 0,1 full, row 2 cols 0,1)
@@ -243,16 +229,6 @@ struct WSeg {
     long sh, sw, sp;
 };
 
-__device__ __forceinline__ void wave_range(int t, int H, int Wd, int &h0, int &np)
-{
-    int lo = t - (Wd - 1);
-    lo = lo > 0 ? (lo + 2) / 3 : 0;
-    int hi = t / 3;
-    if (hi > H - 1) hi = H - 1;
-    h0 = lo;
-    np = hi - lo + 1;
-}
-
 constexpr int WAVE_ROWS = 24;     // workgroup rows over which the positions of one wavefront step are spread (more waves in flight)
 
 __global__ __launch_bounds__(256) void gemv3_wave_kernel(const float *W, int ldw, const float *bias, WSeg s0, WSeg s1, WSeg s2,
@@ -276,16 +252,11 @@ __global__ __launch_bounds__(256) void gemv3_wave_kernel(const float *W, int ldw
             for (int k = lane * 4; k < s.len; k += 256) {
                 const f32x4 xv = *reinterpret_cast<const f32x4 *>(xp + k);
                 const f32x4 wv = *reinterpret_cast<const f32x4 *>(wr + s.woff + k);
-                acc += xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
+                acc += dot4(xv, wv);
             }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-        if (lane == 0) {
-            float v = acc + b;
-            if (act == STEM_ACT_LRELU) v = v > 0.f ? v : v * slope;
-            y[(size_t)p * ldy + n] = v;
-        }
+        acc = wave_sum(acc);
+        if (lane == 0) y[(size_t)p * ldy + n] = finish(acc, b, act, slope);
     }
 }
 
@@ -299,14 +270,13 @@ __global__ void ar_finish_encode_wave_kernel(const float *gp, const float *table
     const int p = i / M, c = i - p * M;
     const int h = h0 + p, w = t - 3 * h;
     const float *g = gp + (size_t)p * 2 * M;
-    const float s = fmaxf(g[c], scale_bound), mu = g[M + c];
-    int k = T - 1;
-    for (int q = 0; q < T - 1; ++q) k -= (s <= table[q]) ? 1 : 0;
+    const float mu = g[M + c];
+    const int k = scale_index(g[c], scale_bound, table, T);
     float *pix = buf + ((size_t)(h + pad) * Wp + (w + pad)) * M;
-    const float qv = rintf(pix[c] - mu);
-    pix[c] = qv + mu;
+    float q;
+    pix[c] = quantise(pix[c], mu, q);
     const size_t o = ((size_t)h * Wd + w) * M + c;
-    sym[o] = (int32_t)qv;
+    sym[o] = (int32_t)q;
     idx[o] = k;
 }
 
@@ -512,26 +482,18 @@ __global__ __launch_bounds__(256) void gemv3b_decode_kernel(const float *W, int 
             for (int t = 0; t < MAXS; ++t) xv[t] = *reinterpret_cast<const f32x4 *>(s.x + g * s.stride + (ok[t] ? lane * 4 + 256 * t : 0));
 #pragma unroll
             for (int t = 0; t < MAXS; ++t) {
-                const float d = xv[t][0] * wv[t][0] + xv[t][1] * wv[t][1] + xv[t][2] * wv[t][2] + xv[t][3] * wv[t][3];
+                const float d = dot4(xv[t], wv[t]);
                 acc[g] = ok[t] ? acc[g] + d : acc[g];
             }
         }
     }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-        float a = acc[g];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
+        const float a = wave_sum(acc[g]);
         if (lane == 0) {
-            float v = a + (bias ? bias[n] : 0.f);
-            if (act == STEM_ACT_LRELU) v = v > 0.f ? v : v * slope;
+            const float v = finish(a, bias ? bias[n] : 0.f, act, slope);
             y[g * ystride + n] = v;
-            if (e.table && n < e.M) {
-                const float sc = fmaxf(v, e.bound);
-                int k = e.T - 1;
-                for (int t = 0; t < e.T - 1; ++t) k -= (sc <= e.table[t]) ? 1 : 0;
-                e.idx[g * e.M + n] = k;
-            }
+            if (e.table && n < e.M) e.idx[g * e.M + n] = scale_index(v, e.bound, e.table, e.T);
         }
     }
 }
@@ -562,8 +524,27 @@ __global__ void ar_finish_decode_batch_kernel(const float *gp, long gp_stride, c
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M * G) return;
     const int g = i / M, c = i - g * M;
-    pix[g * buf_stride + c] = (float)sym[g * M + c] + gp[g * gp_stride + M + c];
+    pix[g * buf_stride + c] = dequantise(sym[g * M + c], gp[g * gp_stride + M + c]);
 }
+
+// STEM_AR_PROFILE: where a decoder step's time goes -- queueing the launches, waiting for the stream, the host coder -- summed over a call
+struct StepTimer {
+    const bool on;
+    double launch = 0, wait = 0, host = 0, mark[3] = {0, 0, 0};
+    StepTimer() : on(enabled()) {}
+    static bool enabled()
+    {
+        static const bool prof = getenv("STEM_AR_PROFILE") != nullptr;
+        return prof;
+    }
+    static double now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    void at(int i) { if (on) mark[i] = now(); }       // 0: the step begins, 1: its launches are queued, 2: the stream has drained
+    void step_done()                                   // ... and the host coder has returned
+    {
+        if (!on) return;
+        launch += mark[1] - mark[0]; wait += mark[2] - mark[1]; host += now() - mark[2];
+    }
+};
 
 }   // namespace
 
@@ -585,9 +566,7 @@ STEM_EXPORT int stem_ar_decode_batch(const float *w_ctx, int ld_ctx, const float
     const int P = 2 * M, Wp = W + 2 * pad;
     const long bufs = (long)(H + 2 * pad) * Wp * M, pris = (long)H * W * P;        // image strides of buf and of tp / hp
     float *pix_prev = nullptr;
-    static const bool prof = getenv("STEM_AR_PROFILE") != nullptr;         // where a position's time goes (launch / wait / host coder)
-    double t_launch = 0, t_wait = 0, t_host = 0;
-    auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    StepTimer tm;
     DecodeExtraB none;
     memset(&none, 0, sizeof(none));
     none.M = M; none.gp_stride = P; none.buf_stride = bufs;
@@ -595,7 +574,7 @@ STEM_EXPORT int stem_ar_decode_batch(const float *w_ctx, int ld_ctx, const float
     for (int h = 0; h < H; ++h)
         for (int w = 0; w < W; ++w) {
             const size_t pos = (size_t)h * W + w;
-            const double ta = prof ? now() : 0;
+            tm.at(0);
             const float *r0 = buf + ((size_t)h * Wp + w) * M, *r1 = r0 + (size_t)Wp * M, *r2 = r1 + (size_t)Wp * M;
             // The previous position's symbols arrive in the pinned host mailbox.  The one-image loop lets every wavefront of
             // the context product substitute them on the fly (saving a launch); with G images that is 2M x G floats fetched
@@ -617,26 +596,23 @@ STEM_EXPORT int stem_ar_decode_batch(const float *w_ctx, int ld_ctx, const float
             DecodeExtraB tail = none;
             tail.table = table; tail.T = T; tail.bound = scale_bound; tail.idx = idx_host;
             launch_gemv3b_g(G, st, P, w2, ld2, b2, SegB{h2, n1, 0, (long)n1}, nil, nil, gp, (long)P, 0, 0.f, tail);
-            const double tb = prof ? now() : 0;
+            tm.at(1);
             if (hipStreamSynchronize(st) != hipSuccess) {
                 stem_set_error("stem_ar_decode_batch: device error at position (%d, %d): %s", h, w, hipGetErrorString(hipGetLastError()));
                 return -2;
             }
-            const double tc = prof ? now() : 0;
+            tm.at(2);
             for (int g = 0; g < G; ++g)
                 if (int rc = decode(decs[g], idx_host + (size_t)g * M, (size_t)M, cdfs, ncdf, cdf_stride, sizes, offsets, sym_host + (size_t)g * M)) {
                     stem_set_error("stem_ar_decode_batch: host symbol decoder failed (%d) for image %d at position (%d, %d)", rc, g, h, w);
                     return -3;
                 }
             pix_prev = buf + ((size_t)(h + pad) * Wp + (w + pad)) * M;
-            if (prof) {
-                const double td = now();
-                t_launch += tb - ta; t_wait += tc - tb; t_host += td - tc;
-            }
+            tm.step_done();
         }
-    if (prof)
+    if (tm.on)
         fprintf(stderr, "[ar decode batch] G=%d positions=%d: launch %.1f us, wait %.1f us, host coder %.1f us per position step\n", G, H * W,
-                t_launch / (H * W), t_wait / (H * W), t_host / (H * W));
+                tm.launch / (H * W), tm.wait / (H * W), tm.host / (H * W));
     hipLaunchKernelGGL(ar_finish_decode_batch_kernel, dim3(cdiv(M * G, 256)), dim3(256), 0, st, gp, (long)P, sym_host, pix_prev, bufs, M, G);
     STEM_LAUNCH_CHECK("ar_decode_batch");
     return 0;
@@ -663,16 +639,6 @@ struct WSegB {
 constexpr int WAVE_ROWS_B = 32;   // workgroup rows over which the G * np positions of a step are spread
 constexpr int WAVE_U = 4;         // positions a wavefront accumulates side by side ...
 constexpr int WAVE_R = 4;         // ... for this many output rows
-
-__host__ __device__ __forceinline__ void wave_range_hd(int t, int H, int Wd, int &h0, int &np)
-{
-    int lo = t - (Wd - 1);
-    lo = lo > 0 ? (lo + 2) / 3 : 0;
-    int hi = t / 3;
-    if (hi > H - 1) hi = H - 1;
-    h0 = lo;
-    np = hi - lo + 1;
-}
 
 // positions j0, j0 + dj, ..., j0 + (U-1) dj of the step (all < G * np) for the output rows n .. n + WAVE_R - 1: every k step loads
 // WAVE_R weight vectors and U x vectors for WAVE_R * U dot products (the single-image kernel loads two vectors per product; at G = 8
@@ -706,21 +672,15 @@ __device__ __forceinline__ void wave_dots(const float *wr, int ldw, const float 
 #pragma unroll
             for (int u = 0; u < U; ++u)
 #pragma unroll
-                for (int r = 0; r < WAVE_R; ++r) acc[u][r] += xv[u][0] * wv[r][0] + xv[u][1] * wv[r][1] + xv[u][2] * wv[r][2] + xv[u][3] * wv[r][3];
+                for (int r = 0; r < WAVE_R; ++r) acc[u][r] += dot4(xv[u], wv[r]);
         }
     }
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
         for (int r = 0; r < WAVE_R; ++r) {
-            float a = acc[u][r];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
-            if (lane == 0) {
-                float v = a + b[r];
-                if (act == STEM_ACT_LRELU) v = v > 0.f ? v : v * slope;
-                y[yo[u] + r] = v;
-            }
+            const float a = wave_sum(acc[u][r]);
+            if (lane == 0) y[yo[u] + r] = finish(a, b[r], act, slope);
         }
 }
 
@@ -733,7 +693,7 @@ __global__ __launch_bounds__(256) void gemv3_wave_batch_kernel(const float *W, i
     const int n = (blockIdx.x * 4 + (threadIdx.x >> 6)) * WAVE_R;
     if (n >= N) return;
     int h0, np;
-    wave_range_hd(t, H, Wd, h0, np);
+    wave_range(t, H, Wd, h0, np);
     const int total = G * np, dj = gridDim.y;
     const float *wr = W + (size_t)n * ldw;
     float b[WAVE_R];
@@ -749,26 +709,73 @@ __global__ __launch_bounds__(256) void gemv3_wave_batch_kernel(const float *W, i
 __global__ void ar_finish_encode_wave_batch_kernel(const float *gp, long gps, const float *table, int T, float scale_bound, float *buf, long bufs,
                                                    int32_t *sym, int32_t *idx, int M, int t, int H, int Wd, int Wp, int pad, int G)
 {
-    int h0, np;
-    wave_range_hd(t, H, Wd, h0, np);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= G * np * M) return;
-    const int j = i / M, c = i - j * M;
-    const int g = j / np, p = j - g * np;
-    const int h = h0 + p, w = t - 3 * h;
-    const float *gpp = gp + (size_t)g * gps + (size_t)p * 2 * M;
-    const float s = fmaxf(gpp[c], scale_bound), mu = gpp[M + c];
-    int k = T - 1;
-    for (int q = 0; q < T - 1; ++q) k -= (s <= table[q]) ? 1 : 0;
-    float *pix = buf + (size_t)g * bufs + ((size_t)(h + pad) * Wp + (w + pad)) * M;
-    const float qv = rintf(pix[c] - mu);
-    pix[c] = qv + mu;
-    const size_t o = (((size_t)g * H + h) * Wd + w) * M + c;
-    sym[o] = (int32_t)qv;
+    WaveElem e;
+    if (!wave_elem(blockIdx.x * blockDim.x + threadIdx.x, t, H, Wd, M, G, e)) return;
+    const float *gpp = gp + (size_t)e.g * gps + (size_t)e.p * 2 * M;
+    const float mu = gpp[M + e.c];
+    const int k = scale_index(gpp[e.c], scale_bound, table, T);
+    float *pix = buf + (size_t)e.g * bufs + ((size_t)(e.h + pad) * Wp + (e.w + pad)) * M;
+    float q;
+    pix[e.c] = quantise(pix[e.c], mu, q);
+    const size_t o = (((size_t)e.g * H + e.h) * Wd + e.w) * M + e.c;
+    sym[o] = (int32_t)q;
     idx[o] = k;
 }
 
 bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// the arguments stem_ar_encode_batch and stem_ar_decode_wave_batch have in common, in the order of their prototypes
+struct WaveBatchArgs {
+    const float *w_ctx; int ld_ctx; const float *b_ctx, *w0; int ld0; const float *b0; int n0;
+    const float *w1; int ld1; const float *b1; int n1; const float *w2; int ld2; const float *b2;
+    float *buf; int G, H, W, M, pad; const float *tp, *hp;
+    float *wctx, *wh1, *wh2, *wgp; const float *table; int T; float scale_bound, slope;
+    int maxp() const { return H < (W + 2) / 3 ? H : (W + 2) / 3; }       // positions of the largest step
+};
+
+// The checks the two entry points share, under the name `who` of the one that asks.  `own`: the pointers only that entry point takes are
+// there; `boxes_ok`: its host mailboxes (the decoder's) are aligned.
+int wave_batch_check(const char *who, const WaveBatchArgs &a, bool own, bool boxes_ok)
+{
+    STEM_CHECK_ARG(a.w_ctx && a.b_ctx && a.w0 && a.b0 && a.w1 && a.b1 && a.w2 && a.b2 && a.buf && a.hp && a.wctx && a.wh1 && a.wh2 && a.wgp && a.table && own,
+                   "%s: null pointer", who);
+    STEM_CHECK_ARG(a.G >= 1, "%s: at least one image per call, got %d", who, a.G);
+    static_assert(WAVE_R == 4, "the size check below is what keeps a wavefront's WAVE_R rows inside each matrix (2M, n0, n1)");
+    STEM_CHECK_ARG(a.H > 0 && a.W > 0 && a.M > 0 && a.M % 4 == 0 && a.n0 > 0 && a.n1 > 0 && a.n0 % 4 == 0 && a.n1 % 4 == 0 && a.ld_ctx % 4 == 0 &&
+                   a.ld0 % 4 == 0 && a.ld1 % 4 == 0 && a.ld2 % 4 == 0 && a.T >= 1 && a.pad == 2, "%s: bad sizes", who);
+    STEM_CHECK_ARG(aligned16(a.w_ctx) && aligned16(a.w0) && aligned16(a.w1) && aligned16(a.w2) && aligned16(a.buf) && aligned16(a.tp) && aligned16(a.hp) &&
+                   aligned16(a.wctx) && aligned16(a.wh1) && aligned16(a.wh2) && aligned16(a.wgp), "%s: weights, buf, tp, hp and scratch must be 16-byte aligned", who);
+    STEM_CHECK_ARG(boxes_ok, "%s: the mailboxes must be 4-byte aligned", who);
+    STEM_CHECK_ARG((long)a.G * a.maxp() * a.M <= 0x7fffffffL, "%s: G * positions per step * M = %ld does not fit an int", who, (long)a.G * a.maxp() * a.M);
+    return 0;
+}
+
+// Step t (np > 0 positions per image) of G images: the four products ctx, EPM.0, EPM.2, EPM.4 over the step's G * np positions, into the
+// scratch [G][maxp][2M | n0 | n1 | 2M].  The encoder queues this and then quantises; the wavefront decoder queues the same and then
+// asks the host for the symbols -- one function, so the decoder's entropy parameters are the encoder's by construction.
+void wave_step_products(const WaveBatchArgs &a, hipStream_t st, int t, int np)
+{
+    const int M = a.M, P = 2 * M, n0 = a.n0, n1 = a.n1, maxp = a.maxp();
+    const long row = (long)(a.W + 2 * a.pad) * M;
+    const long bufs = (long)(a.H + 2 * a.pad) * row, pris = (long)a.H * a.W * P;    // image strides of buf and of tp / hp
+    const WSegB none{nullptr, 0, 0, 0, 0, 0, 0};
+    // context window of position (h, w): rows h, h+1 (5 pixels) and h+2 (2 pixels) of the image's padded buffer, starting at column w
+    const WSegB c0{a.buf, 5 * M, 0, row, M, 0, bufs}, c1{a.buf + row, 5 * M, 5 * M, row, M, 0, bufs}, c2{a.buf + 2 * row, 2 * M, 10 * M, row, M, 0, bufs};
+    const WSegB sctx{a.wctx, P, a.tp ? 2 * P : P, 0, 0, P, (long)maxp * P};
+    const WSegB stp{a.tp, P, 0, (long)a.W * P, P, 0, pris}, shp{a.hp, P, a.tp ? P : 0, (long)a.W * P, P, 0, pris};
+    const WSegB sh1{a.wh1, n0, 0, 0, 0, n0, (long)maxp * n0}, sh2{a.wh2, n1, 0, 0, 0, n1, (long)maxp * n1};
+    const int total = a.G * np;
+    const int gy = total < WAVE_ROWS_B ? total : WAVE_ROWS_B;
+    auto product = [&](const float *Wm, int ldw, const float *bias, const WSegB &s0, const WSegB &s1, const WSegB &s2, float *y, int N, int act) {
+        hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(N, 4 * WAVE_R), gy), dim3(256), 0, st, Wm, ldw, bias, s0, s1, s2, y, N, (long)maxp * N, N, act,
+                           act ? a.slope : 0.f, t, a.H, a.W, a.G);
+    };
+    product(a.w_ctx, a.ld_ctx, a.b_ctx, c0, c1, c2, a.wctx, P, 0);
+    if (a.tp) product(a.w0, a.ld0, a.b0, stp, shp, sctx, a.wh1, n0, (int)STEM_ACT_LRELU);
+    else product(a.w0, a.ld0, a.b0, shp, sctx, none, a.wh1, n0, (int)STEM_ACT_LRELU);
+    product(a.w1, a.ld1, a.b1, sh1, none, none, a.wh2, n1, (int)STEM_ACT_LRELU);
+    product(a.w2, a.ld2, a.b2, sh2, none, none, a.wgp, P, 0);
+}
 
 }   // namespace
 
@@ -778,45 +785,18 @@ STEM_EXPORT int stem_ar_encode_batch(const float *w_ctx, int ld_ctx, const float
                                      float *wctx, float *wh1, float *wh2, float *wgp, const float *table, int T, float scale_bound,
                                      float slope, int32_t *sym, int32_t *idx, void *stream)
 {
-    STEM_CHECK_ARG(w_ctx && b_ctx && w0 && b0 && w1 && b1 && w2 && b2 && buf && hp && wctx && wh1 && wh2 && wgp && table && sym && idx,
-                   "stem_ar_encode_batch: null pointer");
-    STEM_CHECK_ARG(G >= 1, "stem_ar_encode_batch: at least one image per call, got %d", G);
-    static_assert(WAVE_R == 4, "the size check below is what keeps a wavefront's WAVE_R rows inside each matrix (2M, n0, n1)");
-    STEM_CHECK_ARG(H > 0 && W > 0 && M > 0 && M % 4 == 0 && n0 > 0 && n1 > 0 && n0 % 4 == 0 && n1 % 4 == 0 && ld_ctx % 4 == 0 && ld0 % 4 == 0 &&
-                   ld1 % 4 == 0 && ld2 % 4 == 0 && T >= 1 && pad == 2, "stem_ar_encode_batch: bad sizes");
-    STEM_CHECK_ARG(aligned16(w_ctx) && aligned16(w0) && aligned16(w1) && aligned16(w2) && aligned16(buf) && aligned16(tp) && aligned16(hp) &&
-                   aligned16(wctx) && aligned16(wh1) && aligned16(wh2) && aligned16(wgp), "stem_ar_encode_batch: weights, buf, tp, hp and scratch must be 16-byte aligned");
-    const int maxp = H < (W + 2) / 3 ? H : (W + 2) / 3;
-    STEM_CHECK_ARG((long)G * maxp * M <= 0x7fffffffL, "stem_ar_encode_batch: G * positions per step * M = %ld does not fit an int", (long)G * maxp * M);
+    const WaveBatchArgs a{w_ctx, ld_ctx, b_ctx, w0, ld0, b0, n0, w1, ld1, b1, n1, w2, ld2, b2, buf, G, H, W, M, pad, tp, hp,
+                          wctx, wh1, wh2, wgp, table, T, scale_bound, slope};
+    if (int rc = wave_batch_check("stem_ar_encode_batch", a, sym && idx, true)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int P = 2 * M, Wp = W + 2 * pad;
-    const long row = (long)Wp * M;
-    const long bufs = (long)(H + 2 * pad) * row, pris = (long)H * W * P;            // image strides of buf and of tp / hp
-    const WSegB none{nullptr, 0, 0, 0, 0, 0, 0};
-    // context window of position (h, w): rows h, h+1 (5 pixels) and h+2 (2 pixels) of the image's padded buffer, starting at column w
-    const WSegB c0{buf, 5 * M, 0, row, M, 0, bufs}, c1{buf + row, 5 * M, 5 * M, row, M, 0, bufs}, c2{buf + 2 * row, 2 * M, 10 * M, row, M, 0, bufs};
-    const WSegB sctx{wctx, P, tp ? 2 * P : P, 0, 0, P, (long)maxp * P};
-    const WSegB stp{tp, P, 0, (long)W * P, P, 0, pris}, shp{hp, P, tp ? P : 0, (long)W * P, P, 0, pris};
-    const WSegB sh1{wh1, n0, 0, 0, 0, n0, (long)maxp * n0}, sh2{wh2, n1, 0, 0, 0, n1, (long)maxp * n1};
+    const long bufs = (long)(H + 2 * pad) * Wp * M, gps = (long)a.maxp() * P;        // image strides of buf and of wgp
     for (int t = 0; t < W + 3 * (H - 1); ++t) {
         int h0, np;
-        wave_range_hd(t, H, W, h0, np);
+        wave_range(t, H, W, h0, np);
         if (np <= 0) continue;                   // W < 3: steps between two rows hold no position
-        const int total = G * np;
-        const int gy = total < WAVE_ROWS_B ? total : WAVE_ROWS_B;
-        hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(P, 4 * WAVE_R), gy), dim3(256), 0, st, w_ctx, ld_ctx, b_ctx, c0, c1, c2, wctx, P, (long)maxp * P, P,
-                           0, 0.f, t, H, W, G);
-        if (tp)
-            hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(n0, 4 * WAVE_R), gy), dim3(256), 0, st, w0, ld0, b0, stp, shp, sctx, wh1, n0, (long)maxp * n0, n0,
-                               (int)STEM_ACT_LRELU, slope, t, H, W, G);
-        else
-            hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(n0, 4 * WAVE_R), gy), dim3(256), 0, st, w0, ld0, b0, shp, sctx, none, wh1, n0, (long)maxp * n0, n0,
-                               (int)STEM_ACT_LRELU, slope, t, H, W, G);
-        hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(n1, 4 * WAVE_R), gy), dim3(256), 0, st, w1, ld1, b1, sh1, none, none, wh2, n1, (long)maxp * n1, n1,
-                           (int)STEM_ACT_LRELU, slope, t, H, W, G);
-        hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(P, 4 * WAVE_R), gy), dim3(256), 0, st, w2, ld2, b2, sh2, none, none, wgp, P, (long)maxp * P, P,
-                           0, 0.f, t, H, W, G);
-        hipLaunchKernelGGL(ar_finish_encode_wave_batch_kernel, dim3(cdiv(total * M, 256)), dim3(256), 0, st, wgp, (long)maxp * P, table, T, scale_bound,
+        wave_step_products(a, st, t, np);
+        hipLaunchKernelGGL(ar_finish_encode_wave_batch_kernel, dim3(cdiv(G * np * M, 256)), dim3(256), 0, st, wgp, gps, table, T, scale_bound,
                            buf, bufs, sym, idx, M, t, H, W, Wp, pad, G);
     }
     STEM_LAUNCH_CHECK("ar_encode_batch");
@@ -828,16 +808,8 @@ STEM_EXPORT int stem_ar_encode_batch(const float *w_ctx, int ld_ctx, const float
 // steps, H * W, and that count belongs to the order of the symbols in the stream, not to the model: coded step by step (t = w + 3h, rows
 // ascending inside a step, channels inside a position) the decoder needs W + 3(H-1) host round trips -- 321 instead of 8160 for a 1080p
 // frame -- and every input of the encoder's wavefront products is already decoded when step t starts.  So the decoder below runs the
-// encoder's own launches (gemv3_wave_batch_kernel with stem_ar_encode_batch's grids): no float can differ from the encoder's.
+// encoder's own launches (wave_step_products, the function stem_ar_encode_batch calls): no float can differ from the encoder's.
 namespace {
-
-// positions in steps 0 .. t-1: row h' holds min(max(t - 3h', 0), Wd) of them
-__host__ __device__ __forceinline__ long wave_positions_before(int t, int H, int Wd)
-{
-    long n = 0;
-    for (int h = 0; h < H && 3 * h < t; ++h) n += t - 3 * h < Wd ? t - 3 * h : Wd;
-    return n;
-}
 
 // one workgroup per raster position and image: the M symbols and the M indexes of the position move to its wavefront rank
 __global__ __launch_bounds__(64) void ar_to_wave_order_kernel(const int32_t *sym_r, const int32_t *idx_r, int32_t *sym_w, int32_t *idx_w,
@@ -846,7 +818,7 @@ __global__ __launch_bounds__(64) void ar_to_wave_order_kernel(const int32_t *sym
     const int pos = blockIdx.x, g = blockIdx.y;
     const int h = pos / Wd, w = pos - h * Wd, t = w + 3 * h;
     int h0, np;
-    wave_range_hd(t, H, Wd, h0, np);
+    wave_range(t, H, Wd, h0, np);
     const size_t img = (size_t)g * H * Wd * M;
     const size_t src = img + (size_t)pos * M, dst = img + (size_t)(wave_positions_before(t, H, Wd) + (h - h0)) * M;
     for (int c = threadIdx.x; c < M; c += blockDim.x) {
@@ -859,31 +831,19 @@ __global__ __launch_bounds__(64) void ar_to_wave_order_kernel(const int32_t *sym
 __global__ void ar_index_wave_batch_kernel(const float *gp, long gps, const float *table, int T, float scale_bound, int32_t *idx, long idxs,
                                            int M, int t, int H, int Wd, int G)
 {
-    int h0, np;
-    wave_range_hd(t, H, Wd, h0, np);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= G * np * M) return;
-    const int j = i / M, c = i - j * M;
-    const int g = j / np, p = j - g * np;
-    const float s = fmaxf(gp[(size_t)g * gps + (size_t)p * 2 * M + c], scale_bound);
-    int k = T - 1;
-    for (int q = 0; q < T - 1; ++q) k -= (s <= table[q]) ? 1 : 0;
-    idx[(size_t)g * idxs + (size_t)p * M + c] = k;
+    WaveElem e;
+    if (!wave_elem(blockIdx.x * blockDim.x + threadIdx.x, t, H, Wd, M, G, e)) return;
+    idx[(size_t)e.g * idxs + (size_t)e.p * M + e.c] = scale_index(gp[(size_t)e.g * gps + (size_t)e.p * 2 * M + e.c], scale_bound, table, T);
 }
 
 // step t of G images: buffer <- symbol + mean (symbols from the pinned mailbox, means from the step's wgp)
 __global__ void ar_finish_decode_wave_batch_kernel(const float *gp, long gps, const int32_t *sym, long syms, float *buf, long bufs, int M,
                                                    int t, int H, int Wd, int Wp, int pad, int G)
 {
-    int h0, np;
-    wave_range_hd(t, H, Wd, h0, np);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= G * np * M) return;
-    const int j = i / M, c = i - j * M;
-    const int g = j / np, p = j - g * np;
-    const int h = h0 + p, w = t - 3 * h;
-    float *pix = buf + (size_t)g * bufs + ((size_t)(h + pad) * Wp + (w + pad)) * M;
-    pix[c] = (float)sym[(size_t)g * syms + (size_t)p * M + c] + gp[(size_t)g * gps + (size_t)p * 2 * M + M + c];
+    WaveElem e;
+    if (!wave_elem(blockIdx.x * blockDim.x + threadIdx.x, t, H, Wd, M, G, e)) return;
+    float *pix = buf + (size_t)e.g * bufs + ((size_t)(e.h + pad) * Wp + (e.w + pad)) * M;
+    pix[e.c] = dequantise(sym[(size_t)e.g * syms + (size_t)e.p * M + e.c], gp[(size_t)e.g * gps + (size_t)e.p * 2 * M + M + e.c]);
 }
 
 }   // namespace
@@ -907,66 +867,40 @@ STEM_EXPORT int stem_ar_decode_wave_batch(const float *w_ctx, int ld_ctx, const 
                                           int32_t *idx_host, int32_t *sym_host, stem_wave_symbol_decoder_fn decode, void *const *decs,
                                           const int32_t *cdfs, int ncdf, int cdf_stride, const int32_t *sizes, const int32_t *offsets, void *stream)
 {
-    STEM_CHECK_ARG(w_ctx && b_ctx && w0 && b0 && w1 && b1 && w2 && b2 && buf && hp && wctx && wh1 && wh2 && wgp && table && idx_host && sym_host &&
-                   decode && decs, "stem_ar_decode_wave_batch: null pointer");
-    STEM_CHECK_ARG(G >= 1, "stem_ar_decode_wave_batch: at least one image per call, got %d", G);
-    static_assert(WAVE_R == 4, "the size check below is what keeps a wavefront's WAVE_R rows inside each matrix (2M, n0, n1)");
-    STEM_CHECK_ARG(H > 0 && W > 0 && M > 0 && M % 4 == 0 && n0 > 0 && n1 > 0 && n0 % 4 == 0 && n1 % 4 == 0 && ld_ctx % 4 == 0 && ld0 % 4 == 0 &&
-                   ld1 % 4 == 0 && ld2 % 4 == 0 && T >= 1 && pad == 2, "stem_ar_decode_wave_batch: bad sizes");
-    STEM_CHECK_ARG(aligned16(w_ctx) && aligned16(w0) && aligned16(w1) && aligned16(w2) && aligned16(buf) && aligned16(tp) && aligned16(hp) &&
-                   aligned16(wctx) && aligned16(wh1) && aligned16(wh2) && aligned16(wgp), "stem_ar_decode_wave_batch: weights, buf, tp, hp and scratch must be 16-byte aligned");
-    STEM_CHECK_ARG((((uintptr_t)idx_host | (uintptr_t)sym_host) & 3) == 0, "stem_ar_decode_wave_batch: the mailboxes must be 4-byte aligned");
-    const int maxp = H < (W + 2) / 3 ? H : (W + 2) / 3;
-    STEM_CHECK_ARG((long)G * maxp * M <= 0x7fffffffL, "stem_ar_decode_wave_batch: G * positions per step * M = %ld does not fit an int", (long)G * maxp * M);
+    const WaveBatchArgs a{w_ctx, ld_ctx, b_ctx, w0, ld0, b0, n0, w1, ld1, b1, n1, w2, ld2, b2, buf, G, H, W, M, pad, tp, hp,
+                          wctx, wh1, wh2, wgp, table, T, scale_bound, slope};
+    if (int rc = wave_batch_check("stem_ar_decode_wave_batch", a, idx_host && sym_host && decode && decs,
+                                  (((uintptr_t)idx_host | (uintptr_t)sym_host) & 3) == 0))
+        return rc;
     for (int g = 0; g < G; ++g) STEM_CHECK_ARG(decs[g], "stem_ar_decode_wave_batch: no decoder handle for image %d", g);
     hipStream_t st = (hipStream_t)stream;
     const int P = 2 * M, Wp = W + 2 * pad;
-    const long row = (long)Wp * M;
-    const long bufs = (long)(H + 2 * pad) * row, pris = (long)H * W * P;            // image strides of buf and of tp / hp
-    const long gps = (long)maxp * P, boxs = (long)maxp * M;                          // ... of wgp and of the mailboxes
-    static const bool prof = getenv("STEM_AR_PROFILE") != nullptr;         // where a step's time goes (launch / wait / host coder)
-    double t_launch = 0, t_wait = 0, t_host = 0;
-    auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    // the segments of stem_ar_encode_batch
-    const WSegB none{nullptr, 0, 0, 0, 0, 0, 0};
-    const WSegB c0{buf, 5 * M, 0, row, M, 0, bufs}, c1{buf + row, 5 * M, 5 * M, row, M, 0, bufs}, c2{buf + 2 * row, 2 * M, 10 * M, row, M, 0, bufs};
-    const WSegB sctx{wctx, P, tp ? 2 * P : P, 0, 0, P, (long)maxp * P};
-    const WSegB stp{tp, P, 0, (long)W * P, P, 0, pris}, shp{hp, P, tp ? P : 0, (long)W * P, P, 0, pris};
-    const WSegB sh1{wh1, n0, 0, 0, 0, n0, (long)maxp * n0}, sh2{wh2, n1, 0, 0, 0, n1, (long)maxp * n1};
+    const long bufs = (long)(H + 2 * pad) * Wp * M;                                  // image stride of buf
+    const long gps = (long)a.maxp() * P, boxs = (long)a.maxp() * M;                  // ... of wgp and of the mailboxes
+    StepTimer tm;
+    // buffer <- symbol + mean for the step whose symbols sit in the mailbox
+    auto commit = [&](int t) {
+        int h0, np;
+        wave_range(t, H, W, h0, np);
+        hipLaunchKernelGGL(ar_finish_decode_wave_batch_kernel, dim3(cdiv(G * np * M, 256)), dim3(256), 0, st, wgp, gps, sym_host, boxs, buf, bufs, M,
+                           t, H, W, Wp, pad, G);
+    };
     int t_prev = -1, steps = 0;               // the step whose symbols sit in the mailbox, not yet committed to buf
     for (int t = 0; t < W + 3 * (H - 1); ++t) {
         int h0, np;
-        wave_range_hd(t, H, W, h0, np);
+        wave_range(t, H, W, h0, np);
         if (np <= 0) continue;                   // W < 3: steps between two rows hold no position
-        const double ta = prof ? now() : 0;
-        const int total = G * np;
-        const int gy = total < WAVE_ROWS_B ? total : WAVE_ROWS_B;
-        if (t_prev >= 0) {
-            int hp0, npp;
-            wave_range_hd(t_prev, H, W, hp0, npp);
-            hipLaunchKernelGGL(ar_finish_decode_wave_batch_kernel, dim3(cdiv(G * npp * M, 256)), dim3(256), 0, st, wgp, gps, sym_host, boxs, buf, bufs, M,
-                               t_prev, H, W, Wp, pad, G);
-        }
-        hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(P, 4 * WAVE_R), gy), dim3(256), 0, st, w_ctx, ld_ctx, b_ctx, c0, c1, c2, wctx, P, (long)maxp * P, P,
-                           0, 0.f, t, H, W, G);
-        if (tp)
-            hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(n0, 4 * WAVE_R), gy), dim3(256), 0, st, w0, ld0, b0, stp, shp, sctx, wh1, n0, (long)maxp * n0, n0,
-                               (int)STEM_ACT_LRELU, slope, t, H, W, G);
-        else
-            hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(n0, 4 * WAVE_R), gy), dim3(256), 0, st, w0, ld0, b0, shp, sctx, none, wh1, n0, (long)maxp * n0, n0,
-                               (int)STEM_ACT_LRELU, slope, t, H, W, G);
-        hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(n1, 4 * WAVE_R), gy), dim3(256), 0, st, w1, ld1, b1, sh1, none, none, wh2, n1, (long)maxp * n1, n1,
-                           (int)STEM_ACT_LRELU, slope, t, H, W, G);
-        hipLaunchKernelGGL(gemv3_wave_batch_kernel, dim3(cdiv(P, 4 * WAVE_R), gy), dim3(256), 0, st, w2, ld2, b2, sh2, none, none, wgp, P, gps, P,
-                           0, 0.f, t, H, W, G);
-        hipLaunchKernelGGL(ar_index_wave_batch_kernel, dim3(cdiv(total * M, 256)), dim3(256), 0, st, wgp, gps, table, T, scale_bound, idx_host, boxs, M,
+        tm.at(0);
+        if (t_prev >= 0) commit(t_prev);
+        wave_step_products(a, st, t, np);        // the encoder's launches
+        hipLaunchKernelGGL(ar_index_wave_batch_kernel, dim3(cdiv(G * np * M, 256)), dim3(256), 0, st, wgp, gps, table, T, scale_bound, idx_host, boxs, M,
                            t, H, W, G);
-        const double tb = prof ? now() : 0;
+        tm.at(1);
         if (hipStreamSynchronize(st) != hipSuccess) {
             stem_set_error("stem_ar_decode_wave_batch: device error at step %d: %s", t, hipGetErrorString(hipGetLastError()));
             return -2;
         }
-        const double tc = prof ? now() : 0;
+        tm.at(2);
         for (int g = 0; g < G; ++g)
             if (int rc = decode(decs[g], idx_host + (size_t)g * boxs, (size_t)np * M, cdfs, ncdf, cdf_stride, sizes, offsets, sym_host + (size_t)g * boxs)) {
                 stem_set_error("stem_ar_decode_wave_batch: host symbol decoder failed (%d) for image %d at step %d", rc, g, t);
@@ -974,18 +908,12 @@ STEM_EXPORT int stem_ar_decode_wave_batch(const float *w_ctx, int ld_ctx, const 
             }
         t_prev = t;
         ++steps;
-        if (prof) {
-            const double td = now();
-            t_launch += tb - ta; t_wait += tc - tb; t_host += td - tc;
-        }
+        tm.step_done();
     }
-    if (prof)
+    if (tm.on)
         fprintf(stderr, "[ar decode wave batch] G=%d steps=%d positions=%d: launch %.1f us, wait %.1f us, host coder %.1f us per step\n", G, steps, H * W,
-                t_launch / steps, t_wait / steps, t_host / steps);
-    int hp0, npp;
-    wave_range_hd(t_prev, H, W, hp0, npp);
-    hipLaunchKernelGGL(ar_finish_decode_wave_batch_kernel, dim3(cdiv(G * npp * M, 256)), dim3(256), 0, st, wgp, gps, sym_host, boxs, buf, bufs, M, t_prev, H, W,
-                       Wp, pad, G);
+                tm.launch / steps, tm.wait / steps, tm.host / steps);
+    commit(t_prev);
     STEM_LAUNCH_CHECK("ar_decode_wave_batch");
     if (hipStreamSynchronize(st) != hipSuccess) {             // the last step read the mailbox: the caller may free it on return
         stem_set_error("stem_ar_decode_wave_batch: device error after the last step: %s", hipGetErrorString(hipGetLastError()));

@@ -18,13 +18,13 @@
 //
 // Arithmetic: every output row is one wavefront's dot product in the order of gemv3_decode_kernel (segments in order, columns
 // lane * 4 + 256 t ascending, xor-shuffle reduction, bias, leaky ReLU: the canonical product stated in
-// include/stem_ar_batch.h), compiled without FMA contraction like ar.hip -- the
+// include/stem_ar_batch.h; dot4, wave_sum and finish of ar_canon.h), compiled without FMA contraction like ar.hip -- the
 // entropy parameters, hence symbols and bytes, are those of the per-position loop and of the encoder.
 #include <chrono>
 #include <mutex>
 #include <vector>
 
-#include "stem_common.h"
+#include "ar_canon.h"
 
 #pragma clang fp contract(off)
 
@@ -85,7 +85,6 @@ constexpr int WL_FLOATS = (NT / 64) * RC * TCA * 64 * 4;               // LDS im
 constexpr int XA_FLOATS = 2048, XP_FLOATS = 1024, XV_FLOATS = 768;     // staging: rows-above window (10 M) and tp | hp for the look-ahead; the vector of the current product
 constexpr int ARP_LDS = (WL_FLOATS + XA_FLOATS + XP_FLOATS + XV_FLOATS) * 4;
 
-__device__ inline float dot4(const f32x4 xv, const f32x4 wv) { return xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3]; }
 // (a tagged word's value goes through a scalar before it is reinterpreted: hipcc of ROCm 7.2 reads the wrong element when
 // __builtin_bit_cast is applied directly to an element of an ext-vector -- tools/debug/probe/vec_even_elements.hip)
 
@@ -99,13 +98,6 @@ __device__ inline void stage512(float *dst, const float *src, int n)
     const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(src), 0, n * 4, 0x00020000);
     for (int i = threadIdx.x * 4; i < n; i += NT * 4)
         *reinterpret_cast<f32x4 *>(dst + i) = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, i * 4, 0, COHERENT ? 16 : 0));
-}
-
-__device__ inline float wave_sum_xor(float acc)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    return acc;
 }
 
 __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpArgs a)
@@ -351,7 +343,7 @@ __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpAr
 #pragma unroll
                 for (int t = 0; t < TCL; ++t)
                     acc += dot4(x[t], wcl[r][t]);
-                acc = wave_sum_xor(acc);
+                acc = wave_sum(acc);
                 if (lane == 0 && n < P) put(ctxw + n, pack(acc + bc[r], tag));
             }
         }
@@ -369,12 +361,8 @@ __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpAr
 #pragma unroll
                 for (int t = 0; t < T0C; ++t)
                     acc += dot4(x[t], w0c[r][t]);
-                acc = wave_sum_xor(acc);
-                if (lane == 0 && n < a.n0) {
-                    float v = acc + b0v[r];
-                    v = v > 0.f ? v : v * a.slope;
-                    put(h1w + n, pack(v, tag));
-                }
+                acc = wave_sum(acc);
+                if (lane == 0 && n < a.n0) put(h1w + n, pack(finish(acc, b0v[r], STEM_ACT_LRELU, a.slope), tag));
             }
         }
         // ---- h2 = lrelu(b_1 + W_1 . h1)
@@ -391,12 +379,8 @@ __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpAr
 #pragma unroll
                 for (int t = 0; t < T1; ++t)
                     acc += dot4(x[t], w1[r][t]);
-                acc = wave_sum_xor(acc);
-                if (lane == 0 && n < a.n1) {
-                    float v = acc + b1v[r];
-                    v = v > 0.f ? v : v * a.slope;
-                    put(h2w + n, pack(v, tag));
-                }
+                acc = wave_sum(acc);
+                if (lane == 0 && n < a.n1) put(h2w + n, pack(finish(acc, b1v[r], STEM_ACT_LRELU, a.slope), tag));
             }
         }
         // ---- gp = b_2 + W_2 . h2 (scales | means) and the scales' CDF indexes
@@ -413,11 +397,13 @@ __global__ __launch_bounds__(NT, 1) void ar_decode_persistent_kernel(const ArpAr
 #pragma unroll
                 for (int t = 0; t < T2; ++t)
                     acc += dot4(x[t], w2[r][t]);
-                acc = wave_sum_xor(acc);                 // every lane holds the sum
+                acc = wave_sum(acc);                 // every lane holds the sum
                 const float v = acc + b2v[r];
                 // index = #(table[:-1] < scale) (entropy_models.py:598-604): every lane compares the scale with ITS table entry
                 const float sc = fmaxf(v, a.bound);
                 int k = a.T - 1 - __builtin_popcountll(__ballot(lane < a.T - 1 && sc <= tb));
+                // (the ballot is a different algorithm for scale_index's integer, chosen for the dependent path; the tail below is for tables
+                // beyond 65 levels -- the test tables have 8 entries and do not reach it)
                 for (int t = 64; t < a.T - 1; ++t) k -= (sc <= a.table[t]) ? 1 : 0;            // tables beyond 65 levels
                 if (lane == 0 && n < P) {
                     put(gpw + n, pack(v, tag));

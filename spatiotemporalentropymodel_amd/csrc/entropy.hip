@@ -2,6 +2,7 @@
 // quantisation, rate reduction, counter-based noise.  All HBM/latency-bound elementwise work; every
 // multi-pass torch expression of the reference (entropy_models.py:388-452, 570-596) is one kernel.
 #include "stem_common.h"
+#include "ar_canon.h"       // scale_index, for build_indexes_kernel
 
 namespace {
 
@@ -456,10 +457,7 @@ __global__ void build_indexes_kernel(const float *scales, int lds, const float *
     if (i >= npix * C) return;
     const size_t pix = i / C;
     const int c = (int)(i - pix * C);
-    const float s = fmaxf(scales[pix * lds + c], sb);
-    int k = T - 1;
-    for (int t = 0; t < T - 1; ++t) k -= (s <= table[t]) ? 1 : 0;
-    idx[i] = k;
+    idx[i] = scale_index(scales[pix * lds + c], sb, table, T);
 }
 
 inline unsigned nblk(size_t n) { return (unsigned)cdivz(n, 256); }

@@ -8,9 +8,9 @@
 // row of TC + 1 words: the NHWC phase has a wave's 64 lanes on 64 consecutive words of one row, the NCHW phase has them on one
 // column, TC + 1 = 65 words apart, i.e. 1 (mod 32) and 1 (mod 64): conflict-free under either bank modulus of the b32 accesses.
 //
-// Arithmetic: sym = (int32) rintf(y - m) (two fp32 operations, ties to even), y_hat = (float) sym + m (one rounding), the
-// scale-to-index search of build_indexes_kernel (entropy.hip).  Compiled without contraction like the products of ar.hip.
-#include "stem_common.h"
+// Arithmetic: sym = (int32) rint(y - m) (two fp32 operations, ties to even), y_hat = (float) sym + m (one rounding) and the
+// scale-to-index search, all three as ar_canon.h states them.  Compiled without contraction like the products of ar.hip.
+#include "ar_canon.h"
 #include "../../include/stem_ar_batch.h"
 
 #pragma clang fp contract(off)
@@ -44,20 +44,14 @@ __global__ __launch_bounds__(NT) void symbols_pack_kernel(const float *__restric
             if (p >= HW) break;
             const size_t pix = b * (size_t)HW + p;
             if (want_sym) {
-                float v = y[pix * ldy + c];
-                if (means) v = v - means[pix * ldm + c];
-                else if (chan_means) v = v - cm;
-                s_sym[pp * TROW + lane] = (int32_t)rintf(v);
+                const float v = y[pix * ldy + c];
+                float q;
+                if (means) quantise(v, means[pix * ldm + c], q);
+                else if (chan_means) quantise(v, cm, q);
+                else q = round_ties_even(v);                  // no mean: no subtraction
+                s_sym[pp * TROW + lane] = (int32_t)q;
             }
-            if (want_idx) {
-                int k = c;
-                if (scales) {
-                    const float s = fmaxf(scales[pix * lds + c], sb);
-                    k = T - 1;
-                    for (int t = 0; t < T - 1; ++t) k -= (s <= table[t]) ? 1 : 0;
-                }
-                s_idx[pp * TROW + lane] = k;
-            }
+            if (want_idx) s_idx[pp * TROW + lane] = scales ? scale_index(scales[pix * lds + c], sb, table, T) : c;
         }
     }
     __syncthreads();
@@ -101,10 +95,8 @@ __global__ __launch_bounds__(NT) void symbols_unpack_kernel(const int32_t *__res
             const int q = p0 + pp;
             if (q >= HW) break;
             const size_t pix = b * (size_t)HW + q;
-            float v = (float)s_sym[pp * TROW + lane];
-            if (means) v = v + means[pix * ldm + c];
-            else if (chan_means) v = v + cm;
-            y_hat[pix * ldo + c] = v;
+            const int32_t s = s_sym[pp * TROW + lane];
+            y_hat[pix * ldo + c] = means ? dequantise(s, means[pix * ldm + c]) : chan_means ? dequantise(s, cm) : (float)s;      // no mean: no addition
         }
     }
 }

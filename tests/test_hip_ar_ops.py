@@ -1,5 +1,5 @@
-"""GPU, op level: every form of the coding loop's product, of its scale-to-index search and of its quantisation (csrc/ar.hip,
-csrc/ar_persistent.hip) against tests/ar_ref.py, the numpy statement of the canonical product of include/stem_ar_batch.h, which
+"""GPU, op level: every kernel form of the coding loop's product and every kernel that calls its scale-to-index search and its
+quantisation (csrc/ar.hip, csrc/ar_persistent.hip; the arithmetic itself is csrc/ar_canon.h) against tests/ar_ref.py, the numpy statement of the canonical product of include/stem_ar_batch.h, which
 tests/test_ar_ref.py pins on the CPU.  Every comparison is of bits.  Outputs are allocated with a sentinel and whatever a call does
 not own must keep it: rows >= N, the ring of the latent buffer, symbols and indexes of other images.  Mailboxes the codec keeps in
 pinned host memory are pinned here.

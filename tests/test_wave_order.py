@@ -16,7 +16,7 @@ GEOMETRIES = [(1, 1), (1, 7), (5, 1), (4, 6), (7, 5), (3, 16), (68, 120)]
 
 
 def _wave_range(t, H, W):
-    """wave_range of csrc/ar.hip, restated: rows h0 .. h0 + np - 1 hold the positions of step t"""
+    """wave_range of csrc/ar_canon.h, restated: rows h0 .. h0 + np - 1 hold the positions of step t"""
     lo = t - (W - 1)
     lo = (lo + 2) // 3 if lo > 0 else 0
     hi = min(t // 3, H - 1)
