@@ -19,7 +19,7 @@ def install_compressai_alias():
     from . import entropy_models, layers, ops, zoo
     import importlib
 
-    from .models import priors, spatiotemporalpriors, stem_utils, utils
+    from .models import priors, spatiotemporalpriors, stem_utils, utils, waseda
     stem_roi = importlib.import_module(".models.stem_roi", __name__)      # the package attribute of that name is the class
 
     root = types.ModuleType("compressai")
@@ -33,13 +33,13 @@ def install_compressai_alias():
     cxx.pmf_to_quantized_cdf = lambda pmf, precision: entropy_models.pmf_to_quantized_cdf(pmf, precision).tolist()
     models = types.ModuleType("compressai.models")
     models.__path__ = []
-    for mod in (priors, spatiotemporalpriors, stem_roi, stem_utils):
+    for mod in (priors, spatiotemporalpriors, stem_roi, stem_utils, waseda):
         for name in mod.__all__:
             setattr(models, name, getattr(mod, name))
     table = {"compressai": root, "compressai.ans": ans, "compressai._CXX": cxx, "compressai.zoo": zoo,
              "compressai.models": models, "compressai.models.priors": priors, "compressai.models.utils": utils,
              "compressai.models.spatiotemporalpriors": spatiotemporalpriors, "compressai.models.stem_roi": stem_roi,
-             "compressai.models.stem_utils": stem_utils, "compressai.layers": layers,
+             "compressai.models.stem_utils": stem_utils, "compressai.models.waseda": waseda, "compressai.layers": layers,
              "compressai.entropy_models": entropy_models, "compressai.ops": ops}
     for k, v in table.items():
         sys.modules[k] = v

@@ -121,10 +121,23 @@ class _ARContext:
         self.w_ctx = torch.empty((2 * M, 12 * M), device=device, dtype=torch.float32)
         F._chk(_lib.hip().stem_pack_ctx_gemv(w.data_ptr(), self.w_ctx.data_ptr(), 2 * M, M, F._stream()))
         self.b_ctx = m.context_prediction.bias.detach()
-        self.w0 = m.EPM[0].weight.detach().reshape(m.EPM[0].out_channels, -1).contiguous()
-        self.w1 = m.EPM[2].weight.detach().reshape(m.EPM[2].out_channels, -1).contiguous()
-        self.w2 = m.EPM[4].weight.detach().reshape(m.EPM[4].out_channels, -1).contiguous()
-        self.b0, self.b1, self.b2 = m.EPM[0].bias.detach(), m.EPM[2].bias.detach(), m.EPM[4].bias.detach()
+        # The coding kernels take hidden widths that are multiples of 4.  M * 10 // 3 and M * 8 // 3 are that for M = 96, 192, 320 but
+        # not for the M = N = 128 (426, 341) or 64 of the cheng2020 models: their two hidden layers get zero rows (and the next
+        # layer zero columns) up to the next multiple.  A padded unit is lrelu(0) = 0 and meets a zero weight: every real sum keeps
+        # its terms and their order.  Widths that are multiples of 4 already are left as they are.
+        n0, n1 = (-(-m.EPM[i].out_channels // 4) * 4 for i in (0, 2))
+
+        def padded(t, *shape):
+            t = t.detach().reshape(t.shape[0], -1) if t.dim() == 4 else t.detach()
+            if tuple(t.shape) == shape:
+                return t.contiguous()
+            out = torch.zeros(shape, device=t.device, dtype=t.dtype)
+            out[tuple(slice(0, s) for s in t.shape)] = t
+            return out
+        self.w0 = padded(m.EPM[0].weight, n0, m.EPM[0].in_channels)
+        self.w1 = padded(m.EPM[2].weight, n1, n0)
+        self.w2 = padded(m.EPM[4].weight, m.EPM[4].out_channels, n1)
+        self.b0, self.b1, self.b2 = padded(m.EPM[0].bias, n0), padded(m.EPM[2].bias, n1), m.EPM[4].bias.detach()
         self.ctx = torch.empty(2 * M, device=device)
         self.h1 = torch.empty(self.w0.shape[0], device=device)
         self.h2 = torch.empty(self.w1.shape[0], device=device)

@@ -1048,6 +1048,84 @@ def sft_bwd(x, gamma, out, dout, slope=1.0):
     return dx, dg, db
 
 
+def _nhwc_arg(t, name):
+    """(pointer, pixel pitch) of an NHWC-memory tensor or channel-slice view"""
+    _require_cuda(t)
+    ld = nhwc_ld(t)
+    if ld is None:
+        raise RuntimeError(f"{name} must be an NHWC-memory tensor, got strides {tuple(t.stride())} for shape {tuple(t.shape)}")
+    return t.data_ptr(), ld
+
+
+def pixel_shuffle(x, r, slope=1.0, addend=None, out=None):
+    """nn.PixelShuffle(r) on NHWC memory with the blocks' followers folded in (csrc/resblock.hip):
+    out[b, c, h*r+i, w*r+j] = act(x[b, c*r*r + i*r + j, h, w]) (+ addend), act = LeakyReLU(slope), slope 1.0 = none.
+    x and addend may be channel-slice views."""
+    B, Cin, H, W = x.shape
+    r = int(r)
+    if r < 1 or Cin % (r * r):
+        raise ValueError(f"pixel_shuffle: {Cin} channels are not a multiple of r * r = {r * r}")
+    Cc = Cin // (r * r)
+    if out is None:
+        out = empty_nhwc(B, Cc, H * r, W * r, x.device)
+    if addend is not None and tuple(addend.shape) != tuple(out.shape):
+        raise ValueError(f"pixel_shuffle: addend {tuple(addend.shape)} does not match the output {tuple(out.shape)}")
+    (xp, ldx), (op, ldo) = _nhwc_arg(x, "pixel_shuffle: x"), _nhwc_arg(out, "pixel_shuffle: out")
+    ap, lda = _nhwc_arg(addend, "pixel_shuffle: addend") if addend is not None else (0, 0)
+    _chk(_lib.hip().stem_pixel_shuffle_fwd(xp, ldx, ap, lda, op, ldo, B, H, W, Cc, r, slope, _stream()))
+    return out
+
+
+def pixel_shuffle_backward(dout, r, x=None, slope=1.0):
+    """gradient of pixel_shuffle with respect to x: x is the forward input, needed only where slope != 1; the addend's gradient is dout"""
+    B, Cc, Ho, Wo = dout.shape
+    r = int(r)
+    H, W = Ho // r, Wo // r
+    din = empty_nhwc(B, Cc * r * r, H, W, dout.device)
+    dp, ldo = _nhwc_arg(dout, "pixel_shuffle_backward: dout")
+    xp, ldx = _nhwc_arg(x, "pixel_shuffle_backward: x") if x is not None else (0, 0)
+    _chk(_lib.hip().stem_pixel_shuffle_bwd(xp, ldx, dp, ldo, din.data_ptr(), nhwc_ld(din), B, H, W, Cc, r, slope, _stream()))
+    return din
+
+
+def add_act(a, b, slope=0.0):
+    """act(a + b), act = LeakyReLU(slope), slope 0 = ReLU (ResidualUnit, compressai/layers/layers.py:191-196)"""
+    B, Cc, H, W = a.shape
+    assert tuple(b.shape) == tuple(a.shape)
+    out = empty_nhwc(B, Cc, H, W, a.device)
+    (ap, lda), (bp, ldb) = _nhwc_arg(a, "add_act: a"), _nhwc_arg(b, "add_act: b")
+    _chk(_lib.hip().stem_add_act_fwd(ap, lda, bp, ldb, out.data_ptr(), Cc, B * H * W, Cc, slope, _stream()))
+    return out
+
+
+def add_act_backward(out, dout, slope=0.0):
+    """da = db = dout * (out > 0 ? 1 : slope): one tensor serves both"""
+    B, Cc, H, W = out.shape
+    g = empty_nhwc(B, Cc, H, W, out.device)
+    (op, ldo), (dp, ldd) = _nhwc_arg(out, "add_act_backward: out"), _nhwc_arg(dout, "add_act_backward: dout")
+    _chk(_lib.hip().stem_add_act_bwd(op, ldo, dp, ldd, g.data_ptr(), Cc, B * H * W, Cc, slope, _stream()))
+    return g
+
+
+def gate(a, b, x):
+    """a * sigmoid(b) + x (AttentionBlock.forward, compressai/layers/layers.py:207-213)"""
+    B, Cc, H, W = a.shape
+    assert tuple(b.shape) == tuple(a.shape) == tuple(x.shape)
+    out = empty_nhwc(B, Cc, H, W, a.device)
+    (ap, lda), (bp, ldb), (xp, ldx) = _nhwc_arg(a, "gate: a"), _nhwc_arg(b, "gate: b"), _nhwc_arg(x, "gate: x")
+    _chk(_lib.hip().stem_gate_fwd(ap, lda, bp, ldb, xp, ldx, out.data_ptr(), Cc, B * H * W, Cc, _stream()))
+    return out
+
+
+def gate_backward(a, b, dout):
+    """-> (da, db) = (dout * s, dout * a * s * (1 - s)), s = sigmoid(b); the gradient of x is dout itself"""
+    B, Cc, H, W = a.shape
+    da, db = empty_nhwc(B, Cc, H, W, a.device), empty_nhwc(B, Cc, H, W, a.device)
+    (ap, lda), (bp, ldb), (dp, ldd) = _nhwc_arg(a, "gate_backward: a"), _nhwc_arg(b, "gate_backward: b"), _nhwc_arg(dout, "gate_backward: dout")
+    _chk(_lib.hip().stem_gate_bwd(ap, lda, bp, ldb, dp, ldd, da.data_ptr(), Cc, db.data_ptr(), Cc, B * H * W, Cc, _stream()))
+    return da, db
+
+
 def avgpool(x, Ho, Wo):
     """adaptive_avg_pool2d for integer ratios (quality map -> feature resolution)."""
     B, Cc, H, W = x.shape

@@ -7,6 +7,8 @@ kernels through the C ABI -- and the one place that decides which kernel family 
   route / Route / Step       the kernel family of a convolution as a value; f16x3_same_shape: the shape rule engine.py shares
   cat / to_nchw / adaptive_avg_pool2d, the *Function classes      glue operations of the layer-wise models (stem_utils.py, stem_roi.py)
   bump_weight_epoch / weight_epoch / wgrad_side_stream / join_wgrad_stream      what optimisers and trainers synchronise with
+  PixelShuffleFunction / AddActFunction / GateFunction, and (re-exported from layers_residual.py) conv3x3, conv1x1, subpel_conv3x3,
+  ResidualBlock*, AttentionBlock, BlockSequential      the blocks of the cheng2020 models, compressai/layers/layers.py:50-213
 """
 from __future__ import annotations
 
@@ -475,6 +477,59 @@ class AddFunction(torch.autograd.Function):
         return dy, dy
 
 
+class PixelShuffleFunction(torch.autograd.Function):
+    """act(PixelShuffle(r)(x)) (+ addend) in one pass: the sub-pixel convolutions of compressai/layers/layers.py:55-59 with the
+    leaky ReLU / `out += identity` that follow them in ResidualBlockUpsample (layers.py:118-126); slope 1.0: no activation."""
+
+    @staticmethod
+    def forward(ctx, x, r, slope, addend):
+        xin = F.to_nhwc(x)
+        ctx.r, ctx.slope = int(r), float(slope)
+        ctx.save_for_backward(xin if ctx.slope != 1.0 else None)
+        return F.pixel_shuffle(xin, ctx.r, ctx.slope, None if addend is None else F.to_nhwc(addend))
+
+    @staticmethod
+    def backward(ctx, dout):
+        (xin,) = ctx.saved_tensors
+        dout = F.to_nhwc(dout)
+        dx = F.pixel_shuffle_backward(dout, ctx.r, xin, ctx.slope) if ctx.needs_input_grad[0] else None
+        return dx, None, None, (dout if ctx.needs_input_grad[3] else None)
+
+
+class AddActFunction(torch.autograd.Function):
+    """act(a + b), act = LeakyReLU(slope), slope 0 = ReLU: ResidualUnit's relu(conv(x) + x) (compressai/layers/layers.py:191-196)"""
+
+    @staticmethod
+    def forward(ctx, a, b, slope):
+        out = F.add_act(F.to_nhwc(a), F.to_nhwc(b), float(slope))
+        ctx.slope = float(slope)
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (out,) = ctx.saved_tensors
+        g = F.add_act_backward(out, F.to_nhwc(dout), ctx.slope)
+        return g, g, None
+
+
+class GateFunction(torch.autograd.Function):
+    """a * sigmoid(b) + x: AttentionBlock.forward (compressai/layers/layers.py:207-213); the sigmoid is recomputed in the backward pass"""
+
+    @staticmethod
+    def forward(ctx, a, b, x):
+        a, b = F.to_nhwc(a), F.to_nhwc(b)
+        ctx.save_for_backward(a, b)
+        return F.gate(a, b, F.to_nhwc(x))
+
+    @staticmethod
+    def backward(ctx, dout):
+        a, b = ctx.saved_tensors
+        dout = F.to_nhwc(dout)
+        da, db = F.gate_backward(a, b, dout)
+        return da, db, dout
+
+
 class ToNCHWFunction(torch.autograd.Function):
     """NHWC feature map -> contiguous NCHW tensor (the image handed back to the caller)."""
 
@@ -706,3 +761,7 @@ def deconv(in_channels, out_channels, kernel_size=5, stride=2):
     """compressai/models/utils.py:122-130"""
     return ConvTranspose2d(in_channels, out_channels, kernel_size=kernel_size, stride=stride,
                            output_padding=stride - 1, padding=kernel_size // 2)
+
+
+# the residual / sub-pixel / attention blocks of the cheng2020 models, built on the pieces above
+from .layers_residual import *  # noqa: E402,F401,F403
