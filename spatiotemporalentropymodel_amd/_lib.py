@@ -1,5 +1,5 @@
-"""ctypes loader for the three C-ABI libraries (include/stem_hip.h + include/stem_ar_batch.h + include/stem_blocks.h, include/stem_rans.h,
-include/stem_dp.h).
+"""ctypes loader for the three C-ABI libraries (include/stem_hip.h + include/stem_ar_batch.h + include/stem_blocks.h +
+include/stem_hyperprior.h, include/stem_rans.h, include/stem_dp.h).
 
 The headers are the single statement of the ABI: every prototype and descriptor structure below is read from them (_abi.py).
 
@@ -48,6 +48,8 @@ _HIP_PROTO, _HIP_SIG, _RESTYPE = _tables("stem_hip.h")
 _HIP_BATCH_PROTO, _HIP_BATCH_SIG, _ = _tables("stem_ar_batch.h")
 # libstem_hip.so's block kernels of the cheng2020 models (csrc/resblock.hip; not launch-tape entries either)
 _HIP_BLOCKS_PROTO, _HIP_BLOCKS_SIG, _ = _tables("stem_blocks.h")
+# libstem_hip.so's zero-mean likelihood kernels of the bmshj2018 models (csrc/hyperprior.hip; not launch-tape entries either)
+_HIP_HYPERPRIOR_PROTO, _HIP_HYPERPRIOR_SIG, _ = _tables("stem_hyperprior.h")
 _RANS_PROTO, _RANS_SIG, _RANS_RESTYPE = _tables("stem_rans.h")
 _DP_PROTO, _DP_SIG, _ = _tables("stem_dp.h")
 _STRUCTS = _abi.structs(_header("stem_hip.h"))
@@ -93,7 +95,10 @@ def hip():
             raise StemLibraryError(
                 f"{HIP_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the STEM kernels.")
-        _hip = _bind(_bind(_bind(C.CDLL(HIP_SO), _HIP_PROTO), _HIP_BATCH_PROTO), _HIP_BLOCKS_PROTO)
+        lib = C.CDLL(HIP_SO)
+        for protos in (_HIP_PROTO, _HIP_BATCH_PROTO, _HIP_BLOCKS_PROTO, _HIP_HYPERPRIOR_PROTO):
+            _bind(lib, protos)
+        _hip = lib
     return _hip
 
 
@@ -121,6 +126,10 @@ def declared_hip_batch_symbols():
 
 def declared_hip_block_symbols():
     return sorted(_HIP_BLOCKS_SIG)
+
+
+def declared_hip_hyperprior_symbols():
+    return sorted(_HIP_HYPERPRIOR_SIG)
 
 
 def dp():

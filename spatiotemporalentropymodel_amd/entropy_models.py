@@ -236,6 +236,32 @@ class _GCFunction(torch.autograd.Function):
         return dy, dgp[:, :Cc], dgp[:, Cc:], None, None, None
 
 
+class _GCScaleFunction(torch.autograd.Function):
+    """GaussianConditional.forward with means=None (entropy_models.py:570-596): one launch each way, no mean tensor, the noise
+    drawn inside the forward launch, the gradient arriving at `out` added inside the backward launch.  `noise`: what
+    EntropyModel._noise_slot returned (training) or None (eval: round)."""
+
+    @staticmethod
+    def forward(ctx, y, scales, noise, scale_bound, lik_bound):
+        y, sc = F.to_nhwc(y), F.to_nhwc(scales)
+        out, lik = F.gc_scale_forward(y, sc, "round" if noise is None else "noise", **(noise or {}), scale_bound=scale_bound,
+                                      lik_bound=lik_bound)
+        ctx.bounds = (scale_bound, lik_bound)
+        ctx.save_for_backward(out, sc)
+        return out, lik
+
+    @staticmethod
+    def backward(ctx, dout, dlik):
+        out, sc = ctx.saved_tensors
+        B, Cc, H, W = out.shape
+        dsc = F.empty_nhwc(B, Cc, H, W, out.device) if ctx.needs_input_grad[1] else None
+        dy = F.empty_nhwc(B, Cc, H, W, out.device) if ctx.needs_input_grad[0] else None
+        if dsc is not None or dy is not None:
+            F.gc_scale_backward(out, sc, F.to_nhwc(dlik), dscales=dsc, dy=dy, dout=None if dout is None or dy is None else F.to_nhwc(dout),
+                                scale_bound=ctx.bounds[0], lik_bound=ctx.bounds[1])
+        return dy, dsc, None, None, None
+
+
 # ----------------------------------------------------------------------------- modules
 class EntropyModel(nn.Module):
     def __init__(self, likelihood_bound=1e-9, entropy_coder=None, entropy_coder_precision=16):
@@ -630,9 +656,12 @@ class GaussianConditional(EntropyModel):
 
     def forward(self, inputs, scales, means=None):
         if means is None:
-            # entropy_models.py:570-596 with means=None: quantize(inputs) without an offset, likelihood of the values themselves --
-            # exactly what a zero mean computes (x - 0 and round(x - 0) + 0 are x and round(x) in fp32); the kernel takes the tensor
-            means = torch.zeros_like(inputs, memory_format=torch.preserve_format).detach()
+            # entropy_models.py:570-596 with means=None: quantize(inputs) without an offset, likelihood of the values themselves.  The
+            # zero-mean kernels compute what the mean kernels compute from a tensor of zeros, value for value and gradient bit for
+            # bit, except that an eval-mode round(-0.3) stays the reference's -0.0 (round(x - 0) + 0 made it +0.0).  The noise is
+            # drawn in the launch, from the stream coordinates _noise_like would have used.
+            noise = self._noise_slot(F.to_nhwc(inputs.detach())) if self.training else None
+            return _GCScaleFunction.apply(inputs, scales, noise, self._scale_bound, self._lik_bound if self.use_likelihood_bound else 0.0)
         noise = self._noise_like(_dense(inputs.detach())) if self.training else None
         return _GCFunction.apply(inputs, scales, means, noise, self._scale_bound, self._lik_bound if self.use_likelihood_bound else 0.0)
 

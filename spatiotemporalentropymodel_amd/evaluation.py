@@ -2,6 +2,8 @@
 
     inference_iframe(imodel, x)                    stem/evalSTEM.py:34-89   (inferenceI_DVR)
     inference_pframe(imodel, stem, x, y_cond)      stem/evalSTEM.py:92-153  (inferenceP_DVR)
+    eval_image(model, x) / eval_image_estimate     compressai/utils/eval_model/__main__.py:73-135 (inference, inference_entropy_estimation):
+                                                   one image through an I-frame model of the zoo, outside any sequence
     eval_gop(imodel, stem, frames, gop=12)         the frame loop of evalDataset, stem/evalSTEM.py:180-216: frame index % GOP == 1
                                                    is an I frame coded by the image model's own compress / decompress, every other
                                                    frame a P frame conditioned on the previous frame's DECODED latents
@@ -207,9 +209,55 @@ def inference_iframe(model, x, with_msssim=True, yuv=False, write_to=None, order
     return {"y_conditioned": out_dec["y_hat"], "psnr": quality[0], "ms-ssim": quality[1], "bpp": bpp,
             "estimate_bpp": sum(est.values()),
             "estimate_y_bpp": est.get("y"), "estimate_z_bpp": est.get("z"), "y_bpp": len(out_enc["strings"][0][0]) * 8.0 / num_pixels,
-            "z_bpp": len(out_enc["strings"][1][0]) * 8.0 / num_pixels, "encoding_time": enc_time, "decoding_time": dec_time,
+            "z_bpp": len(out_enc["strings"][1][0]) * 8.0 / num_pixels if len(out_enc["strings"]) > 1 else None,      # (no hyper-prior: one string)
+            "encoding_time": enc_time, "decoding_time": dec_time,
             "out_forward": out_forward, "strings": out_enc["strings"], "shape": tuple(out_enc["shape"]), "x_hat": x_hat,
             **_yuv_metrics(frame, x_hat, yuv, write_to)}
+
+
+@torch.no_grad()
+def eval_image(model, x, with_msssim="device"):
+    """compressai/utils/eval_model/__main__.py:73-113 (`inference`) for any of the six zoo models.  x: one image [3,h,w] in [0,1]:
+    centred zero pad to multiples of 64, compress, decompress, crop -> {"psnr", "ms-ssim", "bpp", "encoding_time",
+    "decoding_time"}, bpp from the lengths of the strings.  "ms-ssim" comes from the device metric (`with_msssim`: see `_metrics`;
+    None for images without a fifth scale, where the reference's package raises)."""
+    x = x.unsqueeze(0)
+    h, w = x.size(2), x.size(3)
+    x_padded = bitstream.pad(x, 64)
+    _sync(x)
+    start = time.time()
+    out_enc = model.compress(x_padded)
+    _sync(x)
+    enc_time = time.time() - start
+    start = time.time()
+    out_dec = model.decompress(out_enc["strings"], out_enc["shape"])
+    _sync(x)
+    dec_time = time.time() - start
+    x_hat = bitstream.crop(out_dec["x_hat"], (h, w))
+    num_pixels = x.size(0) * h * w
+    quality = _metrics(x, x_hat, with_msssim)
+    return {"psnr": quality[0], "ms-ssim": quality[1], "bpp": sum(len(s[0]) for s in out_enc["strings"]) * 8.0 / num_pixels,
+            "encoding_time": enc_time, "decoding_time": dec_time}
+
+
+@torch.no_grad()
+def eval_image_estimate(model, x):
+    """eval_model/__main__.py:116-135 (`inference_entropy_estimation`): the forward pass on the image as it is (no padding, as
+    there: sides the model's strides do not divide raise a shape error) -> {"psnr", "bpp", "encoding_time", "decoding_time"}, bpp
+    the rate estimate -sum(log2 likelihoods) / pixels."""
+    x = x.unsqueeze(0)
+    _sync(x)
+    start = time.time()
+    out_net = model(x)
+    _sync(x)
+    elapsed = time.time() - start
+    num_pixels = x.size(0) * x.size(2) * x.size(3)
+    x_hat = out_net["x_hat"]
+    if tuple(x_hat.shape) != tuple(x.shape):
+        raise ValueError(f"eval_image_estimate: the model returns {tuple(x_hat.shape[-2:])} for an image of {tuple(x.shape[-2:])}: "
+                         f"pad it to multiples of the model's downsampling factor")
+    bpp = sum(_bpp_terms({"strings": []}, out_net, num_pixels)[1].values())
+    return {"psnr": psnr(x, x_hat), "bpp": bpp, "encoding_time": elapsed / 2.0, "decoding_time": elapsed / 2.0}
 
 
 @torch.no_grad()

@@ -1451,6 +1451,62 @@ def gc_backward(out, scales, means, dlik, dscales, dmeans, dy=None, scale_bound=
     return q
 
 
+def gc_scale_forward(y, scales, mode="round", noise=None, seed=0, offset=0, epoch=None, scale_bound=0.11, lik_bound=1e-9):
+    """GaussianConditional.forward(y, scales, means=None) in one launch (csrc/hyperprior.hip) -> (out, lik), dense NHWC.
+    mode "noise": out = y + noise, the tensor `noise` or, without one, the Philox draw at (seed, offset, epoch) -- the values
+    uniform_noise_like(y, seed, offset, epoch) holds; mode "round": out = round(y).  y, scales, noise: any NHWC views."""
+    if mode not in ("noise", "round"):
+        raise ValueError(f'gc_scale_forward: mode is "noise" or "round", got {mode!r}')
+    B, Cc, H, W = y.shape
+    if tuple(scales.shape) != tuple(y.shape) or (noise is not None and tuple(noise.shape) != tuple(y.shape)):
+        raise ValueError(f"gc_scale_forward: y {tuple(y.shape)}, scales {tuple(scales.shape)}"
+                         + ("" if noise is None else f", noise {tuple(noise.shape)}") + " differ in shape")
+    (yp, ldy), (sp, lds) = _nhwc_arg(y, "gc_scale_forward: y"), _nhwc_arg(scales, "gc_scale_forward: scales")
+    np_, ldn = _nhwc_arg(noise, "gc_scale_forward: noise") if noise is not None and mode == "noise" else (None, 0)
+    out, lik = empty_nhwc(B, Cc, H, W, y.device), empty_nhwc(B, Cc, H, W, y.device)
+    _, sd, off, ep, stride = _noise_args(None, seed, offset, epoch)
+    _chk(_lib.hip().stem_gc_scale_forward(yp, ldy, np_, ldn, sd, off, ep, stride, sp, lds, out.data_ptr(), Cc, lik.data_ptr(), Cc,
+                                          B * H * W, Cc, 0 if mode == "noise" else 1, scale_bound, lik_bound, _stream()))
+    return out, lik
+
+
+def gc_scale_backward(out, scales, dlik, dscales=None, dy=None, dout=None, scale_bound=0.11, lik_bound=1e-9, record=False):
+    """gc_scale_forward's gradient in one launch: writes dscales and dy (each optional; any NHWC views) from dlik, dy = d lik / d y
+    (+ dout, the gradient that arrived at `out`).  record=True: returns the scale record of (dscales | d lik / d y), as gc_backward"""
+    B, Cc, H, W = out.shape
+    if dout is not None and dy is None:
+        raise ValueError("gc_scale_backward: dout is added into dy, which is missing")
+    args = []
+    for t, name in ((out, "out"), (scales, "scales"), (dlik, "dlik"), (dout, "dout"), (dscales, "dscales"), (dy, "dy")):
+        if t is None:
+            args += [None, 0]
+            continue
+        assert tuple(t.shape) == tuple(out.shape), name
+        args += _nhwc_arg(t, f"gc_scale_backward: {name}")
+    q = qrec_for(B * H * W * Cc, out.device) if record else None
+    _chk(_lib.hip().stem_gc_scale_backward(*args, B * H * W, Cc, scale_bound, lik_bound, _ptr(q), _stream()))
+    return q
+
+
+def abs_(x):
+    """|x| of an NHWC tensor or channel-slice view -> dense NHWC (csrc/hyperprior.hip)"""
+    B, Cc, H, W = x.shape
+    out = empty_nhwc(B, Cc, H, W, x.device)
+    xp, ldx = _nhwc_arg(x, "abs_: x")
+    _chk(_lib.hip().stem_abs_fwd(xp, ldx, out.data_ptr(), Cc, B * H * W, Cc, _stream()))
+    return out
+
+
+def abs_backward(x, g):
+    """g * sign(x), sign(+-0) = 0: torch.abs's derivative -> dense NHWC"""
+    B, Cc, H, W = x.shape
+    assert tuple(g.shape) == tuple(x.shape)
+    dx = empty_nhwc(B, Cc, H, W, x.device)
+    (xp, ldx), (gp, ldg) = _nhwc_arg(x, "abs_backward: x"), _nhwc_arg(g, "abs_backward: g")
+    _chk(_lib.hip().stem_abs_bwd(xp, ldx, gp, ldg, dx.data_ptr(), Cc, B * H * W, Cc, _stream()))
+    return dx
+
+
 def log2_sum(lik, acc):
     """acc (float64[1]) += sum(log2(lik)); lik must be dense."""
     _chk(_lib.hip().stem_log2_sum(lik.data_ptr(), lik.numel(), acc.data_ptr(), _stream()))

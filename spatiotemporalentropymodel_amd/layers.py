@@ -530,6 +530,21 @@ class GateFunction(torch.autograd.Function):
         return da, db, dout
 
 
+class AbsFunction(torch.autograd.Function):
+    """torch.abs on NHWC memory: the |y| in front of ScaleHyperprior's h_a (compressai/models/priors.py:258)"""
+
+    @staticmethod
+    def forward(ctx, x):
+        xin = F.to_nhwc(x)
+        ctx.save_for_backward(xin)
+        return F.abs_(xin)
+
+    @staticmethod
+    def backward(ctx, g):
+        (xin,) = ctx.saved_tensors
+        return F.abs_backward(xin, F.to_nhwc(g))
+
+
 class ToNCHWFunction(torch.autograd.Function):
     """NHWC feature map -> contiguous NCHW tensor (the image handed back to the caller)."""
 

@@ -11,6 +11,9 @@ noise -> same likelihoods, gradients and updated parameters).  The arithmetic is
 the per-dispatch latency of ~50 few-microsecond glue kernels per step and most of the host time.
 
 Only `EMLoss` (rate-only, the trainSTEM criterion) has this closed form; other criteria use the generic route.
+
+`image_step` is the image-side counterpart: one batch of compressai_examples/train.py's loop for an I-frame model of the zoo, on the
+layer-wise autograd Functions (every launch a HIP kernel; no schedule of its own).
 """
 from __future__ import annotations
 
@@ -337,3 +340,37 @@ class SeptupletTrainer:
     def finish(self):
         if self.step_fn is not None:
             self.step_fn.finish()
+
+
+def image_step(model, criterion, optimizer, aux_optimizer, x, clip_max_norm=1.0):
+    """One batch of compressai_examples/train.py:127-143 for an I-frame model of the zoo:
+
+        zero both gradients -> model(x) -> criterion -> loss.backward() -> clip_grad_norm_(all parameters, clip_max_norm) ->
+        optimizer.step() -> model.aux_loss().backward() -> aux_optimizer.step()
+
+    criterion: losses.RateDistortionLoss; (optimizer, aux_optimizer): optim.configure_optimizers(model, args, max_norm=None) -- the
+    clipping is optim.clip_grad_norm_ over both flat gradient buffers, as the script clips model.parameters() (the quantiles get no
+    gradient from the main loss; their zeros join the norm).  The reference's torch.optim.Adam pair (fused=False) works too.
+    -> (out_criterion, aux_loss, grad_norm): device-resident values, no host synchronisation; grad_norm is the norm before
+    clipping, None with clip_max_norm <= 0."""
+    from .layers import to_nchw
+    from .optim import clip_grad_norm_
+    optimizer.zero_grad()
+    aux_optimizer.zero_grad()
+    out_net = model(x)
+    if F.nhwc_ld(out_net["x_hat"]) is not None and not out_net["x_hat"].is_contiguous():
+        out_net = dict(out_net, x_hat=to_nchw(out_net["x_hat"]))          # the criterion reads NCHW: the layout kernel, both ways
+    out_criterion = criterion(out_net, x)
+    out_criterion["loss"].backward()
+    grad_norm = None
+    if clip_max_norm > 0:
+        if hasattr(optimizer, "flat"):
+            grad_norm = clip_grad_norm_((optimizer, aux_optimizer), clip_max_norm)
+        else:
+            join_wgrad_stream()
+            grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), clip_max_norm)
+    optimizer.step()
+    aux_loss = model.aux_loss()
+    aux_loss.backward()
+    aux_optimizer.step()
+    return out_criterion, aux_loss, grad_norm

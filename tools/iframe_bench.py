@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """I-frame models at 1088 x 1920: getY, getX, compress and decompress of mbt2018, cheng2020-anchor and cheng2020-attn (quality 4),
-and the block kernels of csrc/resblock.hip alone at the shapes g_s gives them.
+and the block kernels of csrc/resblock.hip alone at the shapes g_s gives them; analysis, synthesis, compress and decompress of
+bmshj2018-factorized and bmshj2018-hyperprior (which have no getY / getX); the two routes of GaussianConditional.forward(means=None).
 
     python tools/iframe_bench.py                                     print the figures
     python tools/iframe_bench.py --json profiles/cheng_iframe_1080p.json
+    python tools/iframe_bench.py --models bmshj2018-factorized bmshj2018-hyperprior --no-kernels --json profiles/bmshj_iframe_1080p.json
+    python tools/iframe_bench.py --gc-route profiles/gc_scale_route.json      only the zero-mean route against the zero-tensor route
 
 HIP events on the launching stream, warm-up first, the median of the timed passes.  Each kernel's achieved bytes/s (what it must
 read plus what it must write, over its time) stands beside stem_copy_channels moving the same number of bytes: the yardstick of a
@@ -48,6 +51,8 @@ def build(name):
     with torch.no_grad():
         if name == "mbt2018":                                   # tests/golden/make_golden.py:gen_iframe_codec
             m.g_a[6].weight.mul_(4.0), m.g_a[6].bias.mul_(4.0), m.g_s[0].weight.mul_(0.25)
+        elif name.startswith("bmshj2018"):                      # tests/golden/make_golden_bmshj.py:build
+            m.g_s[0].weight.mul_(0.25)
         else:                                                   # tests/golden/make_golden_cheng.py:build
             (last,) = [c for c in m.g_a.children() if isinstance(c, L.Conv2d)]
             last.weight.mul_(0.03), last.bias.mul_(0.03)
@@ -62,20 +67,24 @@ def build(name):
 def bench_models(args):
     x = smooth_frames("iframe_bench", 1, 1, W)[0][:, :, :H, :].contiguous().to(DEV)
     res = {}
-    for name in ("mbt2018", "cheng2020-anchor", "cheng2020-attn"):
+    for name in args.models:
         m = build(name)
         with torch.no_grad():
             y = m.g_a(x)
             y_hat = F.round_(F.dense_nhwc(y))
-            r = {"getY_ms": timed(lambda: m.getY(x), args.warmup, args.passes), "getX_ms": timed(lambda: m.getX(y_hat), args.warmup, args.passes)}
+            if hasattr(m, "getY"):
+                r = {"getY_ms": timed(lambda: m.getY(x), args.warmup, args.passes), "getX_ms": timed(lambda: m.getX(y_hat), args.warmup, args.passes)}
+            else:                                                # the bmshj2018 models: the transforms themselves, and the eval forward
+                r = {"g_a_ms": timed(lambda: m.g_a(x), args.warmup, args.passes),
+                     "g_s_ms": timed(lambda: F.to_nchw(m.g_s(y_hat), clamp01=True), args.warmup, args.passes),
+                     "forward_ms": timed(lambda: m(x), args.warmup, args.passes)}
             enc = m.compress(x)                                  # warm-up: first use of the coding kernels, the decoder's self-check
             m.decompress(enc["strings"], enc["shape"])
             r["compress_ms"] = timed(lambda: m.compress(x), 0, args.codec_passes)
             r["decompress_ms"] = timed(lambda: m.decompress(enc["strings"], enc["shape"]), 0, args.codec_passes)
-            r["bytes"] = len(enc["strings"][0][0]) + len(enc["strings"][1][0])
+            r["bytes"] = sum(len(s[0]) for s in enc["strings"])
         res[name] = r
-        print("%-17s getY %8.2f ms  getX %8.2f ms  compress %9.1f ms  decompress %9.1f ms  (%d bytes)" %
-              (name, r["getY_ms"], r["getX_ms"], r["compress_ms"], r["decompress_ms"], r["bytes"]))
+        print("%-21s " % name + "  ".join("%s %.2f" % (k[:-3] + " ms", v) if k.endswith("_ms") else "(%d bytes)" % v for k, v in r.items()))
         del m
         torch.cuda.empty_cache()
     return res
@@ -124,8 +133,63 @@ def bench_kernels(args):
     return rows
 
 
+GC_ROUTE_SHAPES = ((1, 320, 68, 120), (16, 192, 16, 16))          # the latents of one 1088 x 1920 frame (M = 320); a training batch
+
+
+def bench_gc_route(args):
+    """GaussianConditional.forward(y, scales) in training mode and its backward, both ways, in one process, alternating: the
+    zero-tensor route (memset of a mean tensor, noise pass, stem_gc_forward; stem_gc_backward with a dmeans nobody reads, stem_add)
+    against the zero-mean route (stem_gc_scale_forward; stem_gc_scale_backward), allocations included as the modules make them.
+    Per shape and direction: the median over the rounds of each route's median over `passes` calls."""
+    rows = []
+    for shape in GC_ROUTE_SHAPES:
+        B, C, Hh, Ww = shape
+        y, dlik, dout = (F.empty_nhwc(B, C, Hh, Ww, DEV).normal_() for _ in range(3))
+        sc = F.empty_nhwc(B, C, Hh, Ww, DEV).uniform_(0.05, 4.0)
+
+        def old_fwd():
+            mu = torch.zeros_like(y, memory_format=torch.preserve_format)
+            return F.gc_forward(y, sc, mu, noise=F.uniform_noise_like(y, 0x5713, 0)), mu
+
+        def new_fwd():
+            return F.gc_scale_forward(y, sc, "noise", seed=0x5713, offset=0)
+
+        (out, _), mu = old_fwd()
+
+        def old_bwd():
+            dgp, dy = F.empty_nhwc(B, 2 * C, Hh, Ww, DEV), F.empty_nhwc(B, C, Hh, Ww, DEV)
+            F.gc_backward(out, sc, mu, dlik, dgp[:, :C], dgp[:, C:], dy=dy)
+            return F.add(dy, dout)
+
+        def new_bwd():
+            dsc, dy = F.empty_nhwc(B, C, Hh, Ww, DEV), F.empty_nhwc(B, C, Hh, Ww, DEV)
+            F.gc_scale_backward(out, sc, dlik, dscales=dsc, dy=dy, dout=dout)
+            return dy
+
+        assert bool((new_fwd()[0] == old_fwd()[0][0]).all()) and torch.equal(new_bwd(), old_bwd())
+        for direction, old, new in (("forward", old_fwd, new_fwd), ("backward", old_bwd, new_bwd)):
+            per_round = {"zero_tensor_route": [], "zero_mean_route": []}
+            for _ in range(args.rounds):
+                per_round["zero_tensor_route"].append(timed(old, args.warmup, args.passes))
+                per_round["zero_mean_route"].append(timed(new, args.warmup, args.passes))
+            row = {"shape": list(shape), "direction": direction, "launches": {"zero_tensor_route": 3 if direction == "forward" else 2, "zero_mean_route": 1}}
+            for k, v in per_round.items():
+                row[k + "_ms"] = statistics.median(v)
+                row[k + "_rounds_ms"] = v
+            rows.append(row)
+            print("gc route %-18s %-8s zero tensor %.4f ms  zero mean %.4f ms  (rounds: %s | %s)" %
+                  (list(shape), direction, row["zero_tensor_route_ms"], row["zero_mean_route_ms"],
+                   " ".join("%.4f" % v for v in per_round["zero_tensor_route"]), " ".join("%.4f" % v for v in per_round["zero_mean_route"])))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--models", nargs="*", default=["mbt2018", "cheng2020-anchor", "cheng2020-attn", "bmshj2018-factorized", "bmshj2018-hyperprior"],
+                    choices=["mbt2018", "cheng2020-anchor", "cheng2020-attn", "bmshj2018-factorized", "bmshj2018-hyperprior"], help="the zoo entries to time")
+    ap.add_argument("--no-kernels", action="store_true", help="skip the block kernels of csrc/resblock.hip")
+    ap.add_argument("--gc-route", default=None, metavar="JSON", help="time the two routes of GaussianConditional.forward(means=None), write them here, and stop")
+    ap.add_argument("--rounds", type=int, default=5, help="alternations of the two routes (--gc-route)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--passes", type=int, default=11, help="timed passes of getY / getX and of each kernel")
     ap.add_argument("--codec-passes", type=int, default=3, help="timed passes of compress / decompress (seconds each)")
@@ -134,7 +198,16 @@ def main():
     args = ap.parse_args()
     res = {"size": [H, W], "quality": 4, "warmup": args.warmup, "passes": args.passes, "codec_passes": args.codec_passes,
            "device": torch.cuda.get_device_name(0)}
-    res["kernels"] = bench_kernels(args)
+    if args.gc_route:
+        out = {"warmup": args.warmup, "passes": args.passes, "rounds": args.rounds, "device": res["device"], "timing": "HIP events around each call, "
+               "median of the passes per round, routes alternating round by round", "rows": bench_gc_route(args)}
+        os.makedirs(os.path.dirname(os.path.abspath(args.gc_route)), exist_ok=True)
+        with open(args.gc_route, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        return
+    if not args.no_kernels:
+        res["kernels"] = bench_kernels(args)
     if not args.kernels_only:
         res["models"] = bench_models(args)
     if args.json:
