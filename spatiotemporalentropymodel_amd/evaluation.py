@@ -8,6 +8,10 @@
                                                    is an I frame coded by the image model's own compress / decompress, every other
                                                    frame a P frame conditioned on the previous frame's DECODED latents
 
+    eval_sequence(imodel, stem, frames, ...)       `eval_gop` with the sequence's GOPs coded side by side (`gop_schedule`)
+
+What these and the pixel-domain functions below share is stated once: `_code_image` (pad, timed encode, timed decode, crop of one still
+image), `_frame_record` (a frame's dictionary; "z_bpp" is None for a model with one string) and `_sequence_averages`.
 Same order of operations, same returned keys, same arithmetic for bpp / PSNR as the script.  "ms-ssim": the script calls
 `pytorch_msssim.ms_ssim(x, x_hat, data_range=1.0)` (:81, :147), a third-party package that is not in the reference tree (nor in this
 image; unpinned in the reference's requirements): `ms_ssim` below restates the published algorithm (Wang, Simoncelli, Bovik 2003)
@@ -183,6 +187,60 @@ def _bpp_terms(out_enc, out_forward, num_pixels):
     return bpp, est
 
 
+def _code_image(model, x, extra_ins=(), dec_ins=(), forward=True, **okw):
+    """One still image x [1,3,h,w] through a model: centred zero pad to multiples of 64; model.compress(x_padded, *extra_ins) and, with
+    forward=True, model(x_padded, *extra_ins) (the rate estimate) timed together as encoding; model.decompress(strings, shape, *dec_ins)
+    timed as decoding; crop.  extra_ins / dec_ins arrive padded; okw goes to compress and decompress.
+    -> (out_enc, out_forward or None, out_dec, the cropped x_hat, (encoding time, decoding time))"""
+    ins = [bitstream.pad(x, 64), *extra_ins]
+    _sync(x)
+    start = time.time()
+    out_enc = model.compress(*ins, **okw)
+    out_forward = model(*ins) if forward else None
+    _sync(x)
+    enc_time = time.time() - start
+    start = time.time()
+    out_dec = model.decompress(out_enc["strings"], out_enc["shape"], *dec_ins, **okw)
+    _sync(x)
+    dec_time = time.time() - start
+    return out_enc, out_forward, out_dec, bitstream.crop(out_dec["x_hat"], x.shape[-2:]), (enc_time, dec_time)
+
+
+def _frame_record(x, x_hat, out_enc, out_forward, times, with_msssim, /, **extras):
+    """One frame's dictionary, the keys every inference function shares: x, x_hat [1,3,h,w] the frame and its cropped reconstruction,
+    out_enc what compress returned, out_forward what forward returned (the rate estimates), times = (encoding, decoding).  "z_bpp" is
+    None for a model with one string (no hyper-prior).  extras: the caller's own keys, passed through."""
+    num_pixels = x.size(0) * x.size(2) * x.size(3)
+    strings = out_enc["strings"]
+    bpp, est = _bpp_terms(out_enc, out_forward, num_pixels)
+    quality = _metrics(x, x_hat, with_msssim)
+    return {"psnr": quality[0], "ms-ssim": quality[1], "bpp": bpp, "estimate_bpp": sum(est.values()),
+            "estimate_y_bpp": est.get("y"), "estimate_z_bpp": est.get("z"), "y_bpp": len(strings[0][0]) * 8.0 / num_pixels,
+            "z_bpp": len(strings[1][0]) * 8.0 / num_pixels if len(strings) > 1 else None,
+            "encoding_time": times[0], "decoding_time": times[1], "strings": strings, "shape": tuple(out_enc["shape"]), "x_hat": x_hat, **extras}
+
+
+_YUV_KEYS = ("psnr_y", "psnr_u", "psnr_v", "psnr_yuv")
+
+
+def _sequence_averages(per_frame, also=(), psnr_roi=False):
+    """A sequence's result: "frames" and the averages the scripts log (stem/evalSTEM.py:217-224, eval_stem_roi.py:343-354) --
+    "psnr_ave", "bpp_ave", "estimate_bpp_ave" over every frame, "msssim_ave" over the frames that have an MS-SSIM (None without any).
+    also: further per-frame keys averaged over every frame (`_YUV_KEYS`, "bits"); psnr_roi: "psnr_roi_ave", the mean over the frames
+    with a finite "psnr_roi", None without any."""
+    n = max(1, len(per_frame))
+    ms = [f["ms-ssim"] for f in per_frame if f["ms-ssim"] is not None]
+    res = {"frames": per_frame, "psnr_ave": sum(f["psnr"] for f in per_frame) / n, "bpp_ave": sum(f["bpp"] for f in per_frame) / n,
+           "msssim_ave": (sum(ms) / len(ms)) if ms else None,
+           "estimate_bpp_ave": sum(f["estimate_bpp"] for f in per_frame) / n}
+    for k in also:
+        res[k + "_ave"] = sum(f[k] for f in per_frame) / n
+    if psnr_roi:
+        roi = [f["psnr_roi"] for f in per_frame if f.get("psnr_roi") is not None and math.isfinite(f["psnr_roi"])]
+        res["psnr_roi_ave"] = (sum(roi) / len(roi)) if roi else None
+    return res
+
+
 @torch.no_grad()
 def inference_iframe(model, x, with_msssim=True, yuv=False, write_to=None, order="raster"):
     """x: one image [3,h,w] in [0,1].  Pad to multiples of 64 (centred), compress + forward (the rate estimate), decompress, crop.
@@ -190,29 +248,9 @@ def inference_iframe(model, x, with_msssim=True, yuv=False, write_to=None, order
     order: the symbol order of the y string ("raster" | "wavefront")."""
     okw = _order_kw(order)
     frame, x = x, x.unsqueeze(0)
-    h, w = x.size(2), x.size(3)
-    x_padded = bitstream.pad(x, 64)
-    _sync(x)
-    start = time.time()
-    out_enc = model.compress(x_padded, **okw)
-    out_forward = model(x_padded)
-    _sync(x)
-    enc_time = time.time() - start
-    start = time.time()
-    out_dec = model.decompress(out_enc["strings"], out_enc["shape"], **okw)
-    _sync(x)
-    dec_time = time.time() - start
-    x_hat = bitstream.crop(out_dec["x_hat"], (h, w))
-    num_pixels = x.size(0) * h * w
-    bpp, est = _bpp_terms(out_enc, out_forward, num_pixels)
-    quality = _metrics(x, x_hat, with_msssim)
-    return {"y_conditioned": out_dec["y_hat"], "psnr": quality[0], "ms-ssim": quality[1], "bpp": bpp,
-            "estimate_bpp": sum(est.values()),
-            "estimate_y_bpp": est.get("y"), "estimate_z_bpp": est.get("z"), "y_bpp": len(out_enc["strings"][0][0]) * 8.0 / num_pixels,
-            "z_bpp": len(out_enc["strings"][1][0]) * 8.0 / num_pixels if len(out_enc["strings"]) > 1 else None,      # (no hyper-prior: one string)
-            "encoding_time": enc_time, "decoding_time": dec_time,
-            "out_forward": out_forward, "strings": out_enc["strings"], "shape": tuple(out_enc["shape"]), "x_hat": x_hat,
-            **_yuv_metrics(frame, x_hat, yuv, write_to)}
+    out_enc, out_forward, out_dec, x_hat, times = _code_image(model, x, **okw)
+    return _frame_record(x, x_hat, out_enc, out_forward, times, with_msssim, y_conditioned=out_dec["y_hat"], out_forward=out_forward,
+                         **_yuv_metrics(frame, x_hat, yuv, write_to))
 
 
 @torch.no_grad()
@@ -222,22 +260,10 @@ def eval_image(model, x, with_msssim="device"):
     "decoding_time"}, bpp from the lengths of the strings.  "ms-ssim" comes from the device metric (`with_msssim`: see `_metrics`;
     None for images without a fifth scale, where the reference's package raises)."""
     x = x.unsqueeze(0)
-    h, w = x.size(2), x.size(3)
-    x_padded = bitstream.pad(x, 64)
-    _sync(x)
-    start = time.time()
-    out_enc = model.compress(x_padded)
-    _sync(x)
-    enc_time = time.time() - start
-    start = time.time()
-    out_dec = model.decompress(out_enc["strings"], out_enc["shape"])
-    _sync(x)
-    dec_time = time.time() - start
-    x_hat = bitstream.crop(out_dec["x_hat"], (h, w))
-    num_pixels = x.size(0) * h * w
+    out_enc, _, _, x_hat, times = _code_image(model, x, forward=False)
     quality = _metrics(x, x_hat, with_msssim)
-    return {"psnr": quality[0], "ms-ssim": quality[1], "bpp": sum(len(s[0]) for s in out_enc["strings"]) * 8.0 / num_pixels,
-            "encoding_time": enc_time, "decoding_time": dec_time}
+    return {"psnr": quality[0], "ms-ssim": quality[1], "bpp": sum(len(s[0]) for s in out_enc["strings"]) * 8.0 / (x.size(0) * x.size(2) * x.size(3)),
+            "encoding_time": times[0], "decoding_time": times[1]}
 
 
 @torch.no_grad()
@@ -282,15 +308,9 @@ def inference_pframe(imodel, stem, x, y_conditioned, with_msssim=True, yuv=False
     _sync(x)
     dec_time = time.time() - start
     x_hat = bitstream.crop(x_hat, (h, w))
-    num_pixels = x.size(0) * h * w
-    bpp, est = _bpp_terms(out_enc, out_forward, num_pixels)
-    quality = _metrics(x, x_hat, with_msssim)
-    return {"y_conditioned": y_hat, "psnr": quality[0], "ms-ssim": quality[1], "bpp": bpp,
-            "estimate_bpp": sum(est.values()),
-            "estimate_y_bpp": est.get("y"), "estimate_z_bpp": est.get("z"), "y_bpp": len(out_enc["strings"][0][0]) * 8.0 / num_pixels,
-            "z_bpp": len(out_enc["strings"][1][0]) * 8.0 / num_pixels, "encoding_time": enc_time, "decoding_time": dec_time,
-            "entropy_params": out_dec.get("entropy_params") if isinstance(out_dec, dict) else None,
-            "strings": out_enc["strings"], "shape": tuple(out_enc["shape"]), "x_hat": x_hat, **_yuv_metrics(frame, x_hat, yuv, write_to)}
+    return _frame_record(x, x_hat, out_enc, out_forward, (enc_time, dec_time), with_msssim, y_conditioned=y_hat,
+                         entropy_params=out_dec.get("entropy_params") if isinstance(out_dec, dict) else None,
+                         **_yuv_metrics(frame, x_hat, yuv, write_to))
 
 
 @torch.no_grad()
@@ -317,15 +337,7 @@ def eval_gop(imodel, stem, frames, gop=12, all_intra=False, with_msssim=True, yu
             out["type"] = "P"
         y_cond = out["y_conditioned"]
         per_frame.append(out)
-    n = max(1, len(per_frame))
-    ms = [f["ms-ssim"] for f in per_frame if f["ms-ssim"] is not None]
-    res = {"frames": per_frame, "psnr_ave": sum(f["psnr"] for f in per_frame) / n, "bpp_ave": sum(f["bpp"] for f in per_frame) / n,
-           "msssim_ave": (sum(ms) / len(ms)) if ms else None,
-           "estimate_bpp_ave": sum(f["estimate_bpp"] for f in per_frame) / n}
-    if yuv:
-        for k in ("psnr_y", "psnr_u", "psnr_v", "psnr_yuv"):
-            res[k + "_ave"] = sum(f[k] for f in per_frame) / n
-    return res
+    return _sequence_averages(per_frame, _YUV_KEYS if yuv else ())
 
 
 def gop_schedule(n_frames, gop, concurrent_gops, all_intra=False):
@@ -417,35 +429,15 @@ def eval_sequence(imodel, stem, frames, gop=12, concurrent_gops=8, all_intra=Fal
         _sync(xs[0])
         dec_time = (time.time() - start) / len(step)
         for k, (index, kind, chain) in enumerate(step):
-            x = xs[k]
-            h, w = x.size(2), x.size(3)
-            xh = bitstream.crop(x_hat[k], (h, w))
-            num_pixels = x.size(0) * h * w
-            bpp, est = _bpp_terms(enc[k], fwd[k], num_pixels)
-            quality = _metrics(x, xh, with_msssim)
+            xh = bitstream.crop(x_hat[k], xs[k].shape[-2:])
             sink = io.BytesIO() if writer is not None else None
-            out = {"y_conditioned": y_hat[k], "psnr": quality[0], "ms-ssim": quality[1], "bpp": bpp, "estimate_bpp": sum(est.values()),
-                   "estimate_y_bpp": est.get("y"), "estimate_z_bpp": est.get("z"), "y_bpp": len(enc[k]["strings"][0][0]) * 8.0 / num_pixels,
-                   "z_bpp": len(enc[k]["strings"][1][0]) * 8.0 / num_pixels, "encoding_time": enc_time, "decoding_time": dec_time}
-            if kind == "I":
-                out["out_forward"] = fwd[k]
-            else:
-                out["entropy_params"] = dec[k].get("entropy_params") if isinstance(dec[k], dict) else None
-            out.update({"strings": enc[k]["strings"], "shape": tuple(enc[k]["shape"]), "x_hat": xh, **_yuv_metrics(srcs[k], xh, yuv, sink),
-                        "type": kind, "concurrent": len(step)})
+            own = {"out_forward": fwd[k]} if kind == "I" else {"entropy_params": dec[k].get("entropy_params") if isinstance(dec[k], dict) else None}
+            per_frame[index] = _frame_record(xs[k], xh, enc[k], fwd[k], (enc_time, dec_time), with_msssim, y_conditioned=y_hat[k], **own,
+                                             **_yuv_metrics(srcs[k], xh, yuv, sink), type=kind, concurrent=len(step))
             if writer is not None:
                 writer.put(index, sink.getvalue())
-            per_frame[index] = out
         y_cond = {chain: y_hat[k] for k, (_, _, chain) in enumerate(step)}      # a chain that left the step has ended
-    n = max(1, len(per_frame))
-    ms = [f["ms-ssim"] for f in per_frame if f["ms-ssim"] is not None]
-    res = {"frames": per_frame, "psnr_ave": sum(f["psnr"] for f in per_frame) / n, "bpp_ave": sum(f["bpp"] for f in per_frame) / n,
-           "msssim_ave": (sum(ms) / len(ms)) if ms else None,
-           "estimate_bpp_ave": sum(f["estimate_bpp"] for f in per_frame) / n}
-    if yuv:
-        for k in ("psnr_y", "psnr_u", "psnr_v", "psnr_yuv"):
-            res[k + "_ave"] = sum(f[k] for f in per_frame) / n
-    return res
+    return _sequence_averages(per_frame, _YUV_KEYS if yuv else ())
 
 
 # ----------------------------------------------------------------------------- pixel-domain models (stem_roi/eval_stem_*.py)
@@ -504,33 +496,16 @@ def _pixel_frame(model, x, x_conditioned, qmap, with_msssim, roi_weight):
         roi_weight = None
     else:
         roi_weight = quality_map(roi_weight, h, w).to(x.device)
-    ins = [bitstream.pad(x, 64)]
-    cond = None
+    cond = []
     if x_conditioned is not None:
-        cond = bitstream.pad(x_conditioned.unsqueeze(0) if x_conditioned.dim() == 3 else x_conditioned, 64)
-        ins.append(cond)
+        cond = [bitstream.pad(x_conditioned.unsqueeze(0) if x_conditioned.dim() == 3 else x_conditioned, 64)]
+    ins = list(cond)
     if _takes_qmap(model):
         if qmap is None:
             raise ValueError(f"{type(model).__name__} takes a quality map")
         ins.append(bitstream.pad(qmap, 64))
-    _sync(x)
-    start = time.time()
-    out_enc = model.compress(*ins)
-    out_forward = model(*ins)
-    _sync(x)
-    enc_time = time.time() - start
-    start = time.time()
-    out_dec = model.decompress(out_enc["strings"], out_enc["shape"], *([cond] if cond is not None else []))
-    _sync(x)
-    dec_time = time.time() - start
-    x_hat = bitstream.crop(out_dec["x_hat"], (h, w))
-    num_pixels = x.size(0) * h * w
-    bpp, est = _bpp_terms(out_enc, out_forward, num_pixels)
-    quality = _metrics(x, x_hat, with_msssim)
-    out = {"psnr": quality[0], "ms-ssim": quality[1], "bpp": bpp, "bits": sum(len(s[0]) for s in out_enc["strings"]) * 8.0, "estimate_bpp": sum(est.values()),
-           "estimate_y_bpp": est.get("y"), "estimate_z_bpp": est.get("z"), "y_bpp": len(out_enc["strings"][0][0]) * 8.0 / num_pixels,
-           "z_bpp": len(out_enc["strings"][1][0]) * 8.0 / num_pixels, "encoding_time": enc_time, "decoding_time": dec_time,
-           "strings": out_enc["strings"], "shape": tuple(out_enc["shape"]), "x_hat": x_hat}
+    out_enc, out_forward, _, x_hat, times = _code_image(model, x, ins, cond)
+    out = _frame_record(x, x_hat, out_enc, out_forward, times, with_msssim, bits=sum(len(s[0]) for s in out_enc["strings"]) * 8.0)
     if roi_weight is not None:
         out["psnr_roi"] = psnr_roi(x, x_hat, roi_weight)
     return out
@@ -595,12 +570,7 @@ def eval_gop_pixel(model_i, model_p, frames, qmaps=None, gop=12, all_intra=False
             out["type"] = "P"
         x_cond = out["x_hat"]
         per_frame.append(out)
-    n = max(1, len(per_frame))
-    ms = [f["ms-ssim"] for f in per_frame if f["ms-ssim"] is not None]
-    roi = [f["psnr_roi"] for f in per_frame if f.get("psnr_roi") is not None and math.isfinite(f["psnr_roi"])]
-    return {"frames": per_frame, "psnr_ave": sum(f["psnr"] for f in per_frame) / n, "msssim_ave": (sum(ms) / len(ms)) if ms else None,
-            "bpp_ave": sum(f["bpp"] for f in per_frame) / n, "bits_ave": sum(f["bits"] for f in per_frame) / n,
-            "estimate_bpp_ave": sum(f["estimate_bpp"] for f in per_frame) / n, "psnr_roi_ave": (sum(roi) / len(roi)) if roi else None}
+    return _sequence_averages(per_frame, ("bits",), psnr_roi=True)
 
 
 def eval_levels(model_i, model_p, frames, levels=(0.30, 0.45, 0.55, 0.70), gop=12, level_range=(0, 1), **kwargs):

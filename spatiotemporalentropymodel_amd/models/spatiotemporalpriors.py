@@ -9,9 +9,6 @@ state-dict keys and method contracts (compressai/models/spatiotemporalpriors.py:
 forward / backward run the fused HIP schedule of `engine.StemEngine`; the bitstream side keeps the
 rANS coder on the host (codec.py).
 """
-import math
-import warnings
-
 import torch
 import torch.nn as nn
 
@@ -19,21 +16,10 @@ from .. import functional as F
 from ..engine import StemEngine, StemFunction
 from ..entropy_models import GaussianConditional
 from ..layers import Conv2d, ConvTranspose2d, FusedSequential, LeakyReLU, MaskedConv2d
-from .priors import CompressionModel
-from .utils import update_registered_buffers
+from .priors import CompressionModel, get_scale_table      # get_scale_table: re-exported, it lives next to ScaleHyperprior
 
 __all__ = ["get_scale_table", "SpatioTemporalPriorModelWithoutSPMTPM", "SpatioTemporalPriorModelWithoutSPM",
            "SpatioTemporalPriorModelWithoutTPM", "SpatioTemporalPriorModel", "SpatioTemporalPriorModel_Res"]
-
-# From Balle's tensorflow compression examples (spatiotemporalpriors.py:22-30)
-SCALES_MIN = 0.11
-SCALES_MAX = 256
-SCALES_LEVELS = 64
-
-
-def get_scale_table(min=SCALES_MIN, max=SCALES_MAX, levels=SCALES_LEVELS):  # pylint: disable=W0622
-    return torch.exp(torch.linspace(math.log(min), math.log(max), levels))
-
 
 def _tpm(cin):
     return FusedSequential(Conv2d(cin, 256, kernel_size=5, padding=2, stride=1), LeakyReLU(),
@@ -106,18 +92,6 @@ class _StemBase(CompressionModel):
         assert isinstance(strings, list) and len(strings) == 2
         y_hat = stem_decompress(self, strings, shape, y_conditioned, order=order)
         return {"y_hat": y_hat} if self.DECOMPRESS_RETURNS_DICT else y_hat
-
-    def load_state_dict(self, state_dict, strict=True):
-        update_registered_buffers(self.gaussian_conditional, "gaussian_conditional",
-                                  ["_quantized_cdf", "_offset", "_cdf_length", "scale_table"], state_dict)
-        return super().load_state_dict(state_dict, strict=strict)
-
-    def update(self, scale_table=None, force=False):
-        if scale_table is None:
-            scale_table = get_scale_table()
-        updated = self.gaussian_conditional.update_scale_table(scale_table, force=force)
-        updated |= super().update(force=force)
-        return updated
 
 
 class SpatioTemporalPriorModelWithoutSPMTPM(_StemBase):

@@ -22,9 +22,7 @@ from .. import functional as F
 from ..entropy_models import GaussianConditional
 from ..layers import GDN, Conv2d, ConvTranspose2d, FusedSequential, adaptive_avg_pool2d, cat, conv, deconv, to_nchw
 from .priors import CompressionModel
-from .spatiotemporalpriors import get_scale_table
 from .stem_utils import SFT, SFTResblk
-from .utils import update_registered_buffers
 
 __all__ = ["stem_baseline", "stem_baselinev2", "stem_roi", "stem_roi_wo_gsc", "stem_roi_i"]
 
@@ -146,18 +144,6 @@ class _PixelStem(CompressionModel):
         y_hat = self.gaussian_conditional.decompress(strings[0], None, means=means_hat, scales=scales_hat)
         x_hat = F.to_nchw(self._synthesis(y_hat, z_hat), clamp01=True)
         return {"x_hat": x_hat, "y_hat": y_hat, "entropy_params": {"scales_hat": scales_hat, "means_hat": means_hat}}
-
-    def load_state_dict(self, state_dict, strict=True):
-        update_registered_buffers(self.gaussian_conditional, "gaussian_conditional",
-                                  ["_quantized_cdf", "_offset", "_cdf_length", "scale_table"], state_dict)
-        return super().load_state_dict(state_dict, strict=strict)
-
-    def update(self, scale_table=None, force=False):
-        if scale_table is None:
-            scale_table = get_scale_table()
-        updated = self.gaussian_conditional.update_scale_table(scale_table, force=force)
-        updated |= super().update(force=force)
-        return updated
 
 
 # ----------------------------------------------------------------------------- fixed-rate baselines
