@@ -29,15 +29,13 @@
 // the epilogue stores 16 consecutive channels per lane (32 bytes per plane, 64 bytes of fp32).
 #include <math.h>
 
-#include "stem_common.h"
+#include "f16x3_layout.h"
 
 namespace {
 
-typedef hp8 h16x8;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CHUNK = 12288;                    // bytes of one A-operand chunk: 6 tiles x 2 planes x 64 lanes x 16 B
-constexpr int OOR = 0x7FFFFF00;                 // voffset that every buffer view rejects (returns 0)
 constexpr int OOR_ST = 0x7FFF0000;              // the same with room for the stores' constant offsets (views are < 0x7FFF0000 bytes)
 constexpr int WG_PIX = 128, NTHREADS = 256;     // 4 wavefronts x 32 pixels
 
@@ -107,12 +105,7 @@ __global__ __launch_bounds__(256) void c4gdn_pack_kernel(const float *wp_c4, con
     }
     if (!used) return;
     h16x8 p0, p1;
-    const float sc = q_pow2(c < ksc ? we : ge);
-    for (int j = 0; j < 8; ++j) {
-        hp_t a, b;
-        q_split(v[j], sc, a, b);
-        p0[j] = a; p1[j] = b;
-    }
+    q_split8([&](int j) { return v[j]; }, q_pow2(c < ksc ? we : ge), p0, p1);
     unsigned char *dst = out + (size_t)c * CHUNK + ((size_t)(fp * 2) * 64 + lane) * 16;
     *reinterpret_cast<h16x8 *>(dst) = p0;
     *reinterpret_cast<h16x8 *>(dst + 1024) = p1;

@@ -21,7 +21,7 @@
 // lane lr (0..31) is pixel (row 2 mi + (lr >> 4), column lr < 16 ? lr : (lr - HP) & 15) of the wavefront's four image rows:
 // the rotation of the odd rows makes h == lr (mod 16) for every lane whatever the halo pitch HP and whatever the tap's shift,
 // which is the condition under which the 16-lane groups of ds_read_b128 touch 16 different bank columns (the argument of
-// conv_f16x3.hip's 64-byte-row image).  Weights: [plane][128 rows][64 B] with the same swizzle, as packed.
+// conv_f16x3.hip's 64-byte-row image).  Weights: the gen image (f16x3_layout.h), as packed.
 //
 // Loop: chunks q = slab * T + tap of this workgroup's split [q_begin, q_end); per chunk one barrier.  Weight chunk c + 2 is
 // issued at the top of chunk c into the slot chunk c - 1 has just released; the halo of slab s + 2 is fetched to registers in
@@ -35,25 +35,20 @@
 
 #include <type_traits>
 
-#include "stem_common.h"
+#include "f16x3_layout.h"
 
 namespace {
 
-typedef hp8 h16x8;
-
-constexpr int KC = 32, NPL = 2, SLAB = NPL * 64;
-constexpr int IBN = 128;                                   // output channels per workgroup
-constexpr int IB_PLANE = IBN * 64, IB_BUF = NPL * IB_PLANE; // 16384 B per weight chunk
+// output channels per workgroup = GBN: the kernel streams the gen image (GB_PLANE / GB_BUF per weight chunk) as packed
 constexpr int TS = 16, TPX = TS * TS;                      // 16 x 16 output pixels per workgroup
 constexpr int HPMAX = TS + 4, NHMAX = HPMAX * HPMAX;       // halo at 5x5
 constexpr int IA_PLANE = NHMAX * 64, IA_BUF = NPL * IA_PLANE;       // 25600 / 51200
 constexpr int NRING = 3;
-constexpr int ITP = IBN + 4;                               // fp32 pitch of the epilogue tile
-constexpr int ILDS_MAIN = 2 * IA_BUF + NRING * IB_BUF;     // 151552
+constexpr int ITP = GBN + 4;                               // fp32 pitch of the epilogue tile
+constexpr int ILDS_MAIN = 2 * IA_BUF + NRING * GB_BUF;     // 151552
 static_assert(TPX * ITP * 4 <= ILDS_MAIN, "the epilogue tile re-uses the main loop's LDS");
 constexpr int ILDS = ILDS_MAIN + 32 * 4;                   // + reduction scratch and the last-arriver flag
 constexpr int NTHR = 512;                                  // threads
-constexpr int OOR = 0x7FFFFF00;
 enum { EPI_BIAS = 0, EPI_LRELU = 1, EPI_DACT = 2 };
 
 struct ImgArgs {
@@ -76,28 +71,8 @@ struct ImgArgs {
     int tiles_x, tiles_y;
 };
 
-// block_max on a caller-provided LDS scratch (the kernel keeps ALL its LDS in the one dynamic array: a second __shared__ object
-// beside an LDS-DMA ring makes hipcc drain the ring before every LDS read)
-__device__ inline float block_max512(float v, float *red)
-{
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float m = red[0];
-#pragma unroll
-    for (int w = 1; w < NTHR / 64; ++w) m = fmaxf(m, red[w]);
-    return m;
-}
-__device__ inline float q_amax512(const float *q, float *red)
-{
-    int ns = q_nslots(q);
-    ns = ns < 0 ? 0 : (ns > (1 << 20) ? (1 << 20) : ns);
-    float m = 0.f;
-    for (int i = threadIdx.x; i < ns; i += NTHR) m = fmaxf(m, q[QREC_HDR + i]);
-    return block_max512(m, red);
-}
-
+// The kernel keeps ALL its LDS in the one dynamic array, the scratch of block_max<NTHR> included: a second __shared__ object beside
+// an LDS-DMA ring makes hipcc drain the ring before every LDS read.
 template <int KS>
 __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
 {
@@ -114,7 +89,7 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
     const int tpi = a.tiles_x * a.tiles_y;
     const int bimg = BX / tpi, trem = BX - bimg * tpi, tyi = trem / a.tiles_x, txi = trem - tyi * a.tiles_x;
     const int y0 = tyi * TS, x0 = txi * TS;
-    const int bn0 = BY * IBN, zsplit = BZ;
+    const int bn0 = BY * GBN, zsplit = BZ;
     const int nslab = a.C / KC, T = a.ntaps, nchunks = T * nslab;
     const int q_begin = zsplit * a.cps;
     const int q_end = q_begin + a.cps < nchunks ? q_begin + a.cps : nchunks;
@@ -153,8 +128,8 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
     // weight chunk q -> ring slot: wavefront w copies bytes [2048 w, 2048 w + 2048) as two 1 KiB LDS-DMA instructions
     const int ring_v = wave * 2048 + lane * 16;
     auto dmaB = [&](int q, int slot) {
-        auto *ls = (__attribute__((address_space(3))) void *)(smem + 2 * IA_BUF + slot * IB_BUF + wave * 2048);
-        const int so = (wbase + q) * IB_BUF;
+        auto *ls = (__attribute__((address_space(3))) void *)(smem + 2 * IA_BUF + slot * GB_BUF + wave * 2048);
+        const int so = (wbase + q) * GB_BUF;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, ls, 16, ring_v, so, 0, 0);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, ls, 16, ring_v, so, 1024, 0);
     };
@@ -184,7 +159,7 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
         v0 = ab * IA_BUF + h0 * 64 + ((lh ^ ((h0 >> 2) & 3)) << 4);
         v1 = ab * IA_BUF + h1 * 64 + ((lh ^ ((h1 >> 2) & 3)) << 4);
     };
-    auto addrB = [&](int slot) { return rdB + slot * IB_BUF + pkB0; };
+    auto addrB = [&](int slot) { return rdB + slot * GB_BUF + pkB0; };
     auto rdfrag = [&](int vA0, int vA1, int vB, h16x8 (&af)[2][NPL], h16x8 (&bf)[2][NPL]) {        // 8 ds_read_b128
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl) {
@@ -194,7 +169,7 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
 #pragma unroll
         for (int nj = 0; nj < 2; ++nj)
 #pragma unroll
-            for (int pl = 0; pl < NPL; ++pl) bf[nj][pl] = *reinterpret_cast<const h16x8 *>(smem + vB + pl * IB_PLANE + nj * 32 * 64);
+            for (int pl = 0; pl < NPL; ++pl) bf[nj][pl] = *reinterpret_cast<const h16x8 *>(smem + vB + pl * GB_PLANE + nj * 32 * 64);
     };
     auto mma = [&](const h16x8 (&af)[2][NPL], const h16x8 (&bf)[2][NPL]) {
 #pragma unroll
@@ -405,7 +380,7 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
         return (oy < a.H && ox < a.W) ? (bimg * a.H + oy) * a.W + ox : -1;
     };
     float *Tt = reinterpret_cast<float *>(smem);                   // [256][ITP]
-    const int Npad = GY * IBN;
+    const int Npad = GY * GBN;
     // every pass below gives a thread the same pieces: column group ec4 = tid & 31 (4 floats), tile rows (tid >> 5) + 16 k
     constexpr int ER = TPX / (NTHR / 32);                          // 16 pieces per thread
     const int ec4 = tid & 31, er0 = tid >> 5;
@@ -505,7 +480,7 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
         if (a.yp) *reinterpret_cast<f32x4 *>(&Tt[(er0 + 16 * k) * ITP + ec4 * 4]) = v;
     }
     if (a.yq) {
-        omax = block_max512(omax, red);
+        omax = block_max<NTHR>(omax, red);
         if (tid == 0) {
             a.yq[QREC_HDR + BY * GX + BX] = omax;
             if (BX == 0 && BY == 0) {
@@ -559,7 +534,7 @@ bool stem_fx3_img_eligible(int B, int H, int W, int N, int R, int S, int stride,
     const long tiles = (long)cdiv(H, TS) * cdiv(W, TS);
     // at least half of every tile's pixels exist on average (also what keeps the scale record's slots within planes_slots())
     if ((long)H * W * 2 < tiles * TPX) return false;
-    if ((long)B * tiles * cdiv(N, IBN) > 16384) return false;       // arrival counters
+    if ((long)B * tiles * cdiv(N, GBN) > 16384) return false;       // arrival counters
     // This form exists for launches that cannot fill the chip by pixels (the 16 x 16 latents of the training step: 32 pixel tiles
     // of 128): one workgroup per CU, the halo staged once per channel slab, deep split-K.  A launch whose 128-pixel form already
     // has two workgroups for every CU is left to that form (the variable-rate models' 3 x 3 layers at 64 x 64 .. 256 x 256).  Measured
@@ -590,7 +565,7 @@ int stem_fx3_img_split(int tiles, int nchunks)
     return best;
 }
 
-int stem_fx3_img_tiles(int B, int H, int W, int N) { return B * cdiv(H, TS) * cdiv(W, TS) * cdiv(N, IBN); }
+int stem_fx3_img_tiles(int B, int H, int W, int N) { return B * cdiv(H, TS) * cdiv(W, TS) * cdiv(N, GBN); }
 
 int stem_fx3_img_launch(const void *xp, const float *xq, int xpix, int xbytes, const void *wp, const float *wq, int wbytes, const float *bias, int epi,
                         float slope, const float *z, int ldz, float *y, int ldy, void *yp, float *yq, int B, int H, int W, int C, int N, int KS,
@@ -617,7 +592,7 @@ int stem_fx3_img_launch(const void *xp, const float *xq, int xpix, int xbytes, c
         (void)hipFuncSetAttribute((const void *)conv_f16x3_img_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, ILDS);
         attr_done = true;
     }
-    const dim3 grid(B * a.tiles_x * a.tiles_y, cdiv(N, IBN), a.nsplit);
+    const dim3 grid(B * a.tiles_x * a.tiles_y, cdiv(N, GBN), a.nsplit);
     hipStream_t st = (hipStream_t)stream;
     if (KS == 1)
         hipLaunchKernelGGL((conv_f16x3_img_kernel<1>), grid, dim3(NTHR), ILDS, st, a);

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float *p, float *g, float *m,
 }
 
 // The same update over contiguous chunks of STEM_ADAM_CHUNK parameters per workgroup, which also leaves max |p_new| of every chunk
-// in bmax[4 * chunk .. 4 * chunk + 3] (one value per wavefront): the fp16 weight packing that follows an optimiser step (conv_f16x3.hip) takes its power-of-two scale from the
+// in bmax[4 * chunk .. 4 * chunk + 3] (one value per wavefront): the fp16 weight packing that follows an optimiser step (f16x3_pack.hip) takes its power-of-two scale from the
 // maxima of the chunks a tensor touches instead of a reduction pass of its own (a chunk shared with a neighbouring tensor can
 // only raise the bound).  Same arithmetic per element as adam_kernel.
 __global__ __launch_bounds__(256) void adam_bmax_kernel(float *p, float *g, float *m, float *v, size_t n, const double *sumsq,

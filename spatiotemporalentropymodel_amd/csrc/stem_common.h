@@ -49,7 +49,7 @@ int stem_fx3_img_launch(const void *xp, const float *xq, int xpix, int xbytes, c
                         float slope, const float *z, int ldz, float *y, int ldy, void *yp, float *yq, int B, int H, int W, int C, int N, int KS,
                         int T, int split, float *ws, int *cnt, void *stream);
 
-// parameters per workgroup of the optimiser pass that leaves per-chunk maxima for the fp16 weight packing (optim.hip, conv_f16x3.hip)
+// parameters per workgroup of the optimiser pass that leaves per-chunk maxima for the fp16 weight packing (optim.hip, f16x3_pack.hip)
 #define STEM_ADAM_CHUNK 4096
 
 // ---- the 16-bit operands of the split-operand kernels (conv_f16x3 / wgrad_f16x3 / c4gdn_f16x3) -------------------------------
@@ -58,7 +58,8 @@ int stem_fx3_img_launch(const void *xp, const float *xq, int xpix, int xbytes, c
 // three v_mfma_f32_32x32x16_f16 carry an fp32 product to ~2^-21 (the dropped a1.b1 is <= 2^-22 |a.b|).  fp16 has 5 exponent
 // bits, so every planes tensor / packed weight image carries a power-of-two scale 2^e chosen by its producer from an upper
 // bound of its values (scale records below); fp16 subnormals are kept by the MFMA (tools/debug/probe/f16_denorm.hip), the
-// absolute floor of a stored value is 2^-25 2^-e.
+// absolute floor of a stored value is 2^-25 2^-e.  Where the two numbers of a value sit in a planes tensor / a packed weight image:
+// f16x3_layout.h.
 typedef _Float16 hp_t;
 typedef hp_t hp8 __attribute__((ext_vector_type(8)));
 #define STEM_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
@@ -96,6 +97,8 @@ __device__ inline float wave_max(float v)
     return v;
 }
 // maximum over the workgroup (nthreads a multiple of 64, <= 1024); red: >= 16 floats of LDS; two barriers
+// NT: the workgroup's thread count where the kernel knows it at compile time, 0 = read blockDim.x
+template <int NT = 0>
 __device__ inline float block_max(float v, float *red)
 {
     v = wave_max(v);
@@ -103,7 +106,7 @@ __device__ inline float block_max(float v, float *red)
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     float m = red[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = fmaxf(m, red[w]);
+    for (int w = 1; w < (NT ? NT >> 6 : (int)(blockDim.x >> 6)); ++w) m = fmaxf(m, red[w]);
     return m;
 }
 // max over the slots of a record (every thread gets it)

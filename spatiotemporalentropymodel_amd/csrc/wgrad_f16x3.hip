@@ -1,10 +1,10 @@
-// Weight gradient of a stride-1 convolution on the fp16 matrix cores with fp32-class products (see conv_f16x3.hip for the
+// Weight gradient of a stride-1 convolution on the fp16 matrix cores with fp32-class products (see stem_common.h for the
 // arithmetic: operands pre-split into two fp16 planes, three MFMAs per fp32 product, fp32 accumulate).
 //
 //   dW[k][c][r][s] = sum over output pixels m = (b, y, x) of dy[m][k] * x[b, y + r - pad, x + s - pad][c]
 //
 // Per tap this is a GEMM dW_t[K x C] = dY^T[K x M] . X_t[M x C] whose contraction runs over PIXELS, while both operands are
-// stored pixel-major ([pixel][C/32][2][32] fp16).  The MFMA wants, per lane, 8 consecutive contraction elements of one row /
+// stored pixel-major (planes tensors, f16x3_layout.h).  The MFMA wants, per lane, 8 consecutive contraction elements of one row /
 // column, i.e. 8 pixels of one channel: the chunk (16 pixels x 128 channels per operand and plane) is staged in LDS as it comes
 // (256-byte pixel rows) and read back with gfx950's transposing LDS read (ds_read_b64_tr_b16: a 4-pixel x 16-channel block per
 // 16 lanes, delivered channel-major) -- two reads per operand fragment, no shuffles.  LDS image: the guide's 256-byte-row form
@@ -16,20 +16,16 @@
 // as zeros through the range-checked buffer loads).
 #include <stdlib.h>
 
-#include "stem_common.h"
+#include "f16x3_layout.h"
 
 namespace {
 
-typedef hp8 h16x8;
 typedef short v4s __attribute__((ext_vector_type(4)));
 
 constexpr int TK = 128, TC = 128, NT = 256, PX = 16;      // output tile, threads, pixels per chunk (= one MFMA k-step)
 constexpr int PLANE = PX * 256;                            // 4096 B: 16 pixel rows x 128 channels of one plane
-constexpr int NPL = 2, SLAB = NPL * 64;                    // planes per value; bytes per pixel and 32-channel slab
 constexpr int OP_BUF = NPL * PLANE;                        // one operand, one buffer
 constexpr int LDS_BYTES = 2 * 2 * OP_BUF;                  // 32768: two workgroups per CU (register-limited), 2 wavefronts per SIMD
-constexpr int OOR = 0x7FFFFF00;
-constexpr int MAXTAP = 25;
 
 struct Wg3Args {
     const void *xp, *dyp;

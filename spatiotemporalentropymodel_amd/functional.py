@@ -582,7 +582,7 @@ PLANES_SLAB_BYTES = 128
 
 
 class F16Planes:
-    """An NHWC activation tensor pre-split for the 16-bit matrix cores (csrc/conv_f16x3.hip): every fp32 value v is stored as two
+    """An NHWC activation tensor pre-split for the 16-bit matrix cores (layout: csrc/f16x3_layout.h): every fp32 value v is stored as two
     fp16 numbers whose sum is v * 2^e (to 2^-22 |v|), [pixel][C/32][2][32], followed in the same buffer by the
     tensor's scale record (2^-e and the measured max |v| per producing workgroup: include/stem_hip.h).  Only produced and
     consumed by the split-operand convolution kernels; `shape` is the logical [B,C,H,W].  `channels(c0, c1)` is a view of a
