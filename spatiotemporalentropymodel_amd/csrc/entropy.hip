@@ -3,6 +3,7 @@
 // multi-pass torch expression of the reference (entropy_models.py:388-452, 570-596) is one kernel.
 #include "stem_common.h"
 #include "ar_canon.h"       // scale_index, for build_indexes_kernel
+#include "entropy_elem.h"   // the Gaussian likelihood element and the noise stream, shared with hyperprior.hip
 
 namespace {
 
@@ -156,6 +157,22 @@ __device__ float eb_logits_bwd(const float *p, const EbPrep &e, float v, const f
     return gv;
 }
 
+// the likelihood from the two logits lo = logits(v - 1/2), up = logits(v + 1/2) (entropy_models.py:410-421): sg = -sign(lo + up),
+// su = sigmoid(sg up), sl = sigmoid(sg lo), diff = su - sl; the likelihood is max(|diff|, bound), the backward needs all four
+struct EbTail {
+    float su, sl, sg, diff;
+};
+__device__ __forceinline__ EbTail eb_tail(float lo, float up)
+{
+    EbTail t;
+    const float s = lo + up;
+    t.sg = s > 0.f ? -1.f : (s < 0.f ? 1.f : 0.f);
+    t.su = sigmoid_f(t.sg * up);
+    t.sl = sigmoid_f(t.sg * lo);
+    t.diff = t.su - t.sl;
+    return t;
+}
+
 __global__ __launch_bounds__(256) void eb_forward_kernel(const float *z, int ldz, const float *noise, const float *pack,
                                                          const float *med, float *zhat, float *lik, size_t npix, int C,
                                                          int mode, float bound)
@@ -176,10 +193,7 @@ __global__ __launch_bounds__(256) void eb_forward_kernel(const float *z, int ldz
     zhat[i] = v;
     const float lo = eb_logits<false>(e, v - 0.5f, nullptr, nullptr);
     const float up = eb_logits<false>(e, v + 0.5f, nullptr, nullptr);
-    const float s = lo + up;
-    const float sg = s > 0.f ? -1.f : (s < 0.f ? 1.f : 0.f);
-    const float l = fabsf(sigmoid_f(sg * up) - sigmoid_f(sg * lo));
-    lik[i] = fmaxf(l, bound);
+    lik[i] = fmaxf(fabsf(eb_tail(lo, up).diff), bound);
 }
 
 // eb_forward_kernel with one workgroup per channel (threads over pixels, eb_prepare_shared): the form for tensors with few pixels
@@ -204,10 +218,7 @@ __global__ __launch_bounds__(256) void eb_forward_cm_kernel(const float *z, int 
             zhat[i] = v;
             const float lo = eb_logits<false>(e, v - 0.5f, nullptr, nullptr);
             const float up = eb_logits<false>(e, v + 0.5f, nullptr, nullptr);
-            const float s = lo + up;
-            const float sg = s > 0.f ? -1.f : (s < 0.f ? 1.f : 0.f);
-            const float l = fabsf(sigmoid_f(sg * up) - sigmoid_f(sg * lo));
-            lik[i] = fmaxf(l, bound);
+            lik[i] = fmaxf(fabsf(eb_tail(lo, up).diff), bound);
         }
     }
 }
@@ -235,10 +246,7 @@ __global__ __launch_bounds__(EB_BWD_NT) void eb_backward_kernel(const float *zha
         float pre_lo[4][3], in_lo[4][3], pre_up[4][3], in_up[4][3];
         const float lo = eb_logits<true>(e, v - 0.5f, pre_lo, in_lo);
         const float up = eb_logits<true>(e, v + 0.5f, pre_up, in_up);
-        const float s = lo + up;
-        const float sg = s > 0.f ? -1.f : (s < 0.f ? 1.f : 0.f);
-        const float su = sigmoid_f(sg * up), sl = sigmoid_f(sg * lo);
-        const float diff = su - sl;
+        const auto [su, sl, sg, diff] = eb_tail(lo, up);
         float g = dlik[i];
         if (!(fabsf(diff) >= bound || g < 0.f)) g = 0.f;     // LowerBound rule (bound_ops.py:28-31)
         const float gd = g * (diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f));
@@ -332,9 +340,7 @@ __global__ void eb_unpack_kernel(const float *dpack, MPtr14 t, int C, int accumu
     *dst = accumulate ? *dst + dpack[i] : dpack[i];
 }
 
-// ---- GaussianConditional -----------------------------------------------------------------------
-__device__ __forceinline__ float std_cum(float x) { return 0.5f * erfcf(-0.70710678118654752440f * x); }
-
+// ---- GaussianConditional: the kernels around entropy_elem.h's gauss_lik / gauss_bwd_elem ---------------
 __global__ __launch_bounds__(256) void gc_forward_kernel(const float *y, const float *noise, const float *scales,
                                                          const float *means, int ldsm, float *out, float *lik, size_t npix,
                                                          int C, int mode, float sb, float lb)
@@ -350,10 +356,7 @@ __global__ __launch_bounds__(256) void gc_forward_kernel(const float *y, const f
     else
         o = rintf(o - mu) + mu;
     out[i] = o;
-    const float v = fabsf(o - mu);
-    const float s = fmaxf(sc, sb);
-    const float l = std_cum((0.5f - v) / s) - std_cum((-0.5f - v) / s);
-    lik[i] = fmaxf(l, lb);
+    lik[i] = gauss_lik(fabsf(o - mu), sc, sb, lb);
 }
 
 __global__ __launch_bounds__(256) void gc_backward_kernel(const float *out, const float *scales, const float *means, int ldsm,
@@ -364,25 +367,13 @@ __global__ __launch_bounds__(256) void gc_backward_kernel(const float *out, cons
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     float m = 0.f;
     if (i < npix * C) {
-    const size_t pix = i / C;
-    const int c = (int)(i - pix * C);
-    const float mu = means[pix * ldsm + c], sc = scales[pix * ldsm + c];
-    const float d = out[i] - mu, v = fabsf(d);
-    const float s = fmaxf(sc, sb);
-    const float a = (0.5f - v) / s, b = (-0.5f - v) / s;
-    const float lraw = std_cum(a) - std_cum(b);
-    float g = dlik[i];
-    if (!(lraw >= lb || g < 0.f)) g = 0.f;
-    const float k = 0.39894228040143267794f;
-    const float pa = k * expf(-0.5f * a * a), pb = k * expf(-0.5f * b * b);
-    const float dv = g * (-(pa - pb) / s);
-    float ds = g * (-(pa * a - pb * b) / s);
-    const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-    if (!(sc >= sb || ds < 0.f)) ds = 0.f;
-    if (dsc) dsc[pix * ldd + c] = ds;
-    if (dmu) dmu[pix * ldd + c] = -dv * sgn;
-    if (dy) dy[i] = dv * sgn;
-    m = fmaxf(fabsf(ds), fabsf(dv));
+        const size_t pix = i / C;
+        const int c = (int)(i - pix * C);
+        float ds, dvs;
+        m = gauss_bwd_elem(out[i] - means[pix * ldsm + c], scales[pix * ldsm + c], dlik[i], sb, lb, ds, dvs);
+        if (dsc) dsc[pix * ldd + c] = ds;
+        if (dmu) dmu[pix * ldd + c] = -dvs;
+        if (dy) dy[i] = dvs;
     }
     if (q) record_block_max(q, m);
 }
@@ -421,33 +412,16 @@ __global__ void lrelu_bwd_kernel(const float *yact, const float *dy, float *dx, 
     if (i < n) dx[i] = yact[i] > 0.f ? dy[i] : dy[i] * slope;
 }
 
-// Philox4x32-10
-__device__ __forceinline__ void philox_round(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t k0, uint32_t k1)
-{
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-}
-// epoch != nullptr: the counter additionally advances by epoch[0] * epoch_stride, a device-resident draw count, so that a
-// captured hipGraph produces fresh noise on every replay (the host-side offset is frozen into the graph at capture).
+// the Philox stream (entropy_elem.h) written out: thread q holds the four values of counter offset [+ epoch * stride] + q
 __global__ void noise_kernel(float *out, size_t n, uint64_t seed, uint64_t offset, const long long *epoch, uint64_t epoch_stride)
 {
     const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q * 4 >= n) return;
-    const uint64_t ctr = offset + q + (epoch ? (uint64_t)epoch[0] * epoch_stride : 0);
-    uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0, c3 = 0;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c0, c1, c2, c3, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    const uint32_t r4[4] = {c0, c1, c2, c3};
+    float r[4];
+    philox4(seed, offset + q + (epoch ? (uint64_t)epoch[0] * epoch_stride : 0), r);
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-        if (q * 4 + e < n) out[q * 4 + e] = (float)(r4[e] >> 8) * (1.0f / 16777216.0f) - 0.5f;
+        if (q * 4 + e < n) out[q * 4 + e] = r[e];
 }
 
 __global__ void build_indexes_kernel(const float *scales, int lds, const float *table, int T, int32_t *idx, size_t npix, int C,
@@ -638,28 +612,6 @@ STEM_EXPORT int stem_build_indexes(const float *scales, int lds, const float *ta
 // EMLoss is a sum of logs (utils.py:18-27), so d loss / d likelihood = coef / likelihood is known in the forward pass.
 namespace {
 
-__device__ __forceinline__ void philox4(uint64_t seed, uint64_t ctr, float r[4])
-{
-    uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0, c3 = 0;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int q = 0; q < 10; ++q) {
-        philox_round(c0, c1, c2, c3, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    const uint32_t v[4] = {c0, c1, c2, c3};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = (float)(v[e] >> 8) * (1.0f / 16777216.0f) - 0.5f;      // == noise_kernel
-}
-
-struct NoiseSrc {            // either an explicit tensor (parity tests) or the Philox stream (seed, offset [+ epoch * stride])
-    const float *ptr;
-    uint64_t seed, offset, stride;
-    const long long *epoch;
-};
-__device__ __forceinline__ uint64_t noise_base(const NoiseSrc &s) { return s.offset + (s.epoch ? (uint64_t)s.epoch[0] * s.stride : 0); }
-
 // he_in = [y_cur | y_cond]; target = y_cur - y_cond (residual) or y_cur; t_hat = target + U(-1/2,1/2) (training) or
 // round(target); y_hat = t_hat + y_cond (residual) or t_hat.     spatiotemporalpriors.py:846-856,863
 // q_in / q_t (optional): scale records (stem_common.h) of he_in (= of y_cur and y_cond) and of t_hat: one slot of max |value| per
@@ -740,21 +692,12 @@ __global__ __launch_bounds__(256) void eb_forward_train_kernel(const float *z, i
         const int c = (int)(i - pix * C);
         EbPrep e;
         eb_prepare(pack + (size_t)c * NP, e);
-        float v = z[pix * ldz + c];
-        if (nz.ptr) {
-            v += nz.ptr[i];
-        } else {
-            float r[4];
-            philox4(nz.seed, noise_base(nz) + (i >> 2), r);
-            v += r[i & 3];
-        }
+        const float v = z[pix * ldz + c] + noise_at(nz, i, i);
         zhat[i] = v;
         zm = fmaxf(zm, fabsf(v));
         const float lo = eb_logits<false>(e, v - 0.5f, nullptr, nullptr);
         const float up = eb_logits<false>(e, v + 0.5f, nullptr, nullptr);
-        const float s = lo + up;
-        const float sg = s > 0.f ? -1.f : (s < 0.f ? 1.f : 0.f);
-        const float l = fmaxf(fabsf(sigmoid_f(sg * up) - sigmoid_f(sg * lo)), bound);
+        const float l = fmaxf(fabsf(eb_tail(lo, up).diff), bound);
         lik[i] = l;
         dlik[i] = coef / l;
         lg = (double)log2f(l);
@@ -779,21 +722,12 @@ __global__ __launch_bounds__(256) void eb_forward_train_cm_kernel(const float *z
         eb_prepare_shared(pack + (size_t)c * NP, prep, e);
         for (size_t pix = threadIdx.x; pix < npix; pix += 256) {
             const size_t i = pix * C + c;
-            float v = z[pix * ldz + c];
-            if (nz.ptr) {
-                v += nz.ptr[i];
-            } else {
-                float r[4];
-                philox4(nz.seed, noise_base(nz) + (i >> 2), r);
-                v += r[i & 3];
-            }
+            const float v = z[pix * ldz + c] + noise_at(nz, i, i);
             zhat[i] = v;
             zm = fmaxf(zm, fabsf(v));
             const float lo = eb_logits<false>(e, v - 0.5f, nullptr, nullptr);
             const float up = eb_logits<false>(e, v + 0.5f, nullptr, nullptr);
-            const float s = lo + up;
-            const float sg = s > 0.f ? -1.f : (s < 0.f ? 1.f : 0.f);
-            const float l = fmaxf(fabsf(sigmoid_f(sg * up) - sigmoid_f(sg * lo)), bound);
+            const float l = fmaxf(fabsf(eb_tail(lo, up).diff), bound);
             lik[i] = l;
             dlik[i] = coef / l;
             lg += (double)log2f(l);
@@ -804,8 +738,8 @@ __global__ __launch_bounds__(256) void eb_forward_train_cm_kernel(const float *z
 }
 
 // GaussianConditional.forward in training mode (+noise; means are ignored by the noise quantiser, entropy_models.py:128-135)
-// dsc / dmu (optional, both or none): the backward of the same element in the same pass -- gc_backward_kernel's expressions on the
-// values this thread already holds (d loss / d likelihood is known here: coef / lik) -- and the scale record q of (dscales | dmeans)
+// dsc / dmu (optional, both or none): the backward of the same element in the same pass -- gauss_bwd_elem, which gc_backward_kernel
+// calls, on the values this thread already holds (d loss / d likelihood is known here: coef / lik) -- and the scale record q of (dscales | dmeans)
 __global__ __launch_bounds__(256) void gc_forward_train_kernel(const float *y, NoiseSrc nl, const float *scales, const float *means,
                                                                int ldsm, float *out, float *lik, float *dlik, double *part,
                                                                size_t npix, int C, float sb, float lb, float coef, float *dsc, float *dmu,
@@ -818,36 +752,18 @@ __global__ __launch_bounds__(256) void gc_forward_train_kernel(const float *y, N
         const size_t pix = i / C;
         const int c = (int)(i - pix * C);
         const float mu = means[pix * ldsm + c], sc = scales[pix * ldsm + c];
-        float o = y[i];
-        if (nl.ptr) {
-            o += nl.ptr[i];
-        } else {
-            float r[4];
-            philox4(nl.seed, noise_base(nl) + (i >> 2), r);
-            o += r[i & 3];
-        }
+        const float o = y[i] + noise_at(nl, i, i);
         out[i] = o;
-        const float v = fabsf(o - mu);
-        const float s = fmaxf(sc, sb);
-        const float l = fmaxf(std_cum((0.5f - v) / s) - std_cum((-0.5f - v) / s), lb);
+        const float d = o - mu;
+        const float l = gauss_lik(fabsf(d), sc, sb, lb);
         lik[i] = l;
         dlik[i] = coef / l;
         lg = (double)log2f(l);
         if (dsc) {
-            const float d = o - mu;
-            const float a = (0.5f - v) / s, b = (-0.5f - v) / s;
-            const float lraw = std_cum(a) - std_cum(b);
-            float g = coef / l;
-            if (!(lraw >= lb || g < 0.f)) g = 0.f;
-            const float k = 0.39894228040143267794f;
-            const float pa = k * expf(-0.5f * a * a), pb = k * expf(-0.5f * b * b);
-            const float dv = g * (-(pa - pb) / s);
-            float ds = g * (-(pa * a - pb * b) / s);
-            const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-            if (!(sc >= sb || ds < 0.f)) ds = 0.f;
+            float ds, dvs;
+            gm = gauss_bwd_elem(d, sc, coef / l, sb, lb, ds, dvs);
             dsc[pix * ldd + c] = ds;
-            dmu[pix * ldd + c] = -dv * sgn;
-            gm = fmaxf(fabsf(ds), fabsf(dv));
+            dmu[pix * ldd + c] = -dvs;
         }
     }
     block_log2_partial(lg, part);

@@ -7,84 +7,22 @@
 // has exactly one writer.  Where the channel count and every pitch of a call are multiples of 4 (and the bases 16-byte aligned)
 // a thread moves one float4 per tensor; any other call takes one float per thread.
 //
-// The per-element expressions are entropy.hip:336-388's, in that order, with mu = 0 folded (x - 0 and |x - 0| are x and |x| in fp32),
-// compiled under the same flags: the results compare equal to the mean kernels fed zeros, and the backward's bit for bit
-// (tests/test_hip_hyperprior_ops.py) -- the backward body with contraction off, which is how gc_backward_kernel comes out of the
-// compiler and how the four-element form does not (gcs_backward_elem).  The one place where a zero mean is NOT the identity is the eval-mode output: rintf(y - 0) + 0
-// turns -0.0 into +0.0, rintf(y) keeps it, which is what the reference's means=None branch returns.
+// The per-element expressions and the noise stream are the header's (entropy_elem.h: gauss_lik, gauss_bwd_elem, noise_at), the ones
+// the mean kernels of entropy.hip call, here with the centred value d = out (a zero mean): the results compare equal to the mean
+// kernels fed zeros, and the backward's bit for bit (tests/test_hip_hyperprior_ops.py).  The one place where a zero mean is NOT the
+// identity is the eval-mode output: rintf(y - 0) + 0 turns -0.0 into +0.0, rintf(y) keeps it, which is what the reference's
+// means=None branch returns -- so the quantisation is written here.
 #include "stem_common.h"
+#include "entropy_elem.h"
 #include "../../include/stem_hyperprior.h"
 
 namespace {
 
-// ---- entropy.hip's helpers, restated (anonymous namespace there) --------------------------------------------------------------
-__device__ __forceinline__ float std_cum(float x) { return 0.5f * erfcf(-0.70710678118654752440f * x); }
-
-// Philox4x32-10
-__device__ __forceinline__ void philox_round(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t k0, uint32_t k1)
-{
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-}
-__device__ __forceinline__ void philox4(uint64_t seed, uint64_t ctr, float r[4])
-{
-    uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0, c3 = 0;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int q = 0; q < 10; ++q) {
-        philox_round(c0, c1, c2, c3, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    const uint32_t v[4] = {c0, c1, c2, c3};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = (float)(v[e] >> 8) * (1.0f / 16777216.0f) - 0.5f;      // == noise_kernel
-}
-
-struct NoiseSrc {            // either an explicit tensor (parity tests, injected sources) or the Philox stream
-    const float *ptr;
-    uint64_t seed, offset, stride;
-    const long long *epoch;
-};
-__device__ __forceinline__ uint64_t noise_base(const NoiseSrc &s) { return s.offset + (s.epoch ? (uint64_t)s.epoch[0] * s.stride : 0); }
-
-// ---- one element ------------------------------------------------------------------------------------------------------------
-// gc_forward_kernel (entropy.hip:346-356) with mu = 0
+// ---- one element: quantise (noise nv | round), then the likelihood at |out| ---------------------------------------------------
 __device__ __forceinline__ void gcs_forward_elem(float yv, float nv, float sc, int mode, float sb, float lb, float &o, float &lik)
 {
-    o = yv;
-    if (mode == 0)
-        o += nv;
-    else
-        o = rintf(o);
-    const float v = fabsf(o);
-    const float s = fmaxf(sc, sb);
-    const float l = std_cum((0.5f - v) / s) - std_cum((-0.5f - v) / s);
-    lik = fmaxf(l, lb);
-}
-
-// gc_backward_kernel (entropy.hip:369-385) with mu = 0; -> max(|ds|, |dv|), the element's entry in the scale record.
-// Contraction is off in this body: gc_backward_kernel as compiled rounds every product (pa * a and pb * b share one packed
-// multiply there, so neither is fused into the subtraction), while four elements side by side invite a packed FMA for pa * a - pb * b.
-__device__ __forceinline__ float gcs_backward_elem(float o, float sc, float g, float sb, float lb, float &ds_out, float &dy_out)
-{
-#pragma clang fp contract(off)
-    const float d = o, v = fabsf(d);
-    const float s = fmaxf(sc, sb);
-    const float a = (0.5f - v) / s, b = (-0.5f - v) / s;
-    const float lraw = std_cum(a) - std_cum(b);
-    if (!(lraw >= lb || g < 0.f)) g = 0.f;
-    const float k = 0.39894228040143267794f;
-    const float pa = k * expf(-0.5f * a * a), pb = k * expf(-0.5f * b * b);
-    const float dv = g * (-(pa - pb) / s);
-    float ds = g * (-(pa * a - pb * b) / s);
-    const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-    if (!(sc >= sb || ds < 0.f)) ds = 0.f;
-    ds_out = ds;
-    dy_out = dv * sgn;
-    return fmaxf(fabsf(ds), fabsf(dv));
+    o = mode == 0 ? yv + nv : rintf(yv);
+    lik = gauss_lik(fabsf(o), sc, sb, lb);
 }
 
 // ---- addressing: logical element i = pix * C + c of a tensor with pixel pitch ld ------------------------------------------------
@@ -141,16 +79,7 @@ __global__ __launch_bounds__(256) void gc_scale_forward_kernel(const float *__re
         *reinterpret_cast<f32x4 *>(out + at(p, i, pix, c, ldo)) = o;
         *reinterpret_cast<f32x4 *>(lik + at(p, i, pix, c, ldl)) = l;
     } else {
-        float nv = 0.f;
-        if (mode == 0) {
-            if (nl.ptr) {
-                nv = nl.ptr[at(p, i, pix, c, ldn)];
-            } else {
-                float r[4];
-                philox4(nl.seed, noise_base(nl) + (i >> 2), r);
-                nv = r[i & 3];
-            }
-        }
+        const float nv = mode == 0 ? noise_at(nl, i, at(p, i, pix, c, ldn)) : 0.f;
         float o, l;
         gcs_forward_elem(y[at(p, i, pix, c, ldy)], nv, scales[at(p, i, pix, c, lds)], mode, sb, lb, o, l);
         out[at(p, i, pix, c, ldo)] = o;
@@ -183,7 +112,7 @@ __global__ __launch_bounds__(256) void gc_scale_backward_kernel(const float *__r
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float dse, de;
-                m = fmaxf(m, gcs_backward_elem(o[e], sc[e], g[e], sb, lb, dse, de));
+                m = fmaxf(m, gauss_bwd_elem(o[e], sc[e], g[e], sb, lb, dse, de));
                 ds[e] = dse;
                 d[e] = de;
             }
@@ -198,7 +127,7 @@ __global__ __launch_bounds__(256) void gc_scale_backward_kernel(const float *__r
             }
         } else {
             float ds, d;
-            m = gcs_backward_elem(out[at(p, i, pix, c, ldo)], scales[at(p, i, pix, c, lds)], dlik[at(p, i, pix, c, ldl)], sb, lb, ds, d);
+            m = gauss_bwd_elem(out[at(p, i, pix, c, ldo)], scales[at(p, i, pix, c, lds)], dlik[at(p, i, pix, c, ldl)], sb, lb, ds, d);
             if (dsc) dsc[at(p, i, pix, c, ldds)] = ds;
             if (dy) dy[at(p, i, pix, c, lddy)] = dout ? __fadd_rn(d, dout[at(p, i, pix, c, ldg)]) : d;
         }

@@ -247,6 +247,63 @@ def test_gc_forward_train_vs_float64(F, shape):
     assert len(plain) == 4 and all(torch.equal(a, b) for a, b in zip(plain, (out, lik, dlik, part)))
 
 
+def bits(t):
+    """flat(t) as int32: what "bit-identical" compares (-0.0 differs from +0.0, a NaN equals itself)"""
+    return flat(t).view(np.int32)
+
+
+@pytest.mark.parametrize("shape", [ref.TAIL_SHAPES[0], ref.TAIL_SHAPES[3]], ids=_tail_id)
+def test_gc_fused_backward_is_the_stand_alone_backward(F, shape):
+    """the backward that gc_forward_train folds in and gc_backward run on the fused call's own out and dlik are one element function
+    (csrc/entropy_elem.h: gauss_bwd_elem): dscales, dmeans and the whole scale record bit for bit.  The inputs of
+    test_gc_forward_train_vs_float64: a partial last workgroup, a quarter of the scales below the bound, likelihoods at the floor, and
+    out == mean in the first shape."""
+    B, H, W, C = shape
+    n = B * H * W
+    tie = shape == ref.TAIL_SHAPES[0]
+    coef = -1.0 / (math.log(2.0) * n)
+    y, noise, sc, mu = ref.gc_inputs(B, H, W, C, 41, tie=tie)
+    assert (n * C) % 256 != 0 and (sc < 0.11).mean() > 0.2
+    gp = nhwc(np.concatenate([sc, mu], axis=1), B, H, W)
+    fused, alone = (nhwc(np.full((n, 2 * C), np.nan, np.float32), B, H, W) for _ in range(2))
+    out, lik, dlik, _, q = F.gc_forward_train(nhwc(y, B, H, W), gp[:, :C], gp[:, C:], coef, noise=nhwc(noise, B, H, W),
+                                              backward=(fused[:, :C], fused[:, C:]), record=True)
+    assert (flat(lik) == np.float32(1e-9)).sum() >= n * C // 20 and bool((flat(out) == mu).any()) == tie
+    q_alone = F.gc_backward(out, gp[:, :C], gp[:, C:], dlik, alone[:, :C], alone[:, C:], record=True)
+    assert not np.isnan(flat(fused)).any()
+    assert np.array_equal(bits(fused[:, :C]), bits(alone[:, :C])), "dscales"
+    assert np.array_equal(bits(fused[:, C:]), bits(alone[:, C:])), "dmeans"
+    assert q.numel() == q_alone.numel() == 16 + (n * C + 255) // 256
+    assert torch.equal(q.view(torch.int32), q_alone.view(torch.int32)), "scale record"
+
+
+EB_CM_MAX_PIX = 4096         # stem_eb_forward / stem_eb_forward_train: up to this many pixels the one-workgroup-per-channel kernel runs
+
+
+@pytest.mark.parametrize("shape", [ref.TAIL_SHAPES[0], ref.TAIL_SHAPES[2]], ids=_tail_id)
+def test_eval_and_train_likelihoods_are_one_expression(F, shape):
+    """gc_forward and eb_forward in noise mode with an explicit tensor against gc_forward_train / eb_forward_train fed the same
+    tensor: the quantised values and the likelihoods bit for bit.  198 and 4160 pixels per channel: the per-channel and the
+    per-element kernel of each bottleneck pair."""
+    small, large = (s[0] * s[1] * s[2] for s in (ref.TAIL_SHAPES[0], ref.TAIL_SHAPES[2]))
+    assert small <= EB_CM_MAX_PIX < large
+    B, H, W, C = shape
+    coef = -1.0 / (math.log(2.0) * B * H * W)
+    y, noise, sc, mu = ref.gc_inputs(B, H, W, C, 41)
+    gp = nhwc(np.concatenate([sc, mu], axis=1), B, H, W)
+    yd, nd = nhwc(y, B, H, W), nhwc(noise, B, H, W)
+    out_e, lik_e = F.gc_forward(yd, gp[:, :C], gp[:, C:], noise=nd)
+    out_t, lik_t = F.gc_forward_train(yd, gp[:, :C], gp[:, C:], coef, noise=nd)[:2]
+    assert np.array_equal(bits(out_e), bits(out_t)) and np.array_equal(bits(lik_e), bits(lik_t)), "gc"
+    assert (flat(lik_e) == np.float32(1e-9)).any() and (flat(lik_e) > np.float32(1e-9)).any()
+    z, znoise = ref.eb_inputs(B, H, W, C, 31)
+    zd, znd, pd = nhwc(z, B, H, W, ld=C + 3, c0=1), nhwc(znoise, B, H, W), vec(ref.eb_random_pack(C, 32))
+    zhat_e, zlik_e = F.eb_forward(zd, pd, noise=znd)
+    zhat_t, zlik_t = F.eb_forward_train(zd, pd, coef, noise=znd)[:2]
+    assert np.array_equal(bits(zhat_e), bits(zhat_t)) and np.array_equal(bits(zlik_e), bits(zlik_t)), "eb"
+    assert (flat(zlik_e) == np.float32(1e-9)).any() and (flat(zlik_e) > np.float32(1e-9)).any()
+
+
 # =========================================================================================================== 4. loss reductions
 def test_em_loss_finalize(F):
     """out = scale * (sum py, sum pz, both), double: against exactly rounded sums.  Any summation order of n doubles is within
