@@ -754,7 +754,7 @@ struct TileCfg {
     int bm, bn;
     float eff;
 };
-// relative efficiencies measured on MI355X with STEM_IGEMM_CFG sweeps of tools/kernel_bench.py (padding-free shapes)
+// relative efficiencies measured on MI355X with stem_tuning_set("igemm_cfg") sweeps of tools/kernel_bench.py (padding-free shapes)
 constexpr int NCFG = 6;
 constexpr TileCfg kCfg[NCFG] = {{128, 128, 0.88f}, {64, 192, 0.95f}, {128, 64, 0.85f}, {64, 64, 0.90f},
                                 {128, 192, 1.00f} /* 8 waves */, {128, 128, 0.97f} /* 8 waves */};
@@ -784,12 +784,12 @@ Plan make_plan(const IgemmArgs &g, bool c4, int only_cfg = -1)
     const bool can_split = g.epi != EPI_GDN && g.epi != EPI_IGDN && g.epi != EPI_NORM && !c4 && !g.fuse;
     // MFMA-bound model: time ~ (workgroups on the most loaded CU) x (chunks + fixed prologue/epilogue) x tile / efficiency
     double best = 1e300;
-    static const int forced = getenv("STEM_IGEMM_CFG") ? atoi(getenv("STEM_IGEMM_CFG")) : -1;     // tuning aid
+    const int forced = stem_tuning(STEM_TUNE_IGEMM_CFG) - 1;            // stem_tuning_set("igemm_cfg", 1..6): tests / sweeps
+    const int fuse_cfg = stem_tuning(STEM_TUNE_IGEMM_FUSE_CFG) - 1;     // stem_tuning_set("igemm_fuse_cfg", 2 | 5)
     for (int c = 0; c < NCFG; ++c) {
         if (only_cfg >= 0 && c != only_cfg) continue;
         if (forced >= 0 && only_cfg < 0 && c != forced && !g.fuse) continue;
         if (g.fuse && !((c == 1 || c == 4) && kCfg[c].bn >= g.N)) continue;      // fused GDN: all channels in one 192-wide tile
-        static const int fuse_cfg = getenv("STEM_IGEMM_FUSE_CFG") ? atoi(getenv("STEM_IGEMM_FUSE_CFG")) : -1;     // tuning aid
         if (g.fuse && fuse_cfg >= 0 && c != fuse_cfg) continue;
         const long tm = cdiv(maxM, kCfg[c].bm), tn = cdiv(g.N, kCfg[c].bn);
         const long tiles = tm * tn * g.nphase;
@@ -826,7 +826,7 @@ Plan make_plan(const IgemmArgs &g, bool c4, int only_cfg = -1)
             }
         }
     }
-    static const int forced_split = getenv("STEM_IGEMM_SPLIT") ? atoi(getenv("STEM_IGEMM_SPLIT")) : 0;      // tuning aid
+    const int forced_split = stem_tuning(STEM_TUNE_IGEMM_SPLIT);        // stem_tuning_set("igemm_split", n): tests / sweeps
     if (forced_split > 0 && can_split) pl.nsplit = forced_split < maxchunks ? forced_split : maxchunks;
     pl.cps = cdiv(maxchunks, pl.nsplit);
     pl.nsplit = cdiv(maxchunks, pl.cps);           // drop empty trailing splits
@@ -912,6 +912,8 @@ int run_plan(IgemmArgs &g, const Plan &pl, bool vec, bool c4, void *ws, hipStrea
     g.cnt = (int *)ws;                                        // [kCntBytes] arrival counters, then the partial slabs
     g.ws = (float *)((char *)ws + kCntBytes);
     g.slab = (long)g.B * g.OH * g.OW * g.N;
+    stem_ran_note(STEM_RAN_IGEMM_CFG, pl.cfg + 1);            // test aids: stem_tuning_get("igemm_ran_cfg" | "igemm_ran_split")
+    stem_ran_note(STEM_RAN_IGEMM_SPLIT, pl.nsplit);
     int rc;
     switch (pl.cfg) {
     case 0: rc = launch_cfg<128, 128, 64, 64>(g, vec, c4, st); break;

@@ -17,11 +17,17 @@ STEM_EXPORT const char *stem_last_error(void) { return g_err; }
 STEM_EXPORT int stem_abi_version(void) { return 5; }      // 5 (round 5): + stem_tconv2d_f16x3_*, stem_conv2d_wgrad_f16x3_strided, stem_f16x2_pack_conv_weights_pair_multi, stem_tape_set_farg, stem_tape_entry_recordable, stem_zero_bytes, stem_stream_flag_*; stem_f16x2_pack_desc.flip = 2
 
 static int g_tuning[STEM_TUNE_COUNT] = {0};
-static const char *const kTuningNames[STEM_TUNE_COUNT] = {"fx3_tile", "fx3_split", "wg3_split", "arp_workers", "fx3_depth", "fx3_gen_tile", "fx3_mfma", "fx3_gen_mfma", "fx3_gen_img", "fx3_img_w", "wg3_row", "wg3_minch", "tconv_cps", "arp_giveup_at", "unpack_mb"};
+static const char *const kTuningNames[STEM_TUNE_COUNT] = {"fx3_tile", "fx3_split", "wg3_split", "arp_workers", "fx3_depth", "fx3_gen_tile", "fx3_mfma", "fx3_gen_mfma", "fx3_gen_img", "fx3_img_w", "wg3_row", "wg3_minch", "tconv_cps", "arp_giveup_at", "unpack_mb", "igemm_cfg", "igemm_fuse_cfg", "igemm_split", "wgrad_cfg"};
+// test aids (get-only): the plan of the most recent launch of the fp32-MFMA convolution / weight-gradient family
+static int g_ran[STEM_RAN_COUNT] = {0};
+static const char *const kRanNames[STEM_RAN_COUNT] = {"igemm_ran_cfg", "igemm_ran_split", "wgrad_ran_cfg"};
+void stem_ran_note(int id, int value) { g_ran[id] = value; }
 int stem_tuning(int id) { return g_tuning[id]; }
 STEM_EXPORT int stem_tuning_set(const char *name, int value)
 {
     STEM_CHECK_ARG(name && value >= 0, "stem_tuning_set: null name or negative value");
+    for (int i = 0; i < STEM_RAN_COUNT; ++i)
+        STEM_CHECK_ARG(strcmp(name, kRanNames[i]), "stem_tuning_set: %s is get-only (the plan of the most recent launch)", name);
     for (int i = 0; i < STEM_TUNE_COUNT; ++i)
         if (!strcmp(name, kTuningNames[i])) {
             STEM_CHECK_ARG(i != STEM_TUNE_FX3_TILE || value == 0 || value == 64 || value == 128, "stem_tuning_set: fx3_tile is 0 (automatic), 64 or 128");
@@ -30,16 +36,21 @@ STEM_EXPORT int stem_tuning_set(const char *name, int value)
             STEM_CHECK_ARG(i != STEM_TUNE_FX3_GEN_MFMA || value == 0 || value == 16 || value == 32, "stem_tuning_set: fx3_gen_mfma is 0 (automatic), 16 or 32 (rows of the general kernel's MFMA shape)");
             STEM_CHECK_ARG(i != STEM_TUNE_UNPACK_MB || value == 0 || (value % 32 == 0 && value >= 32 && value <= 192), "stem_tuning_set: unpack_mb is 0 (automatic) or a multiple of 32 up to 192");
             STEM_CHECK_ARG(i != STEM_TUNE_FX3_MFMA || value == 0 || value == 16 || value == 32, "stem_tuning_set: fx3_mfma is 0 (automatic), 16 or 32 (rows of the MFMA shape)");
+            STEM_CHECK_ARG(i != STEM_TUNE_IGEMM_CFG || value <= 6, "stem_tuning_set: igemm_cfg is 0 (automatic) or 1..6 (tile 128x128, 64x192, 128x64, 64x64, 128x192 / 8 waves, 128x128 / 8 waves)");
+            STEM_CHECK_ARG(i != STEM_TUNE_IGEMM_FUSE_CFG || value == 0 || value == 2 || value == 5, "stem_tuning_set: igemm_fuse_cfg is 0 (automatic), 2 or 5 (the 192-wide tiles 64x192 and 128x192 of the fused-GDN kernels)");
+            STEM_CHECK_ARG(i != STEM_TUNE_WGRAD_CFG || value <= 5, "stem_tuning_set: wgrad_cfg is 0 (automatic) or 1..5 (tile 128x128, 128x64, 64x128, 64x64, 128x128 / 8 waves)");
             g_tuning[i] = value;
             return 0;
         }
-    stem_set_error("stem_tuning_set: unknown selector '%s' (fx3_tile, fx3_split, wg3_split, arp_workers, fx3_depth, fx3_gen_tile, fx3_mfma, fx3_gen_mfma, fx3_gen_img, fx3_img_w, wg3_row, wg3_minch, tconv_cps, arp_giveup_at, unpack_mb)", name);
+    stem_set_error("stem_tuning_set: unknown selector '%s' (fx3_tile, fx3_split, wg3_split, arp_workers, fx3_depth, fx3_gen_tile, fx3_mfma, fx3_gen_mfma, fx3_gen_img, fx3_img_w, wg3_row, wg3_minch, tconv_cps, arp_giveup_at, unpack_mb, igemm_cfg, igemm_fuse_cfg, igemm_split, wgrad_cfg)", name);
     return -1;
 }
 STEM_EXPORT int stem_tuning_get(const char *name)
 {
     for (int i = 0; name && i < STEM_TUNE_COUNT; ++i)
         if (!strcmp(name, kTuningNames[i])) return g_tuning[i];
+    for (int i = 0; name && i < STEM_RAN_COUNT; ++i)
+        if (!strcmp(name, kRanNames[i])) return g_ran[i];
     return -1;
 }
 

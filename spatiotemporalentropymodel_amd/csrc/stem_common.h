@@ -39,7 +39,13 @@ static inline size_t cdivz(size_t a, size_t b) { return (a + b - 1) / b; }
 // Plan selectors (a tile shape, a split factor: every choice computes the same contraction, differing at most in summation
 // order) are integers set through the exported stem_tuning_set() -- tests and sweep tools use them; nothing reads the
 // environment per launch.
-enum { STEM_TUNE_FX3_TILE = 0, STEM_TUNE_FX3_SPLIT, STEM_TUNE_WG3_SPLIT, STEM_TUNE_ARP_WORKERS, STEM_TUNE_FX3_DEPTH, STEM_TUNE_FX3_GEN_TILE, STEM_TUNE_FX3_MFMA, STEM_TUNE_FX3_GEN_MFMA, STEM_TUNE_FX3_GEN_IMG, STEM_TUNE_FX3_IMG_W, STEM_TUNE_WG3_ROW, STEM_TUNE_WG3_MINCH, STEM_TUNE_TCONV_CPS, STEM_TUNE_ARP_GIVEUP_AT, STEM_TUNE_UNPACK_MB, STEM_TUNE_COUNT };
+enum { STEM_TUNE_FX3_TILE = 0, STEM_TUNE_FX3_SPLIT, STEM_TUNE_WG3_SPLIT, STEM_TUNE_ARP_WORKERS, STEM_TUNE_FX3_DEPTH, STEM_TUNE_FX3_GEN_TILE, STEM_TUNE_FX3_MFMA, STEM_TUNE_FX3_GEN_MFMA, STEM_TUNE_FX3_GEN_IMG, STEM_TUNE_FX3_IMG_W, STEM_TUNE_WG3_ROW, STEM_TUNE_WG3_MINCH, STEM_TUNE_TCONV_CPS, STEM_TUNE_ARP_GIVEUP_AT, STEM_TUNE_UNPACK_MB, STEM_TUNE_IGEMM_CFG, STEM_TUNE_IGEMM_FUSE_CFG, STEM_TUNE_IGEMM_SPLIT, STEM_TUNE_WGRAD_CFG, STEM_TUNE_COUNT };
+// fp32-MFMA family (igemm.hip / wgrad.hip): igemm_cfg 1..6 = tile configuration 0..5, igemm_fuse_cfg 2 | 5 = the fused-GDN tile
+// 1 | 4, igemm_split n >= 1 (clamped to the chunk count; layers that cannot split ignore it), wgrad_cfg 1..5 = tile 0..4; 0 =
+// the planner's choice.  Test aids, get-only (stem_tuning_get; stem_tuning_set refuses them): the plan of this process's most
+// recent launch of the family -- "igemm_ran_cfg" / "wgrad_ran_cfg" (1-based tile index), "igemm_ran_split" (effective splits).
+enum { STEM_RAN_IGEMM_CFG = 0, STEM_RAN_IGEMM_SPLIT, STEM_RAN_WGRAD_CFG, STEM_RAN_COUNT };
+void stem_ran_note(int id, int value);
 int stem_tuning(int id);
 // image-tile form of the general split-operand convolution (conv_f16x3_img.hip), dispatched from stem_conv2d_f16x3_gen_fwd
 bool stem_fx3_img_eligible(int B, int H, int W, int N, int R, int S, int stride, int pad);

@@ -400,7 +400,7 @@ void plan(int CP, int CG, int T, int nchunks, int *cfg, int *splits)
     const int slots[NCFG] = {512, 768, 768, 1280, 512};      // co-resident workgroups (LDS: 64 / 48 / 48 / 32 / 64 KiB)
     const int wps[NCFG] = {1, 1, 1, 1, 2};                   // wavefronts per SIMD contributed by one workgroup
     static const float eff4 = getenv("STEM_WGRAD_EFF4") ? (float)atof(getenv("STEM_WGRAD_EFF4")) : kWT[4].eff;     // tuning aid
-    static const int forced = getenv("STEM_WGRAD_CFG") ? atoi(getenv("STEM_WGRAD_CFG")) : -1;      // tuning aid
+    const int forced = stem_tuning(STEM_TUNE_WGRAD_CFG) - 1;      // stem_tuning_set("wgrad_cfg", 1..5): tests / sweeps
     for (int c = 0; c < NCFG; ++c) {
         if (forced >= 0 && c != forced) continue;
         const float eff = c == 4 ? eff4 : kWT[c].eff;
@@ -475,7 +475,9 @@ int run(const float *p, int ldp, int CP, const float *g, int ldg, int CG, float 
     const bool vec = wgrad_vec_ok(p, ldp, CP, g, ldg, CG);
     int cfg, s_unused;
     plan(CP, CG, R * S, a.nchunks, &cfg, &s_unused);
-    if (vec && CG == 4 && ldg == 4 && !a.gsq && R * S <= 32) return launch_c4(a, st);
+    const bool c4 = vec && CG == 4 && ldg == 4 && !a.gsq && R * S <= 32;      // folded taps: its own 64x64 kernel
+    stem_ran_note(STEM_RAN_WGRAD_CFG, c4 ? 4 : cfg + 1);      // test aid: stem_tuning_get("wgrad_ran_cfg")
+    if (c4) return launch_c4(a, st);
     switch (cfg) {
     case 0: return launch_cfg<128, 128, 64, 64>(a, vec, st);
     case 1: return launch_cfg<128, 64, 64, 32>(a, vec, st);

@@ -211,11 +211,14 @@ def _ptr(t):
 
 class tuning:
     """`with F.tuning(fx3_split=3): ...` -- force a plan selector of the library (stem_tuning_set: "fx3_tile", "fx3_split",
-    "wg3_split") for the calls inside the block; tests and sweep tools only.  The workspace-size cache of the general fp16
-    kernel depends on the split factor and is dropped on entry and exit."""
+    "wg3_split", "igemm_cfg", "igemm_split", "wgrad_cfg", ...) for the calls inside the block; tests and sweep tools only.  The
+    workspace-size cache of the general fp16 kernel depends on the split factor and is dropped on entry and exit; so is the
+    fp32-MFMA family's (_WS_BYTES) whenever an igemm_* selector is among the keywords -- a plan forced after a geometry's first
+    call would otherwise get the earlier plan's workspace and run unsplit."""
 
     def __init__(self, **kv):
         self.kv, self.old = kv, {}
+        self.igemm = any(k.startswith("igemm_") for k in kv)
 
     def __enter__(self):
         lib = _lib.hip()
@@ -223,6 +226,8 @@ class tuning:
             self.old[k] = int(lib.stem_tuning_get(k.encode()))
             _chk(lib.stem_tuning_set(k.encode(), int(v)))
         _WS_GEN_BYTES.clear()
+        if self.igemm:
+            _WS_BYTES.clear()
         return self
 
     def __exit__(self, *exc):
@@ -231,6 +236,8 @@ class tuning:
             if v >= 0:
                 lib.stem_tuning_set(k.encode(), v)
         _WS_GEN_BYTES.clear()
+        if self.igemm:
+            _WS_BYTES.clear()
         return False
 
 
@@ -432,17 +439,22 @@ def conv2d_dgrad(dy, wp_dgrad, x_shape, K, R, S, stride, pad, xact=None, out=Non
     return out
 
 
-def wgrad_plan(x_shape, K, R, S, stride, pad, deconv=False):
-    """(splits, slab-buffer elements) for a weight-gradient launch on this input shape."""
+def wgrad_plan(x_shape, K, R, S, stride, pad, deconv=False, splits=None):
+    """(splits, slab-buffer elements) for a weight-gradient launch on this input shape; `splits` replaces the planner's count."""
     B, Cc, H, W = x_shape
     lib = _lib.hip()
     if deconv:
-        splits = lib.stem_wgrad_splits(B, H, W, K, Cc, R, S)
         npix = B * H * W
+        if splits is None:
+            splits = lib.stem_wgrad_splits(B, H, W, K, Cc, R, S)
     else:
         Ho, Wo = conv_out_hw(H, W, R, S, stride, pad)
-        splits = lib.stem_wgrad_splits(B, Ho, Wo, Cc, K, R, S)
         npix = B * Ho * Wo
+        if splits is None:
+            splits = lib.stem_wgrad_splits(B, Ho, Wo, Cc, K, R, S)
+    splits = int(splits)
+    if splits < 1:
+        raise ValueError(f"weight-gradient split count must be >= 1, got {splits}")
     return splits, int(lib.stem_wgrad_workspace_elems(splits, Cc, K, R, S, npix))
 
 
@@ -453,7 +465,8 @@ UNPACK_DECONV, UNPACK_ACCUMULATE = 1, 2
 
 def _wgrad_workspace(key, elems, device):
     """Slab / partial-sum / gather-table scratch of one layer geometry.  Kernels of a stream are ordered, so every layer
-    with this geometry shares the buffer, and its gather table (a function of the geometry only) is built once."""
+    with this geometry shares the buffer, and its gather table (a function of the geometry only) is built once.  The split
+    count is part of the key: the table sits behind the slabs."""
     key = key + (_stream(),)                 # one buffer per launching stream: ordering is only guaranteed within a stream
     hit = _WGRAD_WS.get(key)
     if hit is not None and hit.numel() >= elems:
@@ -470,15 +483,16 @@ def _deferred_bias(lib, x, dy, dwp, db, K, Cc, R, S, splits, flags, acc, deconv)
 
 
 def conv2d_wgrad(x, dy, K, R, S, stride, pad, dw_out=None, db_out=None, need_db=True, dwp=None, unpack=True, table_valid=False,
-                 accumulate=False, accumulate_db=False, defer_bias=False):
+                 accumulate=False, accumulate_db=False, defer_bias=False, splits=None):
     """-> (dW [K,C,R,S], db [K]) in the reference's layouts.  With unpack=False only the packed slabs in `dwp`
     are produced (the caller sums/transposes all layers at once with unpack_wgrads_multi).  accumulate=True adds into
-    dw_out / db_out (gradient accumulation over several backward passes)."""
+    dw_out / db_out (gradient accumulation over several backward passes).  splits: pixel-split count in place of the planner's
+    (tests / sweeps; the workspace is sized with it, a caller-supplied `dwp` must be too)."""
     B, Cc, H, W = x.shape
     lib = _lib.hip()
-    splits, elems = wgrad_plan(x.shape, K, R, S, stride, pad)
+    splits, elems = wgrad_plan(x.shape, K, R, S, stride, pad, splits=splits)
     if dwp is None:
-        dwp, table_valid = _wgrad_workspace((x.device, 0, tuple(x.shape), nhwc_ld(x), K, R, S, stride, pad), elems, x.device)
+        dwp, table_valid = _wgrad_workspace((x.device, 0, tuple(x.shape), nhwc_ld(x), K, R, S, stride, pad, splits), elems, x.device)
     assert not accumulate or (dw_out is not None and (db_out is not None or not need_db))
     db = (db_out if db_out is not None else torch.empty(K, device=x.device, dtype=torch.float32)) if need_db else None
     assert not accumulate_db or db_out is not None
@@ -521,13 +535,13 @@ def deconv2d_dgrad(dy, wp_dgrad, x_shape, K, R, S, stride, pad, opad, xact=None,
 
 
 def deconv2d_wgrad(x, dy, K, R, S, stride, pad, opad, dw_out=None, db_out=None, need_db=True, dwp=None, unpack=True, table_valid=False,
-                   accumulate=False, accumulate_db=False, defer_bias=False):
-    """-> (dW [C,K,R,S], db [K]) in nn.ConvTranspose2d's layout."""
+                   accumulate=False, accumulate_db=False, defer_bias=False, splits=None):
+    """-> (dW [C,K,R,S], db [K]) in nn.ConvTranspose2d's layout.  splits: as conv2d_wgrad."""
     B, Cc, H, W = x.shape
     lib = _lib.hip()
-    splits, elems = wgrad_plan(x.shape, K, R, S, stride, pad, deconv=True)
+    splits, elems = wgrad_plan(x.shape, K, R, S, stride, pad, deconv=True, splits=splits)
     if dwp is None:
-        dwp, table_valid = _wgrad_workspace((x.device, 1, tuple(x.shape), nhwc_ld(dy), K, R, S, stride, pad, opad), elems, x.device)
+        dwp, table_valid = _wgrad_workspace((x.device, 1, tuple(x.shape), nhwc_ld(dy), K, R, S, stride, pad, opad, splits), elems, x.device)
     assert not accumulate or (dw_out is not None and (db_out is not None or not need_db))
     db = (db_out if db_out is not None else torch.empty(K, device=x.device, dtype=torch.float32)) if need_db else None
     assert not accumulate_db or db_out is not None

@@ -77,10 +77,27 @@ def test_shipped_library_has_no_result_changing_switches():
     lib = _lib.hip()
     blob = open(_lib.HIP_SO, "rb").read()
     for name in (b"STEM_BF16_PRODUCTS", b"STEM_GA_BF16_PRODUCTS", b"STEM_BF16_PRODUCTS_DYN", b"STEM_IGEMM_EXPER", b"STEM_FX3_EXPER",
-                 b"STEM_FX3_SPLIT", b"STEM_WG3_SPLIT", b"stem_exper_", b"STEM_EXPERIMENTS"):
+                 b"STEM_FX3_SPLIT", b"STEM_WG3_SPLIT", b"stem_exper_", b"STEM_EXPERIMENTS",
+                 b"STEM_IGEMM_CFG", b"STEM_IGEMM_FUSE_CFG", b"STEM_IGEMM_SPLIT", b"STEM_WGRAD_CFG"):
         assert name not in blob, name
     assert lib.stem_tuning_get(b"fx3_split") == 0 and lib.stem_tuning_get(b"no_such") == -1
     assert lib.stem_tuning_set(b"fx3_split", 3) == 0 and lib.stem_tuning_get(b"fx3_split") == 3
     assert lib.stem_tuning_set(b"fx3_split", 0) == 0
     assert lib.stem_tuning_set(b"fx3_tile", 96) != 0 and b"fx3_tile" in lib.stem_last_error()
     assert lib.stem_tuning_set(b"products", 4) != 0
+    # the fp32-MFMA family's plan selectors: round trip, validated with the selector named in the error
+    for name, good, bad in ((b"igemm_cfg", (1, 6), (7,)), (b"igemm_fuse_cfg", (2, 5), (1, 3, 4, 6)), (b"igemm_split", (1, 3, 64), ()),
+                            (b"wgrad_cfg", (1, 5), (6,))):
+        assert lib.stem_tuning_get(name) == 0, name
+        for v in good:
+            assert lib.stem_tuning_set(name, v) == 0 and lib.stem_tuning_get(name) == v, (name, v)
+        for v in bad + (-1,):
+            assert lib.stem_tuning_set(name, v) != 0 and lib.stem_tuning_get(name) == good[-1], (name, v)
+            assert v < 0 or name in lib.stem_last_error(), (name, v, lib.stem_last_error())
+        assert lib.stem_tuning_set(name, 0) == 0 and lib.stem_tuning_get(name) == 0
+    # the plan that ran (test aids): readable (0 until the family's first launch in this process), never settable
+    for name in (b"igemm_ran_cfg", b"igemm_ran_split", b"wgrad_ran_cfg"):
+        before = lib.stem_tuning_get(name)
+        assert before >= 0, name
+        assert lib.stem_tuning_set(name, before + 1) != 0 and name in lib.stem_last_error() and b"get-only" in lib.stem_last_error()
+        assert lib.stem_tuning_set(name, 0) != 0 and lib.stem_tuning_get(name) == before
