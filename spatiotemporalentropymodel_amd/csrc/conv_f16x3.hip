@@ -1253,14 +1253,19 @@ STEM_EXPORT int stem_conv2d_f16x3_gen_fwd(const void *xp, const float *xq, int x
     while (split > 1 && (size_t)split * M * ntn * GBN * sizeof(float) >= 0x7FFFFF00ull) --split;      // the slabs are read through one buffer view
     const size_t need = kGenCntBytes + (size_t)split * M * ntn * GBN * sizeof(float);
     if (split > 1 && (!ws || ws_bytes < need || (size_t)tiles * sizeof(int) > kGenCntBytes)) split = 1;      // no workspace: unsplit, same result up to summation order
+    const int cps = cdiv(nchunks, split), nsplit = cdiv(nchunks, cps);
+    const int gmsel = stem_tuning(STEM_TUNE_FX3_GEN_MFMA);         // MFMA shape: stem_tuning_set("fx3_gen_mfma", 16 | 32); 0 = default
+    const bool g16 = gmsel ? gmsel == 16 : GEN_DEFAULT_MFMA16;
+    stem_ran_note(STEM_RAN_FX3_FORM, img ? 3 : bm == 128 ? 2 : 1);      // test aids: stem_tuning_get("fx3_ran_form" | "fx3_ran_split" | "fx3_ran_mfma")
+    stem_ran_note(STEM_RAN_FX3_SPLIT, nsplit);
+    stem_ran_note(STEM_RAN_FX3_MFMA, !img && g16 ? 16 : 32);
     if (img)
         return stem_fx3_img_launch(xp, xq, xpix, (int)xb, wp, wq, (int)wb,
                                    bias, epi, slope, z, ldz, y, ldy, yp, yq, B, H, W, C, N, R, T, split,
                                    split > 1 ? reinterpret_cast<float *>(static_cast<unsigned char *>(ws) + kGenCntBytes) : nullptr,
                                    split > 1 ? static_cast<int *>(ws) : nullptr, stream);
-    a.nsplit = split;
-    a.cps = cdiv(nchunks, split);
-    a.nsplit = cdiv(nchunks, a.cps);
+    a.cps = cps;
+    a.nsplit = nsplit;
     if (a.nsplit > 1) {
         a.cnt = static_cast<int *>(ws);
         a.ws = reinterpret_cast<float *>(static_cast<unsigned char *>(ws) + kGenCntBytes);
@@ -1274,8 +1279,6 @@ STEM_EXPORT int stem_conv2d_f16x3_gen_fwd(const void *xp, const float *xq, int x
         attr_done = true;
     }
     const dim3 grid(cdiv(M, bm), ntn, a.nsplit);
-    const int gmsel = stem_tuning(STEM_TUNE_FX3_GEN_MFMA);         // MFMA shape: stem_tuning_set("fx3_gen_mfma", 16 | 32); 0 = default
-    const bool g16 = gmsel ? gmsel == 16 : GEN_DEFAULT_MFMA16;
     if (bm == 128 && g16)
         hipLaunchKernelGGL((conv_f16x3_gen_kernel<128, 16>), grid, dim3(512), glds(128), (hipStream_t)stream, a);
     else if (bm == 128)

@@ -44,7 +44,10 @@ enum { STEM_TUNE_FX3_TILE = 0, STEM_TUNE_FX3_SPLIT, STEM_TUNE_WG3_SPLIT, STEM_TU
 // 1 | 4, igemm_split n >= 1 (clamped to the chunk count; layers that cannot split ignore it), wgrad_cfg 1..5 = tile 0..4; 0 =
 // the planner's choice.  Test aids, get-only (stem_tuning_get; stem_tuning_set refuses them): the plan of this process's most
 // recent launch of the family -- "igemm_ran_cfg" / "wgrad_ran_cfg" (1-based tile index), "igemm_ran_split" (effective splits).
-enum { STEM_RAN_IGEMM_CFG = 0, STEM_RAN_IGEMM_SPLIT, STEM_RAN_WGRAD_CFG, STEM_RAN_COUNT };
+// The same for stem_conv2d_f16x3_gen_fwd -- "fx3_ran_form" (1 = conv_f16x3_gen_kernel with 64-pixel tiles, 2 = with 128-pixel
+// tiles, 3 = the image-tile form), "fx3_ran_split" (the split count in the launch arguments: after the cdiv round trip and the
+// "no workspace: unsplit" fallback), "fx3_ran_mfma" (16 | 32 rows of the MFMA shape; the image-tile form has 32 only).
+enum { STEM_RAN_IGEMM_CFG = 0, STEM_RAN_IGEMM_SPLIT, STEM_RAN_WGRAD_CFG, STEM_RAN_FX3_FORM, STEM_RAN_FX3_SPLIT, STEM_RAN_FX3_MFMA, STEM_RAN_COUNT };
 void stem_ran_note(int id, int value);
 int stem_tuning(int id);
 // image-tile form of the general split-operand convolution (conv_f16x3_img.hip), dispatched from stem_conv2d_f16x3_gen_fwd

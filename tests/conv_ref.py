@@ -104,6 +104,13 @@ def mask_a(R, S):
     return m
 
 
+def mask_b(R, S):
+    """type-B mask: the type-A taps and the centre"""
+    m = np.zeros((R, S))
+    m.reshape(-1)[:(R // 2) * S + S // 2 + 1] = 1.0
+    return m
+
+
 def lrelu(v, slope):
     v = _f64(v)
     return np.where(v > 0, v, v * slope)

@@ -139,6 +139,9 @@ def test_general_kernel_per_channel(F, span, case):
     ref = np.where(ref > 0, ref, ref * np.float32(0.01)).astype(np.float32)
     xp = F.F16Planes.split(dev(x))
     y, yp = F.conv2d_f16x3_gen(xp, F.pack_weight_f16x2_gen(dev(w)), dev(b), K, R, R, st, R // 2, epi=F.GEN_EPI_LRELU, want_planes=True)
+    from spatiotemporalentropymodel_amd import _lib
+    form = _lib.hip().stem_tuning_get(b"fx3_ran_form")            # the case's name is checked against the form that ran
+    assert form == 3 if "image-tile form" in case[0] else form in (1, 2), (case[0], form)
     per_channel(host(y), ref, f"{case[0]} forward span 2^-{span}", span=span)
     per_channel(host(yp.merge()), ref, "... its planes output", abs_floor=2.0 ** -24 * yp.record()[0])
     if st == 1:        # input gradient: rows of the flipped image = the layer's input channels c; spread THOSE

@@ -239,6 +239,9 @@ def test_gen_forward_and_input_gradient_vs_oracle(F, case, split, tile, mfma):
     permuted accumulator layout through the split-K slabs and the epilogue tile); planes output = fp32 output."""
     with F.tuning(fx3_split=split, fx3_gen_tile=tile, fx3_gen_mfma=mfma):
         _gen_forward_and_input_gradient(F, case, split)
+        from spatiotemporalentropymodel_amd import _lib
+        form = _lib.hip().stem_tuning_get(b"fx3_ran_form")
+        assert form == {0: form, 64: 1, 128: 2}[tile] and form in (1, 2, 3), (tile, form)       # a forced tile is the tile that ran
 
 
 @pytest.mark.parametrize("kx,kw", [(-70, 0), (0, -40), (45, 20), (-30, 50)])
@@ -338,9 +341,12 @@ def test_masked_convolution_on_the_general_kernel(F, mask_type, R):
     wd = dev(w)
     wp = F.pack_weight_f16x2_gen(wd, taps=taps)
     assert np.array_equal(host(wd), w * mask)                        # zeroed in place, live taps untouched
-    for tile, mfma in ((64, 32), (128, 32), (64, 16), (128, 16)):
-        with F.tuning(fx3_gen_tile=tile, fx3_gen_mfma=mfma):
+    from spatiotemporalentropymodel_amd import _lib
+    # the four general plans and the image-tile form (fx3_gen_img = 2, no tile forced; 11 x 13 is eligible: 286 >= 256 pixels of its one tile)
+    for tile, mfma, img, form in ((64, 32, 0, 1), (128, 32, 0, 2), (64, 16, 0, 1), (128, 16, 0, 2), (0, 32, 2, 3)):
+        with F.tuning(fx3_gen_tile=tile, fx3_gen_mfma=mfma, fx3_gen_img=img):
             y, _ = F.conv2d_f16x3_gen(F.F16Planes.split(dev(x)), wp, dev(b), K, R, R, 1, R // 2, taps=taps)
+            assert (_lib.hip().stem_tuning_get(b"fx3_ran_form"), _lib.hip().stem_tuning_get(b"fx3_ran_mfma")) == (form, mfma)
         assert_close(host(y), orc.conv2d_fwd(x, w * mask, b, 1, R // 2), what=f"masked {mask_type} {R}x{R} tile {tile} mfma {mfma}", floor=0.1)
 
 
