@@ -47,7 +47,10 @@ enum { STEM_TUNE_FX3_TILE = 0, STEM_TUNE_FX3_SPLIT, STEM_TUNE_WG3_SPLIT, STEM_TU
 // The same for stem_conv2d_f16x3_gen_fwd -- "fx3_ran_form" (1 = conv_f16x3_gen_kernel with 64-pixel tiles, 2 = with 128-pixel
 // tiles, 3 = the image-tile form), "fx3_ran_split" (the split count in the launch arguments: after the cdiv round trip and the
 // "no workspace: unsplit" fallback), "fx3_ran_mfma" (16 | 32 rows of the MFMA shape; the image-tile form has 32 only).
-enum { STEM_RAN_IGEMM_CFG = 0, STEM_RAN_IGEMM_SPLIT, STEM_RAN_WGRAD_CFG, STEM_RAN_FX3_FORM, STEM_RAN_FX3_SPLIT, STEM_RAN_FX3_MFMA, STEM_RAN_COUNT };
+// And for stem_conv2d_wgrad_f16x3 / stem_conv2d_wgrad_f16x3_strided (wgrad_f16x3.hip) -- "wg3_ran_form" (1 = the per-tap kernel,
+// 2 = the filter-row kernel), "wg3_ran_taps" (S of the filter-row kernel's instantiation, 0 for the per-tap kernel),
+// "wg3_ran_split" (the pixel splits in the launch arguments = slabs written).
+enum { STEM_RAN_IGEMM_CFG = 0, STEM_RAN_IGEMM_SPLIT, STEM_RAN_WGRAD_CFG, STEM_RAN_FX3_FORM, STEM_RAN_FX3_SPLIT, STEM_RAN_FX3_MFMA, STEM_RAN_WG3_FORM, STEM_RAN_WG3_TAPS, STEM_RAN_WG3_SPLIT, STEM_RAN_COUNT };
 void stem_ran_note(int id, int value);
 int stem_tuning(int id);
 // image-tile form of the general split-operand convolution (conv_f16x3_img.hip), dispatched from stem_conv2d_f16x3_gen_fwd

@@ -514,6 +514,9 @@ STEM_EXPORT int stem_conv2d_wgrad_f16x3(const void *xp, const float *xq, int xpi
             a.dy[r * S + s] = (signed char)(r - pad);
             a.dx[r * S + s] = (signed char)(s - pad);
         }
+    stem_ran_note(STEM_RAN_WG3_FORM, rows ? 2 : 1);      // test aids: stem_tuning_get("wg3_ran_form" | "wg3_ran_taps" | "wg3_ran_split")
+    stem_ran_note(STEM_RAN_WG3_TAPS, rows ? S : 0);
+    stem_ran_note(STEM_RAN_WG3_SPLIT, a.nsplit);
     if (rows) {
         static bool attr_rows = false;
         if (!attr_rows) {
@@ -538,7 +541,7 @@ STEM_EXPORT int stem_conv2d_wgrad_f16x3(const void *xp, const float *xq, int xpi
         attr_done = true;
     }
     const dim3 grid(cdiv(K, TK) * cdiv(C, TC), R * S, splits);
-        hipLaunchKernelGGL(wgrad_f16x3_kernel, grid, dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(wgrad_f16x3_kernel, grid, dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
     STEM_LAUNCH_CHECK("stem_conv2d_wgrad_f16x3");
     return 0;
 }
@@ -588,6 +591,9 @@ STEM_EXPORT int stem_conv2d_wgrad_f16x3_strided(const void *xp, const float *xq,
             a.dy[r * S + s] = (signed char)(r - pad);
             a.dx[r * S + s] = (signed char)(s - pad);
         }
+    stem_ran_note(STEM_RAN_WG3_FORM, 1);
+    stem_ran_note(STEM_RAN_WG3_TAPS, 0);
+    stem_ran_note(STEM_RAN_WG3_SPLIT, a.nsplit);
     static bool attr_done = false;
     if (!attr_done) {
         (void)hipFuncSetAttribute((const void *)wgrad_f16x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);

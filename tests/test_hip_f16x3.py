@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import wg3_cases as W3
 from conftest import REPO, assert_close, close_ratio
 
 sys.path.insert(0, os.path.join(REPO, "oracle"))
@@ -481,6 +482,12 @@ def test_weight_gradient_vs_oracle(F, case, split):
         _weight_gradient_vs_oracle(F, case, split)
 
 
+def wg3_ran():
+    """the plan of the most recent launch of csrc/wgrad_f16x3.hip: (form 1 = per tap / 2 = filter rows, S of the row kernel or 0, splits)"""
+    from spatiotemporalentropymodel_amd import _lib
+    return tuple(int(_lib.hip().stem_tuning_get(k)) for k in (b"wg3_ran_form", b"wg3_ran_taps", b"wg3_ran_split"))
+
+
 def _weight_gradient_vs_oracle(F, case, split):
     B, C, H, W, K, R = case
     pad = R // 2
@@ -493,6 +500,8 @@ def _weight_gradient_vs_oracle(F, case, split):
     dwp = torch.empty(elems, device="cuda")
     dbf = torch.full((K,), float("nan"), device="cuda")
     F.conv2d_wgrad_f16x3(F.F16Planes.split(xd), F.F16Planes.split(dyd), K, R, R, pad, dwp, splits, db=dbf)
+    rows = W3.row_form(H, W, R, R, pad)                 # the form that ran: filter rows wherever the geometry allows them
+    assert wg3_ran() == (2 if rows else 1, R if rows else 0, splits) and splits == W3.splits_s1(B, C, H, W, K, R, R, pad, 0, split)
     dw = dwp.view(splits, R * R, K, C).sum(0).permute(1, 2, 0).reshape(K, C, R, R)
     assert_close(host(dw), dw_ref, what=f"wgrad {case} split={split}", floor=0.1)
     assert_close(host(dbf), db_ref, what="bias gradient from the weight-gradient pass", floor=0.1)
@@ -519,13 +528,21 @@ def test_weight_gradient_filter_row_form_vs_per_tap_form(F, case):
             splits, elems = F.wgrad_f16x3_plan((B, C, H, W), K, R, R, pad)
             dwp, db = torch.empty(elems, device="cuda"), torch.zeros(K, device="cuda")
             F.conv2d_wgrad_f16x3(xp, dyp, K, R, R, pad, dwp, splits, db=db)
+            assert wg3_ran() == ((1, 0, splits) if form else (2, R, splits)), (form, wg3_ran())
+            assert splits == W3.splits_s1(B, C, H, W, K, R, R, pad, form), (form, splits)
             out[form] = (host(dwp.view(splits, R * R, K, C).sum(0)), host(db))
     assert_close(out[0][0], out[1][0], what=f"filter-row form against per-tap form {case}", floor=0.1)
     assert_close(out[0][1], out[1][1], what="bias gradient of the two forms", floor=0.1)
     with F.tuning(wg3_row=1):
         per_tap_splits = F.wgrad_f16x3_plan((B, C, H, W), K, R, R, pad)[0]
-    with F.tuning(wg3_row=0, wg3_split=2):      # a forced split is honoured by the row form's planner too
-        assert F.wgrad_f16x3_plan((B, C, H, W), K, R, R, pad)[0] <= 2 and per_tap_splits >= 1
+    assert per_tap_splits == W3.splits_s1(B, C, H, W, K, R, R, pad, 1) >= 1
+    with F.tuning(wg3_row=0, wg3_split=2):      # a forced split is honoured by the row form's planner too: unclamped but for the chunk count
+        splits, elems = F.wgrad_f16x3_plan((B, C, H, W), K, R, R, pad)
+        assert splits == W3.splits_s1(B, C, H, W, K, R, R, pad, 0, 2) == 2
+        dwp = torch.empty(elems, device="cuda")
+        F.conv2d_wgrad_f16x3(xp, dyp, K, R, R, pad, dwp, splits)
+        assert wg3_ran() == (2, R, 2)
+        assert_close(host(dwp.view(splits, R * R, K, C).sum(0)), out[1][0], what=f"filter-row form at a forced split 2 against per-tap form {case}", floor=0.1)
 
 
 def test_weight_gradient_from_channel_views(F):
@@ -676,6 +693,7 @@ def test_strided_weight_gradient_vs_oracle(F, case):
     dwp = torch.empty(elems, device="cuda")
     bpart = torch.empty(splits * K, device="cuda")
     F.conv2d_wgrad_f16x3_strided(xp, dyp, K, R, R, 2, pad, dwp, splits, bias_part=bpart)
+    assert wg3_ran() == (1, 0, splits) and splits == W3.splits_strided(B, C, H, W, K, R, R, 2, pad)      # the strided entry has the per-tap kernel only
     dw = dwp.view(splits, R * R, K, C).sum(0).permute(1, 2, 0).reshape(K, C, R, R)
     assert_close(host(dw), dw_ref, what=f"strided wgrad {case}", floor=0.1)
     assert_close(host(bpart.view(splits, K).sum(0)), db_ref, what="bias column sums", floor=0.1)
