@@ -1,5 +1,5 @@
 """ctypes loader for the three C-ABI libraries (include/stem_hip.h + include/stem_ar_batch.h + include/stem_blocks.h +
-include/stem_hyperprior.h, include/stem_rans.h, include/stem_dp.h).
+include/stem_hyperprior.h + include/stem_eb_filters.h, include/stem_rans.h, include/stem_dp.h).
 
 The headers are the single statement of the ABI: every prototype and descriptor structure below is read from them (_abi.py).
 
@@ -50,6 +50,8 @@ _HIP_BATCH_PROTO, _HIP_BATCH_SIG, _ = _tables("stem_ar_batch.h")
 _HIP_BLOCKS_PROTO, _HIP_BLOCKS_SIG, _ = _tables("stem_blocks.h")
 # libstem_hip.so's zero-mean likelihood kernels of the bmshj2018 models (csrc/hyperprior.hip; not launch-tape entries either)
 _HIP_HYPERPRIOR_PROTO, _HIP_HYPERPRIOR_SIG, _ = _tables("stem_hyperprior.h")
+# libstem_hip.so's EntropyBottleneck kernels for any `filters` tuple (csrc/eb_filters.hip; not launch-tape entries either)
+_HIP_EBF_PROTO, _HIP_EBF_SIG, _ = _tables("stem_eb_filters.h")
 _RANS_PROTO, _RANS_SIG, _RANS_RESTYPE = _tables("stem_rans.h")
 _DP_PROTO, _DP_SIG, _ = _tables("stem_dp.h")
 _STRUCTS = _abi.structs(_header("stem_hip.h"))
@@ -96,7 +98,7 @@ def hip():
                 f"{HIP_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the STEM kernels.")
         lib = C.CDLL(HIP_SO)
-        for protos in (_HIP_PROTO, _HIP_BATCH_PROTO, _HIP_BLOCKS_PROTO, _HIP_HYPERPRIOR_PROTO):
+        for protos in (_HIP_PROTO, _HIP_BATCH_PROTO, _HIP_BLOCKS_PROTO, _HIP_HYPERPRIOR_PROTO, _HIP_EBF_PROTO):
             _bind(lib, protos)
         _hip = lib
     return _hip
@@ -130,6 +132,10 @@ def declared_hip_block_symbols():
 
 def declared_hip_hyperprior_symbols():
     return sorted(_HIP_HYPERPRIOR_SIG)
+
+
+def declared_hip_eb_filters_symbols():
+    return sorted(_HIP_EBF_SIG)
 
 
 def dp():

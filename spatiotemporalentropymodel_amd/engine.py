@@ -333,6 +333,11 @@ class StemEngine:
     def __init__(self, model, has_tpm: bool, has_spm: bool, residual: bool):
         _config.runtime()                   # parse the environment now if a STEM_* variable changed (the switches read the parsed object)
         self.m = model
+        eb_filters = tuple(model.entropy_bottleneck.filters)
+        if eb_filters != (3, 3, 3, 3):
+            # the schedule, the fused trainer and the launch tape call the specialised stem_eb_*_train* kernels on the [C][58] pack
+            raise ValueError(f"StemEngine: the fused schedule is built for an EntropyBottleneck with filters=(3, 3, 3, 3), this model's "
+                             f"has filters={eb_filters}; its module-by-module forward (model(y_cur, y_conditioned)) and autograd work")
         self.has_tpm, self.has_spm, self.residual = has_tpm, has_spm, residual
         L = lambda mod: _Layer(mod, "conv", self)
         D = lambda mod: _Layer(mod, "deconv", self)

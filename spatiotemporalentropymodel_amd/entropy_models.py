@@ -201,6 +201,31 @@ class _EBFunction(torch.autograd.Function):
 _EB_SHAPES = [(3, 1), (3, 1), (3, 1), (3, 3), (3, 1), (3, 1), (3, 3), (3, 1), (3, 1), (3, 3), (3, 1), (3, 1), (1, 3), (1, 1)]
 
 
+class _EBFFunction(torch.autograd.Function):
+    """_EBFunction for any `filters`: the general kernels (include/stem_eb_filters.h), one each way"""
+
+    @staticmethod
+    def forward(ctx, filters, x, noise, medians, *tensors):
+        pack = F.ebf_pack(list(tensors), filters)
+        z_hat, lik = F.ebf_forward(F.to_nhwc(x), pack, filters, medians=medians, noise=noise)
+        ctx.filters, ctx.shapes = filters, [tuple(t.shape) for t in tensors]
+        ctx.save_for_backward(z_hat, pack)
+        return z_hat, lik
+
+    @staticmethod
+    def backward(ctx, dzhat, dlik):
+        z_hat, pack = ctx.saved_tensors
+        dlik = torch.zeros_like(z_hat) if dlik is None else _dense(dlik)
+        dzin = None if dzhat is None else _dense(dzhat)
+        dz, dpack = F.ebf_backward(z_hat, pack, dlik, ctx.filters, dzhat_in=dzin, want_dz=ctx.needs_input_grad[1],
+                                   want_dpack=any(ctx.needs_input_grad[4:]))
+        grads = [None] * len(ctx.shapes)
+        if dpack is not None:
+            grads = [torch.empty(s, device=pack.device) for s in ctx.shapes]
+            F.ebf_unpack_grads(dpack, grads, ctx.filters)
+        return (None, dz, None, None, *grads)
+
+
 def _dense(t):
     t = F.to_nhwc(t)
     if F.nhwc_ld(t) != t.shape[1]:
@@ -466,16 +491,23 @@ class EntropyModel(nn.Module):
 
 class EntropyBottleneck(EntropyModel):
     def __init__(self, channels, *args, tail_mass=1e-9, init_scale=10, filters=(3, 3, 3, 3), **kwargs):
+        # (3, 3, 3, 3) runs on the specialised kernels (stem_eb_*), any other tuple inside the caps on the general family
+        # (stem_ebf_*, include/stem_eb_filters.h); refused before anything is allocated
+        filters = tuple(int(f) for f in filters)
+        if any(f < 1 for f in filters):
+            raise ValueError(f"filters={filters}: every width must be at least 1")
+        if not F.ebf_in_caps(filters):
+            raise NotImplementedError(f"filters={filters}: the HIP bottleneck kernels take at most {F.EBF_MAX_FILTERS} filters "
+                                      f"of width at most {F.EBF_MAX_WIDTH}")
         super().__init__(*args, **kwargs)
         self.channels = int(channels)
-        self.filters = tuple(int(f) for f in filters)
-        if self.filters != (3, 3, 3, 3):
-            raise NotImplementedError("the HIP bottleneck kernel is specialised for filters=(3,3,3,3) (the only STEM use)")
+        self.filters = filters
         self.init_scale = float(init_scale)
         self.tail_mass = float(tail_mass)
-        # Per-channel MLP 1 -> 3 -> 3 -> 3 -> 3 -> 1 of the cumulative (entropy_models.py:303-340 upstream).  Layer i maps
-        # widths[i] -> widths[i+1]; the initial values make softplus(matrix) a constant 1 / (s * fan_out) with
-        # s = init_scale^(1/5), biases are U(-1/2, 1/2) (drawn layer by layer: the only RNG use), gate factors 0.
+        # Per-channel MLP 1 -> filters[0] -> ... -> filters[-1] -> 1 of the cumulative (entropy_models.py:303-340 upstream; 1 -> 3 -> 3
+        # -> 3 -> 3 -> 1 by default).  Layer i maps widths[i] -> widths[i+1]; the initial values make softplus(matrix) a constant
+        # 1 / (s * fan_out) with s = init_scale^(1 / layers), biases are U(-1/2, 1/2) (drawn layer by layer: the only RNG use), gate
+        # factors 0.
         widths = (1, *self.filters, 1)
         n_layers = len(widths) - 1
         per_layer_scale = self.init_scale ** (1.0 / n_layers)
@@ -493,8 +525,22 @@ class EntropyBottleneck(EntropyModel):
         tail_logit = float(np.log(2.0 / self.tail_mass - 1.0))
         self.register_buffer("target", torch.tensor([-tail_logit, 0.0, tail_logit]))
 
+    @property
+    def _specialised(self):
+        """the default tuple: the specialised kernels (stem_eb_*) and the fused schedules; nothing is stored, so a module pickled
+        before the general kernels existed behaves as it did"""
+        return tuple(self.filters) == (3, 3, 3, 3)
+
     def _tensors14(self):
+        """the 14 tensors of the specialised kernels' [C][58] pack; the fused schedules (engine, trainer, launch tape) know no other"""
+        if not self._specialised:
+            raise ValueError(f"EntropyBottleneck(filters={self.filters}): the fused schedule and its [C][58] pack exist for "
+                             "filters=(3, 3, 3, 3) only; other filters run through the module's own forward / autograd")
         return [getattr(self, n) for n in F.EB_TENSORS]
+
+    def _tensors(self):
+        """the 3 L + 2 tensors in pack order (F.ebf_layout)"""
+        return [getattr(self, n) for n in F.ebf_tensor_names(self.filters)]
 
     def _get_medians(self):
         return self.quantiles[:, :, 1:2]
@@ -550,6 +596,8 @@ class EntropyBottleneck(EntropyModel):
 
     def loss(self):
         """Auxiliary loss (entropy_models.py:383-386); gradient flows to `quantiles` only."""
+        if not self._specialised:
+            return _EBFAuxFunction.apply(self.filters, self.quantiles, self.target, *self._tensors())
         return _EBAuxFunction.apply(self.quantiles, self.target, *self._tensors14())
 
     def forward(self, x):
@@ -558,6 +606,8 @@ class EntropyBottleneck(EntropyModel):
             noise, med = self._noise_like(xin), None
         else:
             noise, med = None, self._medians_vec()
+        if not self._specialised:
+            return _EBFFunction.apply(self.filters, x, noise, med, *self._tensors())
         return _EBFunction.apply(x, noise, med, *self._tensors14())
 
     @staticmethod
@@ -591,6 +641,24 @@ class _EBAuxFunction(torch.autograd.Function):
     def backward(ctx, g):
         (dq,) = ctx.saved_tensors
         return (dq * g, None) + (None,) * 14
+
+
+class _EBFAuxFunction(torch.autograd.Function):
+    """_EBAuxFunction for any `filters`: the general kernel (stem_ebf_aux_loss_grad)"""
+
+    @staticmethod
+    def forward(ctx, filters, quantiles, target, *tensors):
+        pack = F.ebf_pack(list(tensors), filters)
+        q = quantiles.detach().contiguous()
+        dq = torch.empty_like(q)
+        loss = F.ebf_aux_loss_grad(q, pack, target, filters, dq)
+        ctx.save_for_backward(dq)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dq,) = ctx.saved_tensors
+        return (None, dq * g, None) + (None,) * (len(ctx.needs_input_grad) - 3)
 
 
 class GaussianConditional(EntropyModel):

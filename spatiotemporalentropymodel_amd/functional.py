@@ -8,6 +8,7 @@ computes with torch ops.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 
 import torch
@@ -1799,4 +1800,135 @@ def eb_aux_loss_grad(quantiles, pack, target, dq_out, loss_out=None, accumulate=
         loss_out = torch.empty(1, dtype=torch.float32, device=quantiles.device)
     _chk(_lib.hip().stem_eb_aux_loss_grad(quantiles.data_ptr(), pack.data_ptr(), target.data_ptr(), loss_out.data_ptr(),
                                           _ptr(dq_out), quantiles.shape[0], int(bool(accumulate)), _stream()))
+    return loss_out
+
+
+# ----------------------------------------------------------------------------- EntropyBottleneck, any `filters` (include/stem_eb_filters.h)
+EBF_MAX_FILTERS, EBF_MAX_WIDTH, EBF_MAX_NPARAM = 6, 8, 433
+
+
+def _ebf_filters(filters):
+    """filters as the C ABI takes them: (host int array or None, count)"""
+    f = tuple(int(v) for v in filters)
+    return ((C.c_int * len(f))(*f) if f else None), len(f)
+
+
+def ebf_in_caps(filters):
+    f = tuple(int(v) for v in filters)
+    return len(f) <= EBF_MAX_FILTERS and all(1 <= v <= EBF_MAX_WIDTH for v in f)
+
+
+@functools.lru_cache(maxsize=None)
+def _ebf_layout(f):
+    if not ebf_in_caps(f):
+        raise ValueError(f"filters={f} is outside the caps of the general bottleneck kernels: at most {EBF_MAX_FILTERS} filters, "
+                         f"widths 1 .. {EBF_MAX_WIDTH}")
+    widths = (1, *f, 1)
+    out, off = [], 0
+    for i in range(len(f) + 1):
+        groups = [("_matrix", widths[i + 1] * widths[i]), ("_bias", widths[i + 1])] + ([("_factor", widths[i + 1])] if i < len(f) else [])
+        for name, n in groups:
+            out.append((f"{name}{i:d}", off, n))
+            off += n
+    return tuple(out), off
+
+
+def ebf_layout(filters):
+    """[(name, offset, length)] of the 3 L + 2 column groups of a channel's pack, in pack (= tensor) order: per layer i
+    `_matrix{i}` (widths[i+1] x widths[i], row major), `_bias{i}`, and `_factor{i}` for every layer but the last.  Host arithmetic
+    (done once per tuple)."""
+    return list(_ebf_layout(tuple(int(v) for v in filters))[0])
+
+
+def ebf_nparam(filters):
+    """floats per channel of the pack (58 for (3, 3, 3, 3))"""
+    return _ebf_layout(tuple(int(v) for v in filters))[1]
+
+
+def ebf_tensor_names(filters):
+    return [name for name, _, _ in ebf_layout(filters)]
+
+
+def ebf_pack(tensors, filters):
+    """the 3 L + 2 EntropyBottleneck tensors in ebf_layout order -> [C, nparam] pack"""
+    ts = [t.detach().contiguous() for t in tensors]
+    _require_cuda(*ts)
+    layout = ebf_layout(filters)
+    if len(ts) != len(layout) or any(t.numel() != ts[0].shape[0] * n for t, (_, _, n) in zip(ts, layout)):
+        raise ValueError(f"ebf_pack: filters={tuple(filters)} takes {len(layout)} tensors of {[n for _, _, n in layout]} floats per channel")
+    Cc = ts[0].shape[0]
+    pack = torch.empty((Cc, ebf_nparam(filters)), device=ts[0].device, dtype=torch.float32)
+    fa, nf = _ebf_filters(filters)
+    _chk(_lib.hip().stem_ebf_pack(_ptr_array(ts), fa, nf, pack.data_ptr(), Cc, _stream()))
+    return pack
+
+
+def ebf_unpack_grads(dpack, grads, filters, accumulate=False):
+    """dpack [C, nparam] -> the 3 L + 2 gradient tensors (contiguous, written or added to)"""
+    _require_cuda(dpack, *grads)
+    layout = ebf_layout(filters)
+    Cc = dpack.shape[0]
+    if len(grads) != len(layout) or any(not g.is_contiguous() or g.numel() != Cc * n for g, (_, _, n) in zip(grads, layout)):
+        raise ValueError(f"ebf_unpack_grads: filters={tuple(filters)} takes {len(layout)} contiguous tensors")
+    if tuple(dpack.shape) != (Cc, ebf_nparam(filters)) or not dpack.is_contiguous():
+        raise ValueError(f"ebf_unpack_grads: dpack must be a dense [C, {ebf_nparam(filters)}] tensor")
+    fa, nf = _ebf_filters(filters)
+    _chk(_lib.hip().stem_ebf_unpack_grads(dpack.data_ptr(), _ptr_array(grads), fa, nf, Cc, 1 if accumulate else 0, _stream()))
+
+
+def _ebf_check_pack(pack, filters, Cc):
+    if tuple(pack.shape) != (Cc, ebf_nparam(filters)) or not pack.is_contiguous():
+        raise ValueError(f"pack must be a dense [{Cc}, {ebf_nparam(filters)}] tensor for filters={tuple(filters)}, got {tuple(pack.shape)}")
+
+
+def ebf_forward(z, pack, filters, medians=None, noise=None, bound=1e-9):
+    """-> (z_hat, lik) dense NHWC tensors.  noise given -> training mode, else round around medians."""
+    _require_cuda(z, pack, medians, noise)
+    B, Cc, H, W = z.shape
+    _ebf_check_pack(pack, filters, Cc)
+    ldz = nhwc_ld(z)
+    if ldz is None:
+        raise ValueError("ebf_forward: z must have NHWC memory")
+    z_hat, lik = empty_nhwc(B, Cc, H, W, z.device), empty_nhwc(B, Cc, H, W, z.device)
+    mode = 0 if noise is not None else 1
+    if noise is not None and (tuple(noise.shape) != tuple(z.shape) or nhwc_ld(noise) != Cc):
+        raise ValueError("ebf_forward: noise must be a dense NHWC tensor of z's shape")
+    if medians is not None and (medians.numel() != Cc or not medians.is_contiguous()):
+        raise ValueError("ebf_forward: medians must be a contiguous [C] tensor")
+    fa, nf = _ebf_filters(filters)
+    _chk(_lib.hip().stem_ebf_forward(z.data_ptr(), ldz, _ptr(noise), pack.data_ptr(), _ptr(medians), fa, nf, z_hat.data_ptr(),
+                                     lik.data_ptr(), B, H, W, Cc, mode, bound, _stream()))
+    return z_hat, lik
+
+
+def ebf_backward(z_hat, pack, dlik, filters, dzhat_in=None, bound=1e-9, want_dz=True, want_dpack=True, dz_out=None, dpack_out=None):
+    """-> (dz, dpack); an output that is not wanted is None.  dz_out / dpack_out: write into these dense tensors"""
+    _require_cuda(z_hat, pack, dlik, dzhat_in, dz_out, dpack_out)
+    B, Cc, H, W = z_hat.shape
+    _ebf_check_pack(pack, filters, Cc)
+    for t in (z_hat, dlik, dzhat_in, dz_out):
+        if t is not None and (tuple(t.shape) != (B, Cc, H, W) or nhwc_ld(t) != Cc):
+            raise ValueError("ebf_backward: z_hat, dlik, dzhat_in and dz must be dense NHWC tensors of one shape")
+    dz = (dz_out if dz_out is not None else empty_nhwc(B, Cc, H, W, z_hat.device)) if want_dz else None
+    dpack = (dpack_out if dpack_out is not None else torch.empty_like(pack)) if want_dpack else None
+    if dpack is not None:
+        _ebf_check_pack(dpack, filters, Cc)
+    fa, nf = _ebf_filters(filters)
+    _chk(_lib.hip().stem_ebf_backward(z_hat.data_ptr(), pack.data_ptr(), dlik.data_ptr(), _ptr(dzhat_in), fa, nf, _ptr(dz), _ptr(dpack),
+                                      B, H, W, Cc, bound, _stream()))
+    return dz, dpack
+
+
+def ebf_aux_loss_grad(quantiles, pack, target, filters, dq_out, loss_out=None, accumulate=False):
+    """EntropyBottleneck.loss and d loss / d quantiles in one single-workgroup kernel; dq_out (or None) is written (or added to)"""
+    _require_cuda(quantiles, pack, target, dq_out, loss_out)
+    Cc = quantiles.shape[0]
+    _ebf_check_pack(pack, filters, Cc)
+    if quantiles.numel() != 3 * Cc or not quantiles.is_contiguous() or (dq_out is not None and (dq_out.numel() != 3 * Cc or not dq_out.is_contiguous())):
+        raise ValueError("ebf_aux_loss_grad: quantiles and dq_out must be contiguous [C, 1, 3] tensors")
+    if loss_out is None:
+        loss_out = torch.empty(1, dtype=torch.float32, device=quantiles.device)
+    fa, nf = _ebf_filters(filters)
+    _chk(_lib.hip().stem_ebf_aux_loss_grad(quantiles.data_ptr(), pack.data_ptr(), target.data_ptr(), fa, nf, loss_out.data_ptr(),
+                                           _ptr(dq_out), Cc, int(bool(accumulate)), _stream()))
     return loss_out

@@ -15,7 +15,7 @@ import torch.nn as nn
 from .. import functional as F
 from ..engine import StemEngine, StemFunction
 from ..entropy_models import GaussianConditional
-from ..layers import Conv2d, ConvTranspose2d, FusedSequential, LeakyReLU, MaskedConv2d
+from ..layers import CatFunction, Conv2d, ConvTranspose2d, FusedSequential, LeakyReLU, MaskedConv2d
 from .priors import CompressionModel, get_scale_table      # get_scale_table: re-exported, it lives next to ScaleHyperprior
 
 __all__ = ["get_scale_table", "SpatioTemporalPriorModelWithoutSPMTPM", "SpatioTemporalPriorModelWithoutSPM",
@@ -73,7 +73,29 @@ class _StemBase(CompressionModel):
             object.__setattr__(self, "_engine_params", [p for n, p in self.named_parameters() if not n.endswith(".quantiles")])
         return self._engine
 
+    def _forward_modules(self, y_cur, y_conditioned):
+        """The reference's forward module by module (spatiotemporalpriors.py:70-83, 176-194, 291-309, 561-585, 845-868), every module
+        on its own kernels and autograd node: the route of a model whose bottleneck the fused schedule does not know."""
+        gc = self.gaussian_conditional
+        z = self.HE(CatFunction.apply(y_cur, y_conditioned))
+        z_hat, lik_z = self.entropy_bottleneck(z)
+        priors = ([self.TPM(y_conditioned)] if self.HAS_TPM else []) + [self.HD(z_hat)]
+        target = F.sub(F.dense_nhwc(y_cur.detach()), F.dense_nhwc(y_conditioned.detach())) if self.RESIDUAL else y_cur
+        if self.HAS_SPM:
+            t_hat = gc.quantize(target.detach(), "noise" if self.training else "dequantize")
+            priors.append(self.context_prediction(t_hat))
+        gp = self.EPM(CatFunction.apply(*priors) if len(priors) > 1 else priors[0])
+        scales_hat, means_hat = gp.chunk(2, 1)
+        out, lik_y = gc(target, scales_hat, means=means_hat)
+        if self.HAS_SPM:
+            y_hat = F.add(t_hat, F.dense_nhwc(y_conditioned.detach())) if self.RESIDUAL else t_hat
+        else:
+            y_hat = out
+        return {"y_hat": y_hat, "likelihoods": {"y": lik_y, "z": lik_z}}
+
     def forward(self, y_cur, y_conditioned):
+        if tuple(self.entropy_bottleneck.filters) != (3, 3, 3, 3):
+            return self._forward_modules(y_cur, y_conditioned)
         eng = self.engine()
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._engine_params):
             y_hat, lik_y, lik_z = StemFunction.apply(eng, self.training, y_cur, y_conditioned, *self._engine_params)
