@@ -37,7 +37,13 @@ int stem_abi_version(void);
  * of stem_conv2d_f16x3_gen_fwd / stem_conv2d_wgrad_f16x3, 0 = the planner's; "fx3_depth": 0 automatic | 2 | 4 chunks in
  * flight in stem_conv2d_f16x3_fwd; "fx3_gen_tile": 0 automatic | 64 | 128 pixel workgroups of stem_conv2d_f16x3_gen_fwd; "arp_workers": workgroups of the persistent decoder).  Every setting computes the same
  * contraction (summation order aside); process-wide; not for concurrent use with launches.  There is no reference
- * counterpart (torch picks its kernels internally).  Nothing in the library reads the environment to change results. */
+ * counterpart (torch picks its kernels internally).  Nothing in the library reads the environment to change results.
+ * Test aids, get-only (stem_tuning_set refuses them): the plan of this process's most recent launch of a family --
+ * "igemm_ran_cfg", "igemm_ran_split", "wgrad_ran_cfg"; "fx3_ran_form", "fx3_ran_split", "fx3_ran_mfma" (stem_conv2d_f16x3_gen_fwd);
+ * "wg3_ran_form", "wg3_ran_taps", "wg3_ran_split" (stem_conv2d_wgrad_f16x3*); "fx3_col_ran_tile" (64 | 128), "fx3_col_ran_depth"
+ * (2 | 3), "fx3_col_ran_mfma" (16 | 32) of stem_conv2d_f16x3_fwd / _fwd_act; "tconv_ran_tile" (64 | 128), "tconv_ran_cps" (chunks
+ * per workgroup, 2^30 after the unsplit fallback), "tconv_ran_split0" .. "tconv_ran_split3" (split count per phase) of
+ * stem_tconv2d_f16x3_fwd.  Their meaning: csrc/stem_common.h. */
 /* ---- launch tape: the native executor of a static launch schedule (csrc/tape.hip; reference loop body stem/trainSTEM.py:194-218,
  * which the reference walks through the Python interpreter and autograd every step).  A tape holds calls of THIS library's
  * int-returning entry points (function address + integer-class / float arguments; integer arguments may advance by a fixed

@@ -1138,6 +1138,9 @@ static int conv2d_f16x3_launch(const void *xp, const float *xq, const void *wp, 
     // 32x32x16 otherwise; stem_tuning_set("fx3_mfma", 16 | 32) forces it where the loop form allows
     const int msel = stem_tuning(STEM_TUNE_FX3_MFMA);
     const bool m16 = depth == 3 && (msel ? msel == 16 : !small);
+    stem_ran_note(STEM_RAN_FX3_COL_TILE, small ? 64 : 128);      // test aids: stem_tuning_get("fx3_col_ran_tile" | "fx3_col_ran_depth" | "fx3_col_ran_mfma")
+    stem_ran_note(STEM_RAN_FX3_COL_DEPTH, depth == 3 ? 3 : 2);
+    stem_ran_note(STEM_RAN_FX3_COL_MFMA, m16 ? 16 : 32);
     if (small && m16)
         hipLaunchKernelGGL((conv_f16x3_kernel<64, 3, 16>), dim3(cdiv(M, 64)), dim3(256), lds_total(64, 3), st, a);
     else if (small && depth == 3)
@@ -1408,6 +1411,9 @@ STEM_EXPORT int stem_tconv2d_f16x3_fwd(const void *xp, const float *xq, int xpix
         (void)hipFuncSetAttribute((const void *)conv_f16x3_gen_kernel<128, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, glds(128));
         attr_done = true;
     }
+    stem_ran_note(STEM_RAN_TCONV_TILE, bm == 128 ? 128 : 64);      // test aids: stem_tuning_get("tconv_ran_tile" | "tconv_ran_cps" | "tconv_ran_split0" .. "3")
+    stem_ran_note(STEM_RAN_TCONV_CPS, cps);
+    for (int p = 0; p < 4; ++p) stem_ran_note(STEM_RAN_TCONV_SPLIT0 + p, a.ph[p].nsplit);
     const dim3 grid(4 * ptiles, ntn, maxns);
     if (bm == 128)
         hipLaunchKernelGGL((conv_f16x3_gen_kernel<128, 16, true>), grid, dim3(512), glds(128), (hipStream_t)stream, a);

@@ -19,9 +19,10 @@ STEM_EXPORT int stem_abi_version(void) { return 5; }      // 5 (round 5): + stem
 static int g_tuning[STEM_TUNE_COUNT] = {0};
 static const char *const kTuningNames[STEM_TUNE_COUNT] = {"fx3_tile", "fx3_split", "wg3_split", "arp_workers", "fx3_depth", "fx3_gen_tile", "fx3_mfma", "fx3_gen_mfma", "fx3_gen_img", "fx3_img_w", "wg3_row", "wg3_minch", "tconv_cps", "arp_giveup_at", "unpack_mb", "igemm_cfg", "igemm_fuse_cfg", "igemm_split", "wgrad_cfg"};
 // test aids (get-only): the plan of the most recent launch of the fp32-MFMA convolution / weight-gradient family and of the
-// general fp16 forward family (stem_conv2d_f16x3_gen_fwd), and of the fp16 weight-gradient entries (wgrad_f16x3.hip)
+// general fp16 forward family (stem_conv2d_f16x3_gen_fwd), of the fp16 weight-gradient entries (wgrad_f16x3.hip), of the
+// 192-column kernel (stem_conv2d_f16x3_fwd / _fwd_act) and of the four-phase transposed form (stem_tconv2d_f16x3_fwd)
 static int g_ran[STEM_RAN_COUNT] = {0};
-static const char *const kRanNames[STEM_RAN_COUNT] = {"igemm_ran_cfg", "igemm_ran_split", "wgrad_ran_cfg", "fx3_ran_form", "fx3_ran_split", "fx3_ran_mfma", "wg3_ran_form", "wg3_ran_taps", "wg3_ran_split"};
+static const char *const kRanNames[STEM_RAN_COUNT] = {"igemm_ran_cfg", "igemm_ran_split", "wgrad_ran_cfg", "fx3_ran_form", "fx3_ran_split", "fx3_ran_mfma", "wg3_ran_form", "wg3_ran_taps", "wg3_ran_split", "fx3_col_ran_tile", "fx3_col_ran_depth", "fx3_col_ran_mfma", "tconv_ran_tile", "tconv_ran_cps", "tconv_ran_split0", "tconv_ran_split1", "tconv_ran_split2", "tconv_ran_split3"};
 void stem_ran_note(int id, int value) { g_ran[id] = value; }
 int stem_tuning(int id) { return g_tuning[id]; }
 STEM_EXPORT int stem_tuning_set(const char *name, int value)

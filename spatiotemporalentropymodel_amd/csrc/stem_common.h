@@ -50,7 +50,12 @@ enum { STEM_TUNE_FX3_TILE = 0, STEM_TUNE_FX3_SPLIT, STEM_TUNE_WG3_SPLIT, STEM_TU
 // And for stem_conv2d_wgrad_f16x3 / stem_conv2d_wgrad_f16x3_strided (wgrad_f16x3.hip) -- "wg3_ran_form" (1 = the per-tap kernel,
 // 2 = the filter-row kernel), "wg3_ran_taps" (S of the filter-row kernel's instantiation, 0 for the per-tap kernel),
 // "wg3_ran_split" (the pixel splits in the launch arguments = slabs written).
-enum { STEM_RAN_IGEMM_CFG = 0, STEM_RAN_IGEMM_SPLIT, STEM_RAN_WGRAD_CFG, STEM_RAN_FX3_FORM, STEM_RAN_FX3_SPLIT, STEM_RAN_FX3_MFMA, STEM_RAN_WG3_FORM, STEM_RAN_WG3_TAPS, STEM_RAN_WG3_SPLIT, STEM_RAN_COUNT };
+// For stem_conv2d_f16x3_fwd / stem_conv2d_f16x3_fwd_act (conv_f16x3_kernel<BM, DEPTH, MS>) -- "fx3_col_ran_tile" (BM: 64 | 128),
+// "fx3_col_ran_depth" (DEPTH: 2 | 3), "fx3_col_ran_mfma" (MS: 16 | 32; fx3_mfma = 16 with the two-stage loop runs 32: that
+// instantiation does not exist).  For stem_tconv2d_f16x3_fwd (conv_f16x3_gen_kernel<GBM, 16, true>) -- "tconv_ran_tile" (GBM),
+// "tconv_ran_cps" (chunks per workgroup after the "no room for the plan: unsplit" pass, where it is 2^30),
+// "tconv_ran_split0" .. "tconv_ran_split3" (the split count of phase (py, px) = (p >> 1, p & 1) in the launch arguments).
+enum { STEM_RAN_IGEMM_CFG = 0, STEM_RAN_IGEMM_SPLIT, STEM_RAN_WGRAD_CFG, STEM_RAN_FX3_FORM, STEM_RAN_FX3_SPLIT, STEM_RAN_FX3_MFMA, STEM_RAN_WG3_FORM, STEM_RAN_WG3_TAPS, STEM_RAN_WG3_SPLIT, STEM_RAN_FX3_COL_TILE, STEM_RAN_FX3_COL_DEPTH, STEM_RAN_FX3_COL_MFMA, STEM_RAN_TCONV_TILE, STEM_RAN_TCONV_CPS, STEM_RAN_TCONV_SPLIT0, STEM_RAN_TCONV_SPLIT1, STEM_RAN_TCONV_SPLIT2, STEM_RAN_TCONV_SPLIT3, STEM_RAN_COUNT };
 void stem_ran_note(int id, int value);
 int stem_tuning(int id);
 // image-tile form of the general split-operand convolution (conv_f16x3_img.hip), dispatched from stem_conv2d_f16x3_gen_fwd

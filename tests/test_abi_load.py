@@ -97,7 +97,8 @@ def test_shipped_library_has_no_result_changing_switches():
         assert lib.stem_tuning_set(name, 0) == 0 and lib.stem_tuning_get(name) == 0
     # the plan that ran (test aids): readable (0 until the family's first launch in this process), never settable
     for name in (b"igemm_ran_cfg", b"igemm_ran_split", b"wgrad_ran_cfg", b"fx3_ran_form", b"fx3_ran_split", b"fx3_ran_mfma",
-                 b"wg3_ran_form", b"wg3_ran_taps", b"wg3_ran_split"):
+                 b"wg3_ran_form", b"wg3_ran_taps", b"wg3_ran_split", b"fx3_col_ran_tile", b"fx3_col_ran_depth", b"fx3_col_ran_mfma",
+                 b"tconv_ran_tile", b"tconv_ran_cps", b"tconv_ran_split0", b"tconv_ran_split1", b"tconv_ran_split2", b"tconv_ran_split3"):
         before = lib.stem_tuning_get(name)
         assert before >= 0, name
         assert lib.stem_tuning_set(name, before + 1) != 0 and name in lib.stem_last_error() and b"get-only" in lib.stem_last_error()
