@@ -28,7 +28,7 @@
 
 #include <type_traits>
 
-#include "f16x3_layout.h"
+#include "f16x3_tail.h"
 
 namespace {
 
@@ -387,8 +387,8 @@ __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
     const float fac = q_inv(a.xq) * q_inv(a.wq);                   // the operands were stored times 2^ex, 2^ew
     float oscale = 1.f;                                            // 2^e of the planes output
     if (a.yp) {
-        // upper bound of |output| from the operands' maxima: K terms of at most xmax * wmax each, plus the bias; GDN divides by
-        // at least sqrt(min beta').  One layer's worth of over-estimation (the inputs' maxima are measured, not bounded).
+        // tail_oscale's bound (f16x3_tail.h) times the fused GDN's factor (GDN divides by at least sqrt(min beta')), written out
+        // here: every factoring of it that was tried cost one of the six instantiations 1 to 4 vector registers.
         const float xmax = q_amax(a.xq, qred), wmax = q_amax(a.wq, qred);
         float bm = 0.f, btm = 3.0e38f;
         for (int n = tid; n < a.N; n += NT) {
@@ -594,8 +594,8 @@ __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 if (COLL(j, r) < a.N && bm0 + ROWL(r) < Mtot) omax = fmaxf(omax, fabsf(acc[j][r]));
-        omax = block_max(omax, qred);
-        if (tid == 0) {
+        omax = block_max(omax, qred);                      // tail_record (f16x3_tail.h) in place: through the helper the compiler
+        if (tid == 0) {                                    // re-orders scalar code inside the fused-GDN section above
             a.yq[QREC_HDR + blockIdx.x] = omax;
             if (blockIdx.x == 0) {
                 q_header(a.yq, gridDim.x);
@@ -626,20 +626,7 @@ __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
             const int row = e / (oslab * 4), rem = e - row * (oslab * 4), sl = rem >> 2, p = rem & 3;
             const int m = bm0 + row;
             if (m >= Mtot) continue;
-            const f32x4 v0 = *reinterpret_cast<const f32x4 *>(&X2[row * XP + sl * 32 + p * 8]);
-            const f32x4 v1 = *reinterpret_cast<const f32x4 *>(&X2[row * XP + sl * 32 + p * 8 + 4]);
-            h16x8 h0, h1;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                hp_t x0, x1;
-                q_split(v0[c], oscale, x0, x1);
-                h0[c] = x0; h1[c] = x1;
-                q_split(v1[c], oscale, x0, x1);
-                h0[4 + c] = x0; h1[4 + c] = x1;
-            }
-            unsigned char *dst = yp + (size_t)m * opix + sl * SLAB + p * 16;
-            *reinterpret_cast<h16x8 *>(dst) = h0;
-            *reinterpret_cast<h16x8 *>(dst + 64) = h1;
+            planes_store8(&X2[row * XP + sl * 32 + p * 8], oscale, yp + (size_t)m * opix + sl * SLAB + p * 16);
         }
     }
 }
@@ -650,10 +637,9 @@ __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
 // blockIdx.z with the in-kernel last-arriver reduction of igemm.hip (agent-scope partials, integer ticket, fixed summation
 // order), 72 KiB of LDS so that two workgroups share a CU.  Epilogue through an LDS tile: bias, leaky ReLU or its derivative
 // (dgrad of a conv whose input was activated), fp32 rows with a pitch (the result may be a channel slice of a wider buffer)
-// and / or planes for the next layer.  Weights: the gen image (f16x3_layout.h); the four phases of a transposed face: tconv_axis.
-enum { GEN_EPI_BIAS = 0, GEN_EPI_LRELU = 1, GEN_EPI_DACT = 2 };
-
-constexpr int GTP = GBN + 4;                                         // fp32 pitch of the epilogue tile
+// and / or planes for the next layer.  That tail is stated in f16x3_tail.h (the arrival: splitk_arrive, stem_common.h) and shared
+// with conv_f16x3_img_kernel; this file keeps the scatter (ROWL / COLL), the rows' map (OROW) and its own words for the slab sum.
+// Weights: the gen image (f16x3_layout.h); the four phases of a transposed face: tconv_axis.
 // LDS of a GBM-pixel tile: main loop 2 x (GBM + 128) rows x 64 B x NPL planes, reused by the GBM x 132 float epilogue tile; + tap table
 // 16x16x32 by default: alone the STEM layers are 0-8 % slower with it (more issue slots), inside the training step -- a loaded,
 // power-limited chip -- the step is 0.2 ms faster
@@ -852,17 +838,7 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
     // computes the same values, the last arriver uses them)
     __shared__ float qred[16];
     const float fac = q_inv(a.xq) * q_inv(a.wq);                   // the operands were stored times 2^ex, 2^ew
-    float oscale = 1.f;
-    if (a.yp) {     // scale of the planes output from an upper bound of |output| (see conv_f16x3_kernel)
-        const float xmax = q_amax(a.xq, qred), wmax = q_amax(a.wq, qred);
-        float bm = 0.f;
-        if (a.bias)
-            for (int n = tid; n < a.N; n += GNT) bm = fmaxf(bm, fabsf(a.bias[n]));
-        bm = block_max(bm, qred);
-        const int oe = q_exp((float)(a.C * (PH ? a.btaps : ntaps)) * xmax * wmax + bm);
-        oscale = q_pow2(oe);
-        if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) a.yq[1] = q_pow2(-oe);
-    }
+    const float oscale = tail_oscale<GNT>(a.yp != nullptr, a.xq, a.wq, a.bias, a.N, a.C * (PH ? a.btaps : ntaps), a.yq, blockIdx.x == 0 && blockIdx.y == 0, qred);
     __syncthreads();
     if (!dead && MS == 16) {
         int q = q_begin;
@@ -906,25 +882,20 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
         }
     }
 
-    // ---- sums of this workgroup -> the epilogue tile T (directly, or through the split-K workspace) -----------------------
+    // ---- the tail (f16x3_tail.h).  Stated here: the scatter of the accumulators, tile row -> output row (OROW), the slab sum ----
     float *T = reinterpret_cast<float *>(smem);                     // [GBM][GTP]
     const int Npad = gridDim.y * GBN;
-    // every pass of the epilogue gives a thread the same pieces: column group ec4 (4 floats), tile rows er0 + ERS k
     constexpr int ERS = GNT / 32, ER = GBM / ERS;                   // 8 pieces per thread
     const int ec4 = tid & 31, er0 = tid >> 5;
     f32x4 ev[ER];
-    // output pixel of tile pixel m: itself, or -- phases -- the fine pixel (2 qy + py, 2 qx + px) of the OHf x OWf output
-    auto OROW = [&](int m) -> size_t {
-        if constexpr (!PH) return (size_t)m;
+    // output pixel of tile row `row` or -1: m itself, or -- phases -- fine pixel (2 qy + py, 2 qx + px) inside the (odd) OHf x OWf
+    auto OROW = [&](int row) -> long {
+        const int m = bm0 + row;
+        if (m >= Mtot) return -1;
+        if constexpr (!PH) return m;
         const int ohw = a.OH * a.OW, b = m / ohw, rem = m - b * ohw, qy = rem / a.OW, qx = rem - qy * a.OW;
-        return ((size_t)b * a.OHf + 2 * qy + a.ph[phase].ooy) * a.OWf + 2 * qx + a.ph[phase].oox;
-    };
-    // the tile pixel exists (and -- phases -- its fine pixel lies inside an odd-sized fine grid OHf = 2 OH - 1)
-    auto MOK = [&](int m) -> bool {
-        if (m >= Mtot) return false;
-        if constexpr (!PH) return true;
-        const int ohw = a.OH * a.OW, rem = m % ohw, qy = rem / a.OW, qx = rem - qy * a.OW;
-        return 2 * qy + a.ph[phase].ooy < a.OHf && 2 * qx + a.ph[phase].oox < a.OWf;
+        const int oy = 2 * qy + a.ph[phase].ooy, ox = 2 * qx + a.ph[phase].oox;
+        return oy < a.OHf && ox < a.OWf ? ((long)b * a.OHf + oy) * a.OWf + ox : -1;
     };
     if (nsplit > 1) {
         float *wsp = wsb + (size_t)zsplit * Mtot * Npad;
@@ -936,21 +907,12 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
                 if (m < Mtot) __hip_atomic_store(&wsp[(size_t)m * Npad + n], acc[j][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
-        // arrival protocol of igemm.hip: partials moved with agent-scope accesses (no device-wide fence), stores acknowledged,
-        // one ticket per workgroup; the last arriver owns the tile and re-zeroes the counter
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) {
-            int *c = a.cnt + blockIdx.y * gridDim.x + blockIdx.x;
-            tapi[0] = splitk_last_arriver(c, nsplit);
-        }
-        __syncthreads();
-        if (!tapi[0]) return;
+        if (!splitk_arrive(a.cnt + blockIdx.y * gridDim.x + blockIdx.x, nsplit, tapi)) return;
         constexpr int SC1 = 16;               // sc1: read at the device-coherent level, not this XCD's L2
         const __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc(wsb, 0, (int)((size_t)nsplit * Mtot * Npad * 4), 0x00020000);
         const int sstep = Mtot * Npad * 4;
-        // the last arriver sums the slabs in split order, 4 pieces x 4 splits in flight (the read is latency-bound: ~1 us
-        // per dependent round of cross-XCD sc1 loads; it used to keep 4 loads in flight per thread)
+        // tail_slab_sum<ER, 4> in this kernel's own words: 4 pieces x 4 splits in flight.  Through the helper, in every form of it
+        // that was tried, conv_f16x3_gen_kernel<128, 32> takes 114 vector registers instead of 112.
         int eoff[ER];
 #pragma unroll
         for (int k = 0; k < ER; ++k) {
@@ -959,7 +921,6 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
         }
 #pragma unroll
         for (int k = 0; k < ER; ++k) ev[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // (4 pieces x 4 splits = 16 loads = 64 registers per round: the kernel keeps its two workgroups per CU -- 128 registers)
 #pragma unroll
         for (int kb = 0; kb < ER; kb += 4)
             for (int sp = 0; sp < nsplit; sp += 4) {
@@ -984,74 +945,18 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
 #pragma unroll
         for (int k = 0; k < ER; ++k) ev[k] = *reinterpret_cast<const f32x4 *>(&T[(er0 + ERS * k) * GTP + ec4 * 4]);
     }
-    float omax = 0.f;
-    // ---- bias / activation, fp32 rows (16 bytes per thread), activated values into T for the planes pass.  A thread's four
-    // columns are the same in every pass (GNT % 32 == 0): its bias values are loaded once, the z rows of the DACT epilogue all at
-    // once (per-row dependent loads cost ~0.5 us each: 8 us of a 26 us launch)
-    const int ecol = bn0 + ec4 * 4;
-    const bool colok = ecol < a.N;                      // N % 4 == 0 (host check)
-    f32x4 ebias = {0.f, 0.f, 0.f, 0.f};
-    if (a.bias && colok) {               // parameters may sit at any 4-byte offset of a flat buffer: scalar loads
-#pragma unroll
-        for (int c = 0; c < 4; ++c) ebias[c] = a.bias[ecol + c];
-    }
-    f32x4 ez[ER];
-    if (a.epi == GEN_EPI_DACT) {
-#pragma unroll
-        for (int k = 0; k < ER; ++k) {
-            const int m = bm0 + er0 + ERS * k;
-            ez[k] = (colok && MOK(m)) ? *reinterpret_cast<const f32x4 *>(a.z + OROW(m) * a.ldz + ecol) : f32x4{1.f, 1.f, 1.f, 1.f};
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < ER; ++k) {
-        const int row = er0 + ERS * k, m = bm0 + row;
-        f32x4 v = ev[k] * fac + ebias;
-        if (a.epi == GEN_EPI_LRELU) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) v[c] = v[c] > 0.f ? v[c] : v[c] * a.slope;
-        } else if (a.epi == GEN_EPI_DACT) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) v[c] = ez[k][c] > 0.f ? v[c] : v[c] * a.slope;
-        }
-        if (colok && MOK(m)) {
-            if (a.y) *reinterpret_cast<f32x4 *>(a.y + OROW(m) * a.ldy + ecol) = v;
-            omax = fmaxf(fmaxf(omax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
-        }
-        if (a.yp) *reinterpret_cast<f32x4 *>(&T[row * GTP + ec4 * 4]) = v;
-    }
-    if (a.yq) {
-        omax = block_max(omax, qred);
-        if (tid == 0) {
-            a.yq[QREC_HDR + blockIdx.y * gridDim.x + blockIdx.x] = omax;
-            if (blockIdx.x == 0 && blockIdx.y == 0) {
-                q_header(a.yq, gridDim.x * gridDim.y);
-                if (!a.yp) a.yq[1] = 1.f;
-            }
-        }
-    }
+    const int ecol = bn0 + (tid & 31) * 4;
+    float omax = tail_rows<GBM, GNT>(a, ev, T, ecol, fac, tail_bias4(a.bias, ecol, a.N), OROW);
+    tail_record(a.yq, a.yp != nullptr, omax, qred, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
     if (a.yp) {
         __syncthreads();
         const int oslab = a.N / KC, opix = oslab * SLAB;
         unsigned char *yp = static_cast<unsigned char *>(a.yp);
         for (int e = tid; e < GBM * (GBN / 8); e += GNT) {
-            const int row = e / (GBN / 8), c8 = e - row * (GBN / 8);
-            const int m = bm0 + row, n = bn0 + c8 * 8;
-            if (!MOK(m) || n >= a.N) continue;              // N % 32 == 0 for planes (host check)
-            const f32x4 v0 = *reinterpret_cast<const f32x4 *>(&T[row * GTP + c8 * 8]);
-            const f32x4 v1 = *reinterpret_cast<const f32x4 *>(&T[row * GTP + c8 * 8 + 4]);
-            h16x8 h0, h1;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                hp_t x0, x1;
-                q_split(v0[c], oscale, x0, x1);
-                h0[c] = x0; h1[c] = x1;
-                q_split(v1[c], oscale, x0, x1);
-                h0[4 + c] = x0; h1[4 + c] = x1;
-            }
-            unsigned char *dst = yp + OROW(m) * opix + (n >> 5) * SLAB + ((n >> 3) & 3) * 16;
-            *reinterpret_cast<h16x8 *>(dst) = h0;
-            *reinterpret_cast<h16x8 *>(dst + 64) = h1;
+            const int row = e / (GBN / 8), c8 = e - row * (GBN / 8), n = bn0 + c8 * 8;
+            const long m = OROW(row);
+            if (m < 0 || n >= a.N) continue;                // N % 32 == 0 for planes (host check)
+            planes_store8(&T[row * GTP + c8 * 8], oscale, yp + m * opix + (n >> 5) * SLAB + ((n >> 3) & 3) * 16);
         }
     }
 }

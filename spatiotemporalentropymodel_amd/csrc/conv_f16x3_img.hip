@@ -29,13 +29,14 @@
 // whose slabs last one chunk, still has a chunk of latency cover).  vmcnt is counted by hand: LDS-DMA and register loads
 // retire in issue order, and the two DMA instructions of chunk c + 1 are always the youngest at the top of chunk c.
 //
-// Epilogue, split-K (sc1 partial tiles, ticket, last arriver sums in split order), scale records: conv_f16x3_gen_kernel's.
+// Epilogue, split-K (sc1 partial tiles, ticket, last arriver sums in split order), scale records: the tail shared with
+// conv_f16x3_gen_kernel (f16x3_tail.h; splitk_arrive, stem_common.h); this file keeps the scatter (PIXL) and the rows' map (MOF).
 #include <math.h>
 #include <stdlib.h>
 
 #include <type_traits>
 
-#include "f16x3_layout.h"
+#include "f16x3_tail.h"
 
 namespace {
 
@@ -44,12 +45,10 @@ constexpr int TS = 16, TPX = TS * TS;                      // 16 x 16 output pix
 constexpr int HPMAX = TS + 4, NHMAX = HPMAX * HPMAX;       // halo at 5x5
 constexpr int IA_PLANE = NHMAX * 64, IA_BUF = NPL * IA_PLANE;       // 25600 / 51200
 constexpr int NRING = 3;
-constexpr int ITP = GBN + 4;                               // fp32 pitch of the epilogue tile
 constexpr int ILDS_MAIN = 2 * IA_BUF + NRING * GB_BUF;     // 151552
-static_assert(TPX * ITP * 4 <= ILDS_MAIN, "the epilogue tile re-uses the main loop's LDS");
+static_assert(TPX * GTP * 4 <= ILDS_MAIN, "the epilogue tile re-uses the main loop's LDS");
 constexpr int ILDS = ILDS_MAIN + 32 * 4;                   // + reduction scratch and the last-arriver flag
 constexpr int NTHR = 512;                                  // threads
-enum { EPI_BIAS = 0, EPI_LRELU = 1, EPI_DACT = 2 };
 
 struct ImgArgs {
     const void *xp, *wp;
@@ -199,11 +198,7 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
     // columns are the same in every pass of the epilogue (512 threads = 16 rows x 32 column groups): its bias values are loaded here
     const float fac = q_inv(a.xq) * q_inv(a.wq);
     const int ecol = bn0 + (tid & 31) * 4;
-    f32x4 ebias = {0.f, 0.f, 0.f, 0.f};
-    if (a.bias && ecol < a.N) {
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) ebias[cc] = a.bias[ecol + cc];          // parameters may sit at any 4-byte offset of a flat buffer
-    }
+    const f32x4 ebias = tail_bias4(a.bias, ecol, a.N);
     float oscale = 1.f;
     if (a.yp) {
         // max |x| and max |w| over the slots of the operands' records and max |bias|: the loads of all three go out together,
@@ -227,9 +222,7 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
         for (int w8 = 1; w8 < NTHR / 64; ++w8) {
             xmax = fmaxf(xmax, red[w8]); wmax = fmaxf(wmax, red[8 + w8]); bm = fmaxf(bm, red[16 + w8]);
         }
-        const int oe = q_exp((float)(a.C * a.ntaps) * xmax * wmax + bm);
-        oscale = q_pow2(oe);
-        if (BX == 0 && BY == 0 && tid == 0) a.yq[1] = q_pow2(-oe);
+        oscale = tail_oscale_of((float)(a.C * a.ntaps) * xmax * wmax + bm, a.yq, BX == 0 && BY == 0);
     }
     if (q_begin < q_end) {
         storeA(0);
@@ -368,7 +361,7 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the look-ahead DMA of the last chunks still writes LDS
     __syncthreads();            // every wavefront is done with the operand images: the epilogue tile takes their place
 
-    // ---- sums of this workgroup -> the epilogue tile Tt (directly, or through the split-K workspace) --------------------------
+    // ---- the tail (f16x3_tail.h).  Stated here: the scatter of the accumulators and how a tile pixel maps to an output row (MOF) ----
     // accumulator register r of MFMA tile mi: tile row rho = (r & 3) + 8 (r >> 2) + 4 lh -> pixel (4 wm + 2 mi + (rho >> 4), rotated column)
     auto PIXL = [&](int mi, int r) {
         const int rho = (r & 3) + 8 * (r >> 2) + 4 * lh;
@@ -379,7 +372,7 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
         const int oy = y0 + (pix >> 4), ox = x0 + (pix & 15);
         return (oy < a.H && ox < a.W) ? (bimg * a.H + oy) * a.W + ox : -1;
     };
-    float *Tt = reinterpret_cast<float *>(smem);                   // [256][ITP]
+    float *Tt = reinterpret_cast<float *>(smem);                   // [256][GTP]
     const int Npad = GY * GBN;
     // every pass below gives a thread the same pieces: column group ec4 = tid & 31 (4 floats), tile rows (tid >> 5) + 16 k
     constexpr int ER = TPX / (NTHR / 32);                          // 16 pieces per thread
@@ -389,17 +382,9 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
 #pragma unroll
     for (int k = 0; k < ER; ++k) em[k] = MOF(er0 + 16 * k);
     if (a.nsplit > 1) {
-        // partial tile -> workspace, one 4-byte agent-scope store per accumulator element (each register: two 128-byte row
-        // segments), then the arrival protocol of igemm.hip: stores acknowledged, one ticket per workgroup, the last arriver owns
-        // the tile and re-zeroes the counter.  NOT 16-byte `buffer_store ... sc1` stores of the tile staged through LDS: with
-        // those the ticket overtook the data on the first launch after the workspace was (re)allocated -- the last arriver
-        // summed the allocation's zeros for a few pieces (tools/debug/repro_fwd.py: 40 of 40 fresh runs; this form and a
-        // plain-store + agent-release form: 0 of 40)
-        // (a last arriver that keeps its own tile in LDS instead was measured slower in the step: DESIGN.md 7)
-        constexpr int SC1 = 16;
-        const __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc(a.ws, 0, (int)((size_t)a.nsplit * Mtot * Npad * 4), 0x00020000);
-        const int sstep = Mtot * Npad * 4;
-        int eoff[ER];
+        // partial tile -> workspace, one 4-byte agent-scope store per accumulator element (why not wider: splitk_arrive,
+        // stem_common.h; a last arriver that keeps its own tile in LDS instead was measured slower in the step: DESIGN.md 7)
+        int eoff[ER];                                              // byte offsets of this thread's pieces inside a slab
 #pragma unroll
         for (int k = 0; k < ER; ++k) eoff[k] = em[k] >= 0 ? (em[k] * Npad + bn0 + ec4 * 4) * 4 : OOR;
         float *wsp = a.ws + (size_t)zsplit * Mtot * Npad;
@@ -415,33 +400,8 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
                         __hip_atomic_store(&wsp[(size_t)m * Npad + bn0 + wn * 64 + nj * 32 + lr], acc[mi][nj][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) flag[0] = splitk_last_arriver(cn, a.nsplit);
-        __syncthreads();
-        if (!flag[0]) return;
-        // the owner sums the slabs in split order (its own included: one fixed order whoever arrives last), 8 rows x 4
-        // splits = 32 sc1 loads in flight per thread: the read is latency-bound (cross-XCD, ~1 us per dependent round)
-#pragma unroll
-        for (int k = 0; k < ER; ++k) ev[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kb = 0; kb < ER; kb += 8) {
-            for (int sp = 0; sp < a.nsplit; sp += 4) {
-                f32x4 tt[8][4];
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const bool other = sp + u < a.nsplit;
-                        const int so = (other ? sp + u : 0) * sstep;
-                        tt[k][u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rws, other ? eoff[kb + k] : OOR, so, SC1));
-                    }
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) ev[kb + k] += tt[k][u];          // beyond nsplit: zeros (out-of-range loads)
-            }
-        }
+        if (!splitk_arrive(cn, a.nsplit, flag)) return;
+        tail_slab_sum<ER, 8>(ev, a.ws, a.nsplit, Mtot * Npad, eoff);
     } else {
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
@@ -449,46 +409,14 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
             for (int r = 0; r < 16; ++r) {
                 const int pix = PIXL(mi, r);
 #pragma unroll
-                for (int nj = 0; nj < 2; ++nj) Tt[pix * ITP + wn * 64 + nj * 32 + lr] = acc[mi][nj][r];
+                for (int nj = 0; nj < 2; ++nj) Tt[pix * GTP + wn * 64 + nj * 32 + lr] = acc[mi][nj][r];
             }
         __syncthreads();
 #pragma unroll
-        for (int k = 0; k < ER; ++k) ev[k] = *reinterpret_cast<const f32x4 *>(&Tt[(er0 + 16 * k) * ITP + ec4 * 4]);
+        for (int k = 0; k < ER; ++k) ev[k] = *reinterpret_cast<const f32x4 *>(&Tt[(er0 + 16 * k) * GTP + ec4 * 4]);
     }
-    // ---- bias / activation, fp32 rows (16 bytes per thread), activated values into Tt for the planes pass -------------------------
-    float omax = 0.f;
-    const bool colok = ecol < a.N;                                 // N % 4 == 0 (host check)
-    f32x4 ez[ER];
-    if (a.epi == EPI_DACT) {
-#pragma unroll
-        for (int k = 0; k < ER; ++k) ez[k] = (colok && em[k] >= 0) ? *reinterpret_cast<const f32x4 *>(a.z + (size_t)em[k] * a.ldz + ecol) : f32x4{1.f, 1.f, 1.f, 1.f};
-    }
-#pragma unroll
-    for (int k = 0; k < ER; ++k) {
-        f32x4 v = ev[k] * fac + ebias;
-        if (a.epi == EPI_LRELU) {
-#pragma unroll
-            for (int cc = 0; cc < 4; ++cc) v[cc] = v[cc] > 0.f ? v[cc] : v[cc] * a.slope;
-        } else if (a.epi == EPI_DACT) {
-#pragma unroll
-            for (int cc = 0; cc < 4; ++cc) v[cc] = ez[k][cc] > 0.f ? v[cc] : v[cc] * a.slope;
-        }
-        if (colok && em[k] >= 0) {
-            if (a.y) *reinterpret_cast<f32x4 *>(a.y + (size_t)em[k] * a.ldy + ecol) = v;
-            omax = fmaxf(fmaxf(omax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
-        }
-        if (a.yp) *reinterpret_cast<f32x4 *>(&Tt[(er0 + 16 * k) * ITP + ec4 * 4]) = v;
-    }
-    if (a.yq) {
-        omax = block_max<NTHR>(omax, red);
-        if (tid == 0) {
-            a.yq[QREC_HDR + BY * GX + BX] = omax;
-            if (BX == 0 && BY == 0) {
-                q_header(a.yq, GX * GY);
-                if (!a.yp) a.yq[1] = 1.f;
-            }
-        }
-    }
+    float omax = tail_rows<TPX, NTHR>(a, ev, Tt, ecol, fac, ebias, MOF);
+    tail_record<NTHR>(a.yq, a.yp != nullptr, omax, red, BY * GX + BX, GX * GY);
     if (a.yp) {
         __syncthreads();
         const int oslab = a.N / KC, opix = oslab * SLAB;
@@ -499,20 +427,7 @@ __global__ __launch_bounds__(NTHR) void conv_f16x3_img_kernel(const ImgArgs a)
             for (int k = 0; k < TPX / (NTHR / 16); ++k) {
                 const int row = (tid >> 4) + 32 * k, m = MOF(row);
                 if (m < 0) continue;
-                const f32x4 v0 = *reinterpret_cast<const f32x4 *>(&Tt[row * ITP + c8 * 8]);
-                const f32x4 v1 = *reinterpret_cast<const f32x4 *>(&Tt[row * ITP + c8 * 8 + 4]);
-                h16x8 h0, h1;
-#pragma unroll
-                for (int cc = 0; cc < 4; ++cc) {
-                    hp_t x0h, x1h;
-                    q_split(v0[cc], oscale, x0h, x1h);
-                    h0[cc] = x0h; h1[cc] = x1h;
-                    q_split(v1[cc], oscale, x0h, x1h);
-                    h0[4 + cc] = x0h; h1[4 + cc] = x1h;
-                }
-                unsigned char *dst = yp + (size_t)m * opix + (pn >> 5) * SLAB + ((pn >> 3) & 3) * 16;
-                *reinterpret_cast<h16x8 *>(dst) = h0;
-                *reinterpret_cast<h16x8 *>(dst + 64) = h1;
+                planes_store8(&Tt[row * GTP + c8 * 8], oscale, yp + (size_t)m * opix + (pn >> 5) * SLAB + ((pn >> 3) & 3) * 16);
             }
         }
     }

@@ -481,16 +481,8 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void igemm_kernel(const
         // are moved with agent-scope accesses (sc1: write-through stores, L2-bypassing loads), every thread waits for its
         // own stores to be acknowledged (vmcnt 0), the workgroup meets at a barrier and ONE thread takes a ticket.  The
         // workgroup that draws the last ticket knows all nsplit partial tiles are complete; it re-zeroes the counter for
-        // the next launch.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int *flag = tapi;                     // LDS scratch, free after the main loop
-        if (tid == 0) {
-            int *c = a.cnt + ((size_t)zphase * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-            flag[0] = splitk_last_arriver(c, a.nsplit);
-        }
-        __syncthreads();
-        if (!flag[0]) return;
+        // the next launch.  (tapi: LDS scratch, free after the main loop)
+        if (!splitk_arrive(a.cnt + ((size_t)zphase * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, a.nsplit, tapi)) return;
         // y[pix][n] = epi(bias[n] + sum_s ws[s][pix][n]): rows of the tile, 4 channels per thread, fixed split order.  The
         // partials are fetched with sc1 (agent-scope) buffer loads, 4 splits in flight per thread.
         constexpr int NQ = BN / 4;

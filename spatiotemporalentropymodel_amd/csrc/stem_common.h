@@ -179,6 +179,19 @@ __device__ inline bool splitk_last_arriver(int *counter, int nsplit)
     }
     return last;
 }
+// The whole arrival, called by EVERY thread of a workgroup right behind its partial-tile stores: stores acknowledged, barrier, one
+// thread takes the ticket, barrier; true in every thread of the last arriver.  lds_flag: one int of LDS nobody else uses now.
+// The partial tile is written with 4-byte agent-scope stores, NOT with 16-byte `buffer_store ... sc1` stores of the tile staged
+// through LDS: with those the ticket overtook the data on the first launch after the workspace was (re)allocated -- the last arriver
+// summed the allocation's zeros for a few pieces (tools/debug/repro_fwd.py: 40 of 40 fresh runs; this form: 0 of 40).
+__device__ inline bool splitk_arrive(int *counter, int nsplit, int *lds_flag)
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) lds_flag[0] = splitk_last_arriver(counter, nsplit);
+    __syncthreads();
+    return lds_flag[0] != 0;
+}
 // the two fp16 numbers whose sum is x * s (s a power of two)
 __device__ inline void q_split(const float x, const float s, hp_t &h0, hp_t &h1)
 {

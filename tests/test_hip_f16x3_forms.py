@@ -17,23 +17,25 @@ U(-1, 1) times that scale, z holds exact 0.0 and -0.0.  Planes outputs are held 
 the channel's maximum or the grid of the second fp16 number, 2^-24 of the unit in the scale record) and to
 test_hip_f16x3.planes_match against the fp32 copy of the same launch.
 
-Exact relations asserted on top (lines of csrc/conv_f16x3_img.hip unless stated; conv_f16x3.hip has the same statements):
-  * sentinels outside the output's channel slice are untouched (the stores are `colok && em[k] >= 0` rows of 16 bytes at
-    a.y + em[k] * ldy + ecol);
+Exact relations asserted on top (lines of csrc/f16x3_tail.h, the tail both kernels share, unless stated):
+  * sentinels outside the output's channel slice are untouched (tail_rows: the stores are `colok && m >= 0` rows of 16 bytes
+    at a.y + m * a.ldy + ecol, m = the kernel's output row of the tile row: MOF in conv_f16x3_img.hip, OROW in conv_f16x3.hip);
   * the same forced launch twice into the same workspace is bit-identical, fp32 and planes, scale records included byte for
-    byte ("the owner sums the slabs in split order (its own included: one fixed order whoever arrives last)"; q_header zeroes
-    the reserved words, stem_common.h);
+    byte (tail_slab_sum: "sums the nsplit slabs ... in split order, its own included at its place: one fixed order whoever
+    arrives last"; conv_f16x3.hip states the same loop itself; q_header zeroes the reserved words, stem_common.h);
   * after every split launch the first 64 KiB of the workspace are zero (splitk_last_arriver re-arms the counter);
   * POISONED SLABS: before each split launch everything behind the counters is NaN.  A workgroup writes every element of its
-    partial tile that lies inside the image (`if (m >= 0)` stores of all 128 columns, dead wavefronts included: their
-    accumulators are zero) and the owner reads exactly those (eoff[k] = em[k] >= 0 ? ... : OOR), so a sum that includes an
-    element nobody wrote THIS launch is NaN and fails the gate at once; columns >= N and rows outside the image are discarded;
+    partial tile that lies inside the image (conv_f16x3_img.hip: `if (m >= 0)` stores of all 128 columns, dead wavefronts
+    included: their accumulators are zero; conv_f16x3.hip: `if (m < Mtot)`) and the owner reads exactly those
+    (conv_f16x3_img.hip: eoff[k] = em[k] >= 0 ? ... : OOR; conv_f16x3.hip: eoff[k] = m < Mtot ? ... : OOR), so a sum that
+    includes an element nobody wrote THIS launch is NaN and fails the gate at once; columns >= N and rows outside the image
+    are discarded;
   * a forced split with a null workspace runs unsplit ("no workspace: unsplit", conv_f16x3.hip) and equals forced s = 1 to the bit;
   * on the image-tile form conv(2^kx x, 2^kw w) == 2^(kx+kw) conv(x, w) bit for bit (the scale records carry the exponents:
     fac = q_inv(xq) * q_inv(wq) is a power of two), an all-zero input gives exact zeros and the record (1.0, 0.0);
-  * fp32 output with a record but no planes (yq set, yp null): the header says inv = 1 (`if (!a.yp) a.yq[1] = 1.f`), one slot per
-    workgroup of the grid's first two dimensions, their maximum is max|y|, and stem_f16x2_split_nhwc fed that record as src_q
-    writes the bytes F16Planes.split(y) writes.
+  * fp32 output with a record but no planes (yq set, yp null): the header says inv = 1 (tail_record:
+    `if (!planes) yq[1] = 1.f`), one slot per workgroup of the grid's first two dimensions, their maximum is max|y|, and
+    stem_f16x2_split_nhwc fed that record as src_q writes the bytes F16Planes.split(y) writes.
 
 Exclusions -- refused by the library with an error (asserted), nothing else is left out:
   * planes output of the N = 132 shape ("planes output needs N % 32 == 0"): fp32 output with a record instead;
