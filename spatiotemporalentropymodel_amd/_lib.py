@@ -1,5 +1,5 @@
 """ctypes loader for the three C-ABI libraries (include/stem_hip.h + include/stem_ar_batch.h + include/stem_blocks.h +
-include/stem_hyperprior.h + include/stem_eb_filters.h, include/stem_rans.h, include/stem_dp.h).
+include/stem_hyperprior.h + include/stem_eb_filters.h + include/stem_gdn1.h, include/stem_rans.h, include/stem_dp.h).
 
 The headers are the single statement of the ABI: every prototype and descriptor structure below is read from them (_abi.py).
 
@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 from . import _abi
 
@@ -52,6 +53,8 @@ _HIP_BLOCKS_PROTO, _HIP_BLOCKS_SIG, _ = _tables("stem_blocks.h")
 _HIP_HYPERPRIOR_PROTO, _HIP_HYPERPRIOR_SIG, _ = _tables("stem_hyperprior.h")
 # libstem_hip.so's EntropyBottleneck kernels for any `filters` tuple (csrc/eb_filters.hip; not launch-tape entries either)
 _HIP_EBF_PROTO, _HIP_EBF_SIG, _ = _tables("stem_eb_filters.h")
+# libstem_hip.so's GDN1 kernels (csrc/gdn1.hip; not launch-tape entries either)
+_HIP_GDN1_PROTO, _HIP_GDN1_SIG, _ = _tables("stem_gdn1.h")
 _RANS_PROTO, _RANS_SIG, _RANS_RESTYPE = _tables("stem_rans.h")
 _DP_PROTO, _DP_SIG, _ = _tables("stem_dp.h")
 _STRUCTS = _abi.structs(_header("stem_hip.h"))
@@ -98,7 +101,7 @@ def hip():
                 f"{HIP_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the STEM kernels.")
         lib = C.CDLL(HIP_SO)
-        for protos in (_HIP_PROTO, _HIP_BATCH_PROTO, _HIP_BLOCKS_PROTO, _HIP_HYPERPRIOR_PROTO, _HIP_EBF_PROTO):
+        for protos in (_HIP_PROTO, _HIP_BATCH_PROTO, _HIP_BLOCKS_PROTO, _HIP_HYPERPRIOR_PROTO, _HIP_EBF_PROTO, _HIP_GDN1_PROTO):
             _bind(lib, protos)
         _hip = lib
     return _hip
@@ -136,6 +139,18 @@ def declared_hip_hyperprior_symbols():
 
 def declared_hip_eb_filters_symbols():
     return sorted(_HIP_EBF_SIG)
+
+
+def declared_hip_gdn1_symbols():
+    return sorted(_HIP_GDN1_SIG)
+
+
+def header_macro(header, name):
+    """integer value of `#define <name> <integer>` in include/<header> (the caps and chunk sizes the headers state)"""
+    m = re.search(rf"^[ \t]*#[ \t]*define[ \t]+{name}[ \t]+(\d+)\b", open(_header(header)).read(), flags=re.M)
+    if not m:
+        raise StemLibraryError(f"include/{header} does not define {name} as an integer")
+    return int(m.group(1))
 
 
 def dp():

@@ -1072,6 +1072,59 @@ def _nhwc_arg(t, name):
     return t.data_ptr(), ld
 
 
+GDN1_MAX_C = _lib.header_macro("stem_gdn1.h", "STEM_GDN1_MAX_C")
+GDN1_PIX_CHUNK = _lib.header_macro("stem_gdn1.h", "STEM_GDN1_PIX_CHUNK")
+
+
+def _gdn1_params(beta, gamma, Cc, who):
+    _require_cuda(beta, gamma)
+    if tuple(beta.shape) != (Cc,) or tuple(gamma.shape) != (Cc, Cc):
+        raise ValueError(f"{who}: beta {tuple(beta.shape)} / gamma {tuple(gamma.shape)} do not belong to {Cc} channels")
+    return beta.detach().contiguous(), gamma.detach().contiguous()
+
+
+def gdn1_forward(x, beta, gamma, inverse=False, beta_min=1e-6, out=None):
+    """GDN1 (compressai/layers/gdn.py:70-96): y = x / (beta' + gamma' |x|), inverse: y = x * (beta' + gamma' |x|), from the STORED
+    beta [C] and gamma [C, C]; one launch of csrc/gdn1.hip.  x and out may be channel-slice views; any C up to GDN1_MAX_C."""
+    B, Cc, H, W = x.shape
+    beta, gamma = _gdn1_params(beta, gamma, Cc, "gdn1_forward")
+    if out is None:
+        out = empty_nhwc(B, Cc, H, W, x.device)
+    elif tuple(out.shape) != tuple(x.shape):
+        raise ValueError(f"gdn1_forward: out {tuple(out.shape)} does not match x {tuple(x.shape)}")
+    (xp, ldx), (op, ldo) = _nhwc_arg(x, "gdn1_forward: x"), _nhwc_arg(out, "gdn1_forward: out")
+    _chk(_lib.hip().stem_gdn1_fwd(xp, ldx, beta.data_ptr(), gamma.data_ptr(), op, ldo, B * H * W, Cc, int(bool(inverse)), float(beta_min),
+                                  _stream()))
+    return out
+
+
+def gdn1_backward(x, dy, beta, gamma, inverse, beta_min, need_dx=True, need_dparams=True, ws=None):
+    """-> (dx, dbeta, dgamma) of gdn1_forward: gradients wrt the input and the STORED parameters; None for what was not asked for.
+    x and dy may be channel-slice views.  The only scratch is one [npix, C] tensor and the partials of the parameter sums; `ws`
+    (a float32 tensor of at least stem_gdn1_bwd_workspace_bytes, whatever it holds) replaces the allocation."""
+    if not (need_dx or need_dparams):
+        raise ValueError("gdn1_backward: nothing to compute")
+    B, Cc, H, W = x.shape
+    if tuple(dy.shape) != tuple(x.shape):
+        raise ValueError(f"gdn1_backward: dy {tuple(dy.shape)} does not match x {tuple(x.shape)}")
+    beta, gamma = _gdn1_params(beta, gamma, Cc, "gdn1_backward")
+    (xp, ldx), (gp, ldg) = _nhwc_arg(x, "gdn1_backward: x"), _nhwc_arg(dy, "gdn1_backward: dy")
+    lib, npix = _lib.hip(), B * H * W
+    dx = empty_nhwc(B, Cc, H, W, x.device) if need_dx else None
+    dbeta, dgamma, ws, nbytes = None, None, None, 0
+    if need_dparams:
+        dbeta, dgamma = ((torch.empty_like if npix else torch.zeros_like)(t) for t in (beta, gamma))
+        nbytes = int(lib.stem_gdn1_bwd_workspace_bytes(npix, Cc))
+        if ws is None:
+            ws = torch.empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)
+        _require_cuda(ws)
+        if ws.numel() * 4 < nbytes or not ws.is_contiguous():
+            raise ValueError(f"gdn1_backward: the workspace holds {ws.numel() * 4} bytes, {nbytes} are needed")
+    _chk(lib.stem_gdn1_bwd(xp, ldx, gp, ldg, beta.data_ptr(), gamma.data_ptr(), _ptr(dx), Cc, _ptr(dbeta), _ptr(dgamma), npix, Cc,
+                           int(bool(inverse)), float(beta_min), _ptr(ws), nbytes, _stream()))
+    return dx, dbeta, dgamma
+
+
 def pixel_shuffle(x, r, slope=1.0, addend=None, out=None):
     """nn.PixelShuffle(r) on NHWC memory with the blocks' followers folded in (csrc/resblock.hip):
     out[b, c, h*r+i, w*r+j] = act(x[b, c*r*r + i*r + j, h, w]) (+ addend), act = LeakyReLU(slope), slope 1.0 = none.

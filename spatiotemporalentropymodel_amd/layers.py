@@ -2,7 +2,7 @@
 kernels through the C ABI -- and the one place that decides which kernel family serves a convolution (`route`).
 
   Conv2d / ConvTranspose2d   torch.nn.Conv2d / ConvTranspose2d as built by compressai/models/utils.py:112-130 (conv / deconv)
-  MaskedConv2d, GDN          compressai/layers/layers.py:21-47, gdn.py:22-67;  LeakyReLU: index-keeping placeholder
+  MaskedConv2d, GDN, GDN1    compressai/layers/layers.py:21-47, gdn.py:22-96;  LeakyReLU: index-keeping placeholder
   FusedSequential            nn.Sequential that plans its children into steps (conv, conv+GDN, conv+LeakyReLU), then runs them
   route / Route / Step       the kernel family of a convolution as a value; f16x3_same_shape: the shape rule engine.py shares
   cat / to_nchw / adaptive_avg_pool2d, the *Function classes      glue operations of the layer-wise models (stem_utils.py, stem_roi.py)
@@ -410,6 +410,27 @@ class GDNFunction(torch.autograd.Function):
         return dx, dbeta, dgamma, None, None
 
 
+class GDN1Function(torch.autograd.Function):
+    """GDN1 on the kernels of csrc/gdn1.hip: any channel count up to F.GDN1_MAX_C; the backward computes what is asked for"""
+
+    @staticmethod
+    def forward(ctx, x, beta, gamma, inverse, beta_min):
+        xin = F.to_nhwc(x)
+        ctx.cfg = (inverse, beta_min)
+        ctx.save_for_backward(xin, beta, gamma)
+        return F.gdn1_forward(xin, beta, gamma, inverse, beta_min)
+
+    @staticmethod
+    def backward(ctx, dy):
+        inverse, beta_min = ctx.cfg
+        xin, beta, gamma = ctx.saved_tensors
+        need_dx, need_dparams = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        if not (need_dx or need_dparams):
+            return None, None, None, None, None
+        dx, dbeta, dgamma = F.gdn1_backward(xin, F.to_nhwc(dy), beta, gamma, inverse, beta_min, need_dx, need_dparams)
+        return dx, (dbeta if ctx.needs_input_grad[1] else None), (dgamma if ctx.needs_input_grad[2] else None), None, None
+
+
 class SFTFunction(torch.autograd.Function):
     """act(x * (1 + gamma) + beta), act = leaky-ReLU(slope) or identity (slope 1): stem_utils.py:41,56-57."""
 
@@ -691,6 +712,20 @@ class GDN(nn.Module):
         return GDNFunction.apply(x, self.beta, self.gamma, self.inverse, self.beta_min)
 
 
+class GDN1(GDN):
+    """Simplified GDN (compressai/layers/gdn.py:70-96): y = x / (beta + gamma |x|), no square and no square root.  A GDN by class,
+    as in the reference, with the same parameters and state-dict keys -- but never by kernel: FusedSequential runs it as a step of
+    its own, so it cannot reach the squared GDN fused into the convolution kernels."""
+
+    def forward(self, x):
+        return GDN1Function.apply(x, self.beta, self.gamma, self.inverse, self.beta_min)
+
+
+def _fusable_gdn(m):
+    """a GDN the conv+GDN kernels compute: the squared form only"""
+    return isinstance(m, GDN) and not isinstance(m, GDN1)
+
+
 class LeakyReLU(nn.LeakyReLU):
     """Placeholder that keeps nn.Sequential indices (`HE.0`, `HE.2`, …) identical to the reference;
     FusedSequential folds it into the preceding convolution's epilogue."""
@@ -720,14 +755,15 @@ class FusedSequential(nn.Sequential):
 
     def plan(self, in_shape, src, grad, on_device, cfg=None, c4gdn=None):
         """The children as a list of Steps for an input of logical shape `in_shape` (other arguments: see `route`).  Pure and cheap:
-        planned at every call.  A GDN behind a convolution is fused where the route has a kernel for it; a LeakyReLU (slope) or
-        ReLU (= slope 0) is folded into the layer-wise kernels' epilogue; planes travel between convolutions on the fp16 kernels."""
+        planned at every call.  A GDN behind a convolution is fused where the route has a kernel for it (a GDN1 never is: always a
+        lone step); a LeakyReLU (slope) or ReLU (= slope 0) is folded into the layer-wise kernels' epilogue; planes travel between
+        convolutions on the fp16 kernels."""
         mods, steps, shape, i = list(self), [], tuple(in_shape), 0
         kw = dict(grad=grad, on_device=on_device, cfg=_runtime(cfg), c4gdn=c4gdn)
 
         def routed(j, shape, src, consumer=None):
             nxt = mods[j + 1] if j + 1 < len(mods) else None
-            gdn = ("igdn" if nxt.inverse else "gdn") if isinstance(nxt, GDN) else None
+            gdn = ("igdn" if nxt.inverse else "gdn") if _fusable_gdn(nxt) else None
             return route(mods[j], shape, src, gdn=gdn, act=isinstance(nxt, _ACTIVATIONS), consumer=consumer, **kw)
 
         while i < len(mods):
@@ -741,7 +777,7 @@ class FusedSequential(nn.Sequential):
             # who reads the output: the convolution behind a fusable GDN / a folded activation, or the very next child
             nxt = mods[i + 1] if i + 1 < len(mods) else None
             folded = isinstance(nxt, _ACTIVATIONS)
-            j = i + (2 if folded or (isinstance(nxt, GDN) and not nxt.inverse) else 1)
+            j = i + (2 if folded or (_fusable_gdn(nxt) and not nxt.inverse) else 1)
             out_shape, consumer = _out_shape(m, shape), None
             if j < len(mods) and type(mods[j]) is Conv2d and mods[j].in_channels == m.out_channels:
                 consumer = routed(j, out_shape, "nhwc" if folded else "planes")

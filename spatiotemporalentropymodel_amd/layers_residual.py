@@ -58,6 +58,8 @@ def _subpel(seq, x, slope=1.0, addend=None):
 
 def _conv(m, x, slope=None, gdn=None):
     """convolution `m`, then a leaky ReLU of `slope` (None: none) or the GDN module `gdn`, on the route `layers.route` gives"""
+    if gdn is not None and not L._fusable_gdn(gdn):          # a GDN1: never inside a convolution's kernel
+        return gdn(_conv(m, x, slope))
     act = F.ACT_NONE if slope is None else F.ACT_LRELU
     slope = F.LRELU_SLOPE if slope is None else float(slope)
     r = L.route(m, x.shape, L._src(x), grad=torch.is_grad_enabled(), on_device=x.is_cuda,

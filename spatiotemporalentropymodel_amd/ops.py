@@ -10,6 +10,36 @@ Their forward is kept for host-side use (e.g. `update()`), on whatever device th
 import torch
 import torch.nn as nn
 
+from . import functional as F
+
+__all__ = ["ste_round", "LowerBound", "NonNegativeParametrizer"]
+
+
+class STERoundFunction(torch.autograd.Function):
+    """round half to even on the device (stem_round); the gradient passes unchanged"""
+
+    @staticmethod
+    def forward(ctx, x):
+        F._require_cuda(x)
+        order = sorted(range(x.dim()), key=lambda d: (x.stride(d), x.shape[d]), reverse=True)
+        packed = x.numel() == 0 or x.permute(order).is_contiguous()          # some permutation of a contiguous block
+        if not packed:
+            x = x.contiguous()
+        out = torch.empty_strided(x.shape, x.stride(), device=x.device, dtype=x.dtype)
+        if x.numel():
+            F._chk(F._lib.hip().stem_round(x.data_ptr(), out.data_ptr(), x.numel(), F._stream()))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return g
+
+
+def ste_round(x):
+    """Rounding with the identity as its derivative (compressai/ops/ops.py:18).  The result has its input's memory layout (NHWC
+    stays NHWC); a view with gaps, such as a channel slice, is made contiguous first."""
+    return STERoundFunction.apply(x)
+
 
 class LowerBoundFunction(torch.autograd.Function):
     """max(x, bound) with the gradient passed through when x >= bound or when it pushes x up."""
