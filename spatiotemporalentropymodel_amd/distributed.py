@@ -98,10 +98,18 @@ def all_reduce_sum_(t: torch.Tensor):
 
 
 def broadcast_parameters(module: torch.nn.Module, src=0):
-    """Replicas must start identical (weights stay replicated afterwards: same gradient, same update)."""
+    """Replicas must start identical (weights stay replicated afterwards: same gradient, same update).  The values arrive through
+    `.data`, which moves no version counter: a rank that has already run a forward (a warm-up, a self-check) holds packed weight
+    copies and host CDF tables of its OLD values, so both are invalidated here."""
     if not dist.is_initialized():
         return
+    from .entropy_models import EntropyModel
+    from .layers import bump_weight_epoch
     stage = dist.get_backend() == "gloo"
+    bump_weight_epoch(list(module.parameters()))
+    for m in module.modules():
+        if isinstance(m, EntropyModel):
+            m._tables = None
     for t in list(module.parameters()) + list(module.buffers()):
         if not t.numel():
             continue

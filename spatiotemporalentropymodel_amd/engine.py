@@ -452,9 +452,11 @@ class StemEngine:
             st = bs[which] = F.make_stream(device, "branch")
         return st
 
-    def ensure_packed(self, block_max=None):
+    def ensure_packed(self, block_max=None, split=True):
         """(Re)build every layer's packed weight copies with ONE kernel launch when any weight changed.  Inside
         StemEngine.forward the check has already run for the whole schedule (`_checked`).
+        split=False: every launch on the current stream, whatever `split_pack` says (a caller that orders all later work after
+        the current stream and cannot wait for the events of the side streams: tape.TapedPFrameStep).
         block_max = (maxima, flat): the per-chunk maxima an optimiser pass just left for the flat parameter buffer `flat`
         (optim.step(block_max=True)); the fp16 images of weights inside that buffer take their scales from them instead of a
         maximum launch.  Only meaningful in the call that directly follows that optimiser step."""
@@ -470,7 +472,12 @@ class StemEngine:
         if block_max is not None and self.pack_pair and self._pack_pairs(*block_max):
             self._pack_key = self._weights_key()
             return
-        side = self.side_stream(dev) if self.split_pack and not torch.cuda.is_current_stream_capturing() else None
+        side = self.side_stream(dev) if split and self.split_pack and not torch.cuda.is_current_stream_capturing() else None
+        if not split:
+            # ... and after whatever the engine's own streams still hold: an earlier packing launch may be among it
+            for st in list(self._side.values()) + list(getattr(self, "_bstreams", {}).values()):
+                F.stream_wait(F.cur_stream(dev), st)
+            self._dgrad_pack_event = None
         roles = ((0, 1), (1, 2)) if side is not None else ((0, 2),)
         for lo, hi in roles:                     # descriptor 0 of a layer = forward role, descriptor 1 = input-gradient role
             on_side = side is not None and lo == 1

@@ -32,12 +32,18 @@ def pmf_to_quantized_cdf(pmf, precision=16):
 
 
 class _Tables:
-    """Dense int32 views of (cdf, cdf_length, offset) handed to libstem_rans.so without per-call conversion."""
+    """Dense int32 arrays of (cdf, cdf_length, offset) handed to libstem_rans.so without per-call conversion.  A tensor is COPIED:
+    a numpy view of a host buffer would follow later writes into it and pin its storage (a table that numpy holds cannot be
+    resized by update_registered_buffers)."""
+
+    @staticmethod
+    def _host(a):
+        if torch.is_tensor(a):
+            a = a.detach().to("cpu", torch.int32, copy=True).contiguous().numpy()
+        return np.ascontiguousarray(a, dtype=np.int32)
 
     def __init__(self, cdf, sizes, offsets):
-        self.cdf = np.ascontiguousarray(cdf.detach().cpu().numpy() if torch.is_tensor(cdf) else cdf, dtype=np.int32)
-        self.sizes = np.ascontiguousarray(sizes.detach().cpu().numpy() if torch.is_tensor(sizes) else sizes, dtype=np.int32).reshape(-1)
-        self.offsets = np.ascontiguousarray(offsets.detach().cpu().numpy() if torch.is_tensor(offsets) else offsets, dtype=np.int32).reshape(-1)
+        self.cdf, self.sizes, self.offsets = self._host(cdf), self._host(sizes).reshape(-1), self._host(offsets).reshape(-1)
         assert self.cdf.ndim == 2 and self.cdf.shape[0] == self.sizes.size == self.offsets.size
 
     def args(self):

@@ -81,14 +81,12 @@ class GraphedPFrameStep:
             for _ in range(self.warmup):
                 self._body()
             for o, data, m, v, t in saved:
-                o.flat.data.copy_(data)
+                o.flat.restore(data)                      # (bumps the weight epoch: the capture must CONTAIN the packing launch)
                 o.m.copy_(m)
                 o.v.copy_(v)
                 o.t = t
                 o.sync_device_state()
             self._epoch.zero_()
-            bump_weight_epoch(self.opt.flat.params)       # weights restored + the capture must CONTAIN the packing launch
-            bump_weight_epoch(self.aux_opt.flat.params)
             # host-side Philox offsets as frozen into the graph (tests replay the same stream eagerly)
             self._capture_offsets = {id(m): m._noise_offset for m in (stem.entropy_bottleneck, stem.gaussian_conditional)}
             self.graph = torch.cuda.CUDAGraph()

@@ -55,6 +55,13 @@ class FlatParameters:
             p.grad = p._flat_grad_view
         bump_weight_epoch(self.params)
 
+    def restore(self, data):
+        """Overwrite every parameter with `data` (a tensor of the buffer's size, e.g. an earlier `flat.data.clone()`).  The write
+        goes to the buffer the parameters are views of, which moves none of their version counters: the packed copies of the
+        weights are told here."""
+        self.data.copy_(data)
+        bump_weight_epoch(self.params)
+
     def zero_grad(self):
         join_wgrad_stream()
         if self.grad.is_cuda:

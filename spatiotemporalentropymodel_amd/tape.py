@@ -361,7 +361,9 @@ class TapedPFrameStep:
     copy them before the next call.
 
     Optimiser hyper-parameters (lr, betas, eps, max_norm of both optimisers) are read again at every replay: a scheduler that
-    edits `param_groups[0]["lr"]` between steps (stem/trainSTEM.py:123,290) is honoured.  A schedule the tape cannot hold
+    edits `param_groups[0]["lr"]` between steps (stem/trainSTEM.py:123,290) is honoured.  So are weights written between two
+    steps (a checkpoint load, a broadcast: anything the engine's weight key sees): the recorded step packs the weights at its end
+    for the next forward, so a replay that follows such a write packs them again first.  A schedule the tape cannot hold
     (TapeRefused: device-resident optimiser state, torch operators on device memory inside the step, a launch sequence that
     differs between two steps) keeps running on the ordinary `FusedPFrameStep.step`, with one warning; `taped` tells which."""
 
@@ -460,7 +462,14 @@ class TapedPFrameStep:
             y_hat = self.result[0]["y_hat"]
             self.yhat_slots = self.tape.pointer_slots(y_hat.data_ptr())
             self.yhat_bufs = [y_hat, torch.empty_like(y_hat)] if (self.cond_slots and self.yhat_slots) else None
+            self._weights_key = f.eng._weights_key()
             return res
+        if f.eng._weights_key() != self._weights_key:
+            # somebody wrote the weights between two steps (a checkpoint load, a broadcast).  The recorded step packs them at its
+            # END, for the next forward: this replay's forward would read the copies of the weights as they were before the write.
+            # Pack now, on the key's stream, which the replay's first launches are ordered after.
+            f.eng._pack_key = None
+            f.eng.ensure_packed(split=False)
         if self.cur_slots:
             self.tape.set_pointer(self.cur_slots, y_cur.data_ptr())
         else:
@@ -480,6 +489,7 @@ class TapedPFrameStep:
         for (o, a), d in zip(self._counters(), self.deltas):
             setattr(o, a, getattr(o, a) + d)
         f.after_replay()
+        self._weights_key = f.eng._weights_key()
         return result
 
     def finish(self):
