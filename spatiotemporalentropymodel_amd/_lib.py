@@ -1,5 +1,6 @@
 """ctypes loader for the three C-ABI libraries (include/stem_hip.h + include/stem_ar_batch.h + include/stem_blocks.h +
-include/stem_hyperprior.h + include/stem_eb_filters.h + include/stem_gdn1.h, include/stem_rans.h, include/stem_dp.h).
+include/stem_hyperprior.h + include/stem_eb_filters.h + include/stem_gdn1.h + include/stem_validation.h, include/stem_rans.h,
+include/stem_dp.h).
 
 The headers are the single statement of the ABI: every prototype and descriptor structure below is read from them (_abi.py).
 
@@ -55,6 +56,8 @@ _HIP_HYPERPRIOR_PROTO, _HIP_HYPERPRIOR_SIG, _ = _tables("stem_hyperprior.h")
 _HIP_EBF_PROTO, _HIP_EBF_SIG, _ = _tables("stem_eb_filters.h")
 # libstem_hip.so's GDN1 kernels (csrc/gdn1.hip; not launch-tape entries either)
 _HIP_GDN1_PROTO, _HIP_GDN1_SIG, _ = _tables("stem_gdn1.h")
+# libstem_hip.so's eval-mode rate kernels and running loss sum of the validation pass (csrc/entropy.hip; not launch-tape entries either)
+_HIP_VALIDATION_PROTO, _HIP_VALIDATION_SIG, _ = _tables("stem_validation.h")
 _RANS_PROTO, _RANS_SIG, _RANS_RESTYPE = _tables("stem_rans.h")
 _DP_PROTO, _DP_SIG, _ = _tables("stem_dp.h")
 _STRUCTS = _abi.structs(_header("stem_hip.h"))
@@ -101,7 +104,8 @@ def hip():
                 f"{HIP_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the STEM kernels.")
         lib = C.CDLL(HIP_SO)
-        for protos in (_HIP_PROTO, _HIP_BATCH_PROTO, _HIP_BLOCKS_PROTO, _HIP_HYPERPRIOR_PROTO, _HIP_EBF_PROTO, _HIP_GDN1_PROTO):
+        for protos in (_HIP_PROTO, _HIP_BATCH_PROTO, _HIP_BLOCKS_PROTO, _HIP_HYPERPRIOR_PROTO, _HIP_EBF_PROTO, _HIP_GDN1_PROTO,
+                       _HIP_VALIDATION_PROTO):
             _bind(lib, protos)
         _hip = lib
     return _hip
@@ -143,6 +147,10 @@ def declared_hip_eb_filters_symbols():
 
 def declared_hip_gdn1_symbols():
     return sorted(_HIP_GDN1_SIG)
+
+
+def declared_hip_validation_symbols():
+    return sorted(_HIP_VALIDATION_SIG)
 
 
 def header_macro(header, name):

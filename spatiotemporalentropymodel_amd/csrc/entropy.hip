@@ -4,6 +4,7 @@
 #include "stem_common.h"
 #include "ar_canon.h"       // scale_index, for build_indexes_kernel
 #include "entropy_elem.h"   // the Gaussian likelihood element and the noise stream, shared with hyperprior.hip
+#include "../../include/stem_validation.h"   // the eval-mode twins of the fused training glue, at the end of this file
 
 namespace {
 
@@ -1004,5 +1005,161 @@ STEM_EXPORT int stem_eb_aux_loss_grad(const float *quantiles, const float *pack,
     hipLaunchKernelGGL(eb_aux_block_kernel, dim3(1), dim3(AUX_T), lds, (hipStream_t)stream, quantiles, pack, target3, loss, dquantiles, C,
                        accumulate);
     STEM_LAUNCH_CHECK("eb_aux_block");
+    return 0;
+}
+
+// =================================================================================================================
+// Validation glue (include/stem_validation.h).  The eval-mode P-frame forward of a validation pass (stem/trainSTEM.py:265-295) has the
+// training step's problem without its arithmetic: between the convolutions it issues copy, subtract, round, add, the two likelihood
+// kernels, two log-sums and torch scalar operations, each a few microseconds behind ~10 us of dispatch latency, and the `+=` on a host
+// float synchronises twice per frame.  The eval twins of the fused training kernels: rounding instead of noise, no d rate, the same
+// per-workgroup log2 partials; and a finaliser that adds the frame's weighted loss into a device-resident accumulator.
+namespace {
+
+// eb_forward_kernel's mode 1 (the statements in its order: the same bits) + block_log2_partial
+__global__ __launch_bounds__(256) void eb_forward_eval_rate_kernel(const float *z, int ldz, const float *pack, const float *med, float *zhat,
+                                                                   float *lik, double *part, size_t npix, int C, float bound)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    double lg = 0.0;
+    if (i < npix * C) {
+        const size_t pix = i / C;
+        const int c = (int)(i - pix * C);
+        EbPrep e;
+        eb_prepare(pack + (size_t)c * NP, e);
+        float v = z[pix * ldz + c];
+        const float m = med[c];
+        v = rintf(v - m) + m;
+        zhat[i] = v;
+        const float lo = eb_logits<false>(e, v - 0.5f, nullptr, nullptr);
+        const float up = eb_logits<false>(e, v + 0.5f, nullptr, nullptr);
+        const float l = fmaxf(fabsf(eb_tail(lo, up).diff), bound);
+        lik[i] = l;
+        lg = (double)log2f(l);
+    }
+    block_log2_partial(lg, part);
+}
+
+// eb_forward_cm_kernel's mode 1 (one workgroup per channel, eb_prepare_shared) + block_log2_partial: a workgroup's partial is the
+// sum over the channels it visits, as in eb_forward_train_cm_kernel
+__global__ __launch_bounds__(256) void eb_forward_eval_rate_cm_kernel(const float *z, int ldz, const float *pack, const float *med,
+                                                                      float *zhat, float *lik, double *part, size_t npix, int C, float bound)
+{
+    __shared__ float prep[NP];
+    double lg = 0.0;
+    for (int c = blockIdx.x; c < C; c += gridDim.x) {
+        EbPrep e;
+        eb_prepare_shared(pack + (size_t)c * NP, prep, e);
+        for (size_t pix = threadIdx.x; pix < npix; pix += 256) {
+            const size_t i = pix * C + c;
+            float v = z[pix * ldz + c];
+            const float m = med[c];
+            v = rintf(v - m) + m;
+            zhat[i] = v;
+            const float lo = eb_logits<false>(e, v - 0.5f, nullptr, nullptr);
+            const float up = eb_logits<false>(e, v + 0.5f, nullptr, nullptr);
+            const float l = fmaxf(fabsf(eb_tail(lo, up).diff), bound);
+            lik[i] = l;
+            lg += (double)log2f(l);
+        }
+    }
+    block_log2_partial(lg, part);
+}
+
+// gc_forward_kernel's mode 1 + block_log2_partial
+__global__ __launch_bounds__(256) void gc_forward_eval_rate_kernel(const float *y, const float *scales, const float *means, int ldsm,
+                                                                   float *out, float *lik, double *part, size_t npix, int C, float sb, float lb)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    double lg = 0.0;
+    if (i < npix * C) {
+        const size_t pix = i / C;
+        const int c = (int)(i - pix * C);
+        const float mu = means[pix * ldsm + c], sc = scales[pix * ldsm + c];
+        float o = y[i];
+        o = rintf(o - mu) + mu;
+        out[i] = o;
+        const float l = gauss_lik(fabsf(o - mu), sc, sb, lb);
+        lik[i] = l;
+        lg = (double)log2f(l);
+    }
+    block_log2_partial(lg, part);
+}
+
+// em_loss_finalize_kernel's three values (the same sums in the same order, contraction off) -> out3 (optional) and, weighted, into the
+// running sums acc[0..2]; acc[3] collects the weights.  One workgroup: the read-modify-write of acc is ordered by the stream
+__global__ __launch_bounds__(256) void em_loss_accumulate_kernel(const double *py, int ny, const double *pz, int nz, double scale, double weight,
+                                                                 double *out, double *acc)
+{
+    __shared__ double red[2][256];
+    double a = 0.0, b = 0.0;
+    for (int i = threadIdx.x; i < ny; i += 256) a += py[i];
+    for (int i = threadIdx.x; i < nz; i += 256) b += pz[i];
+    red[0][threadIdx.x] = a;
+    red[1][threadIdx.x] = b;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (threadIdx.x < k) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + k];
+            red[1][threadIdx.x] += red[1][threadIdx.x + k];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+        const double y = red[0][0] * scale, z = red[1][0] * scale;
+        const double l = y + z;
+        if (out) {
+            out[0] = y;
+            out[1] = z;
+            out[2] = l;
+        }
+        const double wy = weight * y, wz = weight * z, wl = weight * l;
+        acc[0] = acc[0] + wy;
+        acc[1] = acc[1] + wz;
+        acc[2] = acc[2] + wl;
+        acc[3] = acc[3] + weight;
+    }
+}
+
+}   // namespace
+
+STEM_EXPORT int stem_eb_forward_eval_rate(const float *z, int ldz, const float *pack, const float *medians, float *z_hat, float *lik,
+                                          double *partials, size_t npix, int C, float bound, void *stream)
+{
+    STEM_CHECK_ARG(z && pack && medians && z_hat && lik && partials, "stem_eb_forward_eval_rate: null pointer");
+    STEM_CHECK_ARG(C >= 1 && ldz >= C, "stem_eb_forward_eval_rate: needs C >= 1 and a pixel pitch ldz >= C (C=%d ldz=%d)", C, ldz);
+    STEM_CHECK_ARG(npix <= ((size_t)1 << 31) * 256 / (size_t)C, "stem_eb_forward_eval_rate: npix * C = %zu * %d elements exceed one grid", npix, C);
+    if (npix == 0) return 0;
+    // the form switch of stem_eb_forward: few pixels per channel (hyper-latents) -> one workgroup per channel
+    hipLaunchKernelGGL(npix <= 4096 ? eb_forward_eval_rate_cm_kernel : eb_forward_eval_rate_kernel, dim3(nblk(npix * C)), dim3(256), 0,
+                       (hipStream_t)stream, z, ldz, pack, medians, z_hat, lik, partials, npix, C, bound);
+    STEM_LAUNCH_CHECK("eb_forward_eval_rate");
+    return 0;
+}
+
+STEM_EXPORT int stem_gc_forward_eval_rate(const float *y, const float *scales, const float *means, int ldsm, float *out, float *lik,
+                                          double *partials, size_t npix, int C, float scale_bound, float lik_bound, void *stream)
+{
+    STEM_CHECK_ARG(y && scales && means && out && lik && partials, "stem_gc_forward_eval_rate: null pointer");
+    STEM_CHECK_ARG(C >= 1 && ldsm >= C, "stem_gc_forward_eval_rate: needs C >= 1 and a common pitch ldsm >= C (C=%d ldsm=%d)", C, ldsm);
+    STEM_CHECK_ARG(npix <= ((size_t)1 << 31) * 256 / (size_t)C, "stem_gc_forward_eval_rate: npix * C = %zu * %d elements exceed one grid", npix, C);
+    if (npix == 0) return 0;
+    hipLaunchKernelGGL(gc_forward_eval_rate_kernel, dim3(nblk(npix * C)), dim3(256), 0, (hipStream_t)stream, y, scales, means, ldsm, out, lik,
+                       partials, npix, C, scale_bound, lik_bound);
+    STEM_LAUNCH_CHECK("gc_forward_eval_rate");
+    return 0;
+}
+
+STEM_EXPORT int stem_em_loss_accumulate(const double *partials_y, int ny, const double *partials_z, int nz, double scale, double weight,
+                                        double *out3, double *acc4, void *stream)
+{
+    // an empty list may come with a null pointer, as in stem_em_loss_finalize: its sum is 0
+    STEM_CHECK_ARG(acc4, "stem_em_loss_accumulate: null accumulator");
+    STEM_CHECK_ARG(ny >= 0 && nz >= 0 && (partials_y || ny == 0) && (partials_z || nz == 0),
+                   "stem_em_loss_accumulate: a list of %d / %d partials needs its pointer", ny, nz);
+    hipLaunchKernelGGL(em_loss_accumulate_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials_y, ny, partials_z, nz, scale, weight,
+                       out3, acc4);
+    STEM_LAUNCH_CHECK("em_loss_accumulate");
     return 0;
 }

@@ -747,6 +747,57 @@ class StemEngine:
         return y_hat, lik_y, lik_z, k
 
     # -------------------------------------------------------------------------------------------
+    def eval_rate(self, y_cur, y_cond, num_pixels, acc=None, weight=1.0):
+        """The eval-mode forward with its EMLoss value, on the fused validation glue (include/stem_validation.h): the step of a
+        validation pass (stem/trainSTEM.py:280-287).  -> (y_hat, lik_y, lik_z, loss3): the three tensors are forward(y_cur, y_cond,
+        False)'s, bit for bit; loss3 = fp64 (y_bpp, z_bpp, loss) with the -1 / num_pixels normalisation of utils.py:18-27.
+        acc: an fp64 [4] device tensor that receives acc[0..2] += weight * loss3, acc[3] += weight (one is made and dropped when None).
+        No noise is drawn and no noise offset moves; nothing syncs with the host."""
+        self.ensure_packed()
+        self._checked = True
+        try:
+            return self._eval_rate(y_cur, y_cond, num_pixels, acc, weight)
+        finally:
+            self._checked = False
+
+    def _eval_rate(self, y_cur, y_cond, num_pixels, acc, weight):
+        # the schedule of _forward(training=False) with its elementwise work regrouped: prologue (he_in, target, round(target), y_hat),
+        # bottleneck + rate, Gaussian + rate, loss + running sum.  No scale records: every split measures its own input, as there
+        m = self.m
+        yc, yd = F.to_nhwc(y_cur.detach()), F.to_nhwc(y_cond.detach())
+        B, Cin, H, W = yc.shape
+        dev = yc.device
+        eb, gc = m.entropy_bottleneck, m.gaussian_conditional
+        ep = self.has_spm                     # _forward's `training or self.has_spm`: without a spatial prior, codec._chain's arithmetic
+        he_in, target, t_hat, y_hat = F.prior_prologue(yc, yd, self.residual, False, self.has_spm, records=None)
+        P = 2 * Cin
+        epm_in = F.empty_nhwc(B, self.nprior * P, H, W, dev)
+        o_tp, o_hp = (0, P) if self.has_tpm else (None, 0)
+        o_ctx = o_hp + P
+        bs = self._branch(dev)
+        main = F.cur_stream(dev) if bs is not None else None
+        if bs is not None:
+            F.stream_wait(bs, main)
+        if self.has_tpm:
+            self._chain_forward(self.TPM, _Act(yd), out=epm_in[:, o_tp:o_tp + P], planes=ep)
+        with F.on_stream(bs):
+            z = self._chain_forward(self.HE, _Act(he_in), planes=ep)[-1].x
+            z_hat, lik_z, part_z = F.eb_forward_eval_rate(z, F.eb_pack(eb._tensors14()), eb._medians_vec())     # _forward's eval call
+            self._chain_forward(self.HD, _Act(z_hat), out=epm_in[:, o_hp:o_hp + P], planes=ep)
+        if self.has_spm:
+            self.CTX.forward(_Act(t_hat), out=epm_in[:, o_ctx:o_ctx + P])
+        if bs is not None:
+            F.stream_wait(main, bs)
+            for t in (lik_z, part_z):
+                t.record_stream(main)         # allocated on the branch stream, read (and freed) on this one
+        gp = self._chain_forward(self.EPM, _Act(epm_in), planes=ep)[-1].x
+        gc_out, lik_y, part_y = F.gc_forward_eval_rate(target, gp[:, :Cin], gp[:, Cin:], scale_bound=gc._scale_bound, lik_bound=gc._lik_bound)
+        if acc is None:
+            acc = torch.zeros(4, dtype=torch.float64, device=dev)
+        loss3 = F.em_loss_accumulate(part_y, part_z, -1.0 / num_pixels, acc, weight=weight)
+        return (y_hat if self.has_spm else gc_out), lik_y, lik_z, loss3
+
+    # -------------------------------------------------------------------------------------------
     def backward(self, k, dlik_y, dlik_z):
         """Parameter gradients of a scalar that depends on (lik_y, lik_z), ADDED into .grad as autograd does (the
         training loop zeroes them before every backward, stem/trainSTEM.py:203; a slot that does not exist yet starts

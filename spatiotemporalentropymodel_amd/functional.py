@@ -1847,6 +1847,52 @@ def em_loss_finalize(part_y, part_z, scale, out3=None):
     return out3
 
 
+# ----------------------------------------------------------------------------- fused validation glue (include/stem_validation.h)
+def eb_forward_eval_rate(z, pack, medians, bound=1e-9):
+    """-> (z_hat, lik, partials): eval-mode EntropyBottleneck forward (round around the medians; eb_forward(medians=)'s bits) + the
+    log2 partial sums of its likelihoods.  z: any NHWC view (a channel slice of a wider buffer is fine)."""
+    _require_cuda(z, pack, medians)
+    B, Cc, H, W = z.shape
+    ldz = nhwc_ld(z)
+    assert ldz is not None, "eb_forward_eval_rate: z must be NHWC memory"
+    assert pack.shape == (Cc, EB_NPARAM) and pack.is_contiguous() and medians.numel() == Cc and medians.is_contiguous()
+    z_hat, lik = empty_nhwc(B, Cc, H, W, z.device), empty_nhwc(B, Cc, H, W, z.device)
+    part = torch.empty(rate_partials(z.numel()), dtype=torch.float64, device=z.device)
+    _chk(_lib.hip().stem_eb_forward_eval_rate(z.data_ptr(), ldz, pack.data_ptr(), medians.data_ptr(), z_hat.data_ptr(), lik.data_ptr(),
+                                              part.data_ptr(), B * H * W, Cc, bound, _stream()))
+    return z_hat, lik, part
+
+
+def gc_forward_eval_rate(y, scales, means, scale_bound=0.11, lik_bound=1e-9):
+    """-> (out, lik, partials): eval-mode GaussianConditional forward (round around the means; gc_forward(noise=None)'s bits) + the
+    log2 partial sums of its likelihoods.  y dense NHWC; scales / means channel slices with a common pitch."""
+    _require_cuda(y, scales, means)
+    B, Cc, H, W = y.shape
+    assert nhwc_ld(y) == Cc and scales.shape == y.shape and means.shape == y.shape
+    ldsm = nhwc_ld(scales)
+    assert ldsm is not None and ldsm == nhwc_ld(means)
+    out, lik = empty_nhwc(B, Cc, H, W, y.device), empty_nhwc(B, Cc, H, W, y.device)
+    part = torch.empty(rate_partials(y.numel()), dtype=torch.float64, device=y.device)
+    _chk(_lib.hip().stem_gc_forward_eval_rate(y.data_ptr(), scales.data_ptr(), means.data_ptr(), ldsm, out.data_ptr(), lik.data_ptr(),
+                                              part.data_ptr(), B * H * W, Cc, scale_bound, lik_bound, _stream()))
+    return out, lik, part
+
+
+def em_loss_accumulate(part_y, part_z, scale, acc4, weight=1.0, out3=None):
+    """em_loss_finalize's (y_bpp, z_bpp, loss) -> out3 (fp64 [3], allocated when None), and acc4[0..2] += weight * them,
+    acc4[3] += weight: the running sums of a validation pass, which stay on the device (fp64 [4], zeroed by the caller)"""
+    assert acc4.is_cuda and acc4.dtype == torch.float64 and acc4.numel() == 4 and acc4.is_contiguous()
+    for p in (part_y, part_z):
+        assert p.dtype == torch.float64 and p.is_contiguous() and (p.is_cuda or p.numel() == 0)
+    if out3 is None:
+        out3 = torch.empty(3, dtype=torch.float64, device=acc4.device)
+    assert out3.is_cuda and out3.dtype == torch.float64 and out3.numel() == 3 and out3.is_contiguous()
+    _chk(_lib.hip().stem_em_loss_accumulate(part_y.data_ptr() if part_y.numel() else 0, part_y.numel(),
+                                            part_z.data_ptr() if part_z.numel() else 0, part_z.numel(), float(scale), float(weight),
+                                            out3.data_ptr(), acc4.data_ptr(), _stream()))
+    return out3
+
+
 def eb_aux_loss_grad(quantiles, pack, target, dq_out, loss_out=None, accumulate=False):
     """EntropyBottleneck.loss and d loss / d quantiles in one single-workgroup kernel; dq_out is written (or added to)"""
     if loss_out is None:

@@ -492,5 +492,14 @@ class TapedPFrameStep:
         self._weights_key = f.eng._weights_key()
         return result
 
+    def packs_are_current(self):
+        """For a caller that runs the engine's forward BETWEEN two replays (a validation pass, stem/trainSTEM.py:228-231): a replayed
+        step has packed the weights at its end, as the recorded one did, but the engine's own key still names the weights of the
+        recording -- its next ensure_packed() would pack them again, from measured maxima instead of the optimiser pass's, into the
+        buffers the next replay's forward reads.  Tells the engine that the copies belong to the weights as the last replay left
+        them; a write since then (a checkpoint load) still shows in the key and is packed."""
+        if self.tape is not None and self.replays > 1:
+            self.fused.eng._pack_key = self._weights_key
+
     def finish(self):
         self.fused.finish()

@@ -14,6 +14,11 @@ Only `EMLoss` (rate-only, the trainSTEM criterion) has this closed form; other c
 
 `image_step` is the image-side counterpart: one batch of compressai_examples/train.py's loop for an I-frame model of the zoo, on the
 layer-wise autograd Functions (every launch a HIP kernel; no schedule of its own).
+
+What steers those loops is here too: `validate` (the validation pass of stem/trainSTEM.py:265-295, on engine.eval_rate's fused eval
+glue or module by module), `fit` (the epoch loop of :172-262 around a SeptupletTrainer: validation every N P-frame steps from its
+`on_step` hook, scheduler step, best-loss and periodic checkpoints, `resume_state`), `validate_pixel` (stem_roi/train_stem_roi.py
+:348-391 and :658-716) and `validate_image` (compressai_examples/train.py:179-207).
 """
 from __future__ import annotations
 
@@ -341,6 +346,25 @@ class SeptupletTrainer:
         if self.step_fn is not None:
             self.step_fn.finish()
 
+    def validate(self, loader, **kw):
+        """`validate` (below; stem/trainSTEM.py:265-295) on this trainer's models, between two P-frame steps -- also in the middle of a
+        septuplet, from `on_step`, where the reference calls it (:228-231).  The step's auxiliary stream is joined first (the eval
+        forward reads the quantiles the auxiliary optimiser writes); the pass has a prefetcher of its own, kept for the next pass;
+        nothing the next step reads -- parameters, optimiser states, noise offsets, the training prefetcher's latents, a recorded
+        tape's buffers -- is written.  A `criterion` given to the trainer serves the generic route."""
+        self.finish()
+        if hasattr(self.step_fn, "packs_are_current"):
+            self.step_fn.packs_are_current()
+        if kw.get("prefetch", True) is True and self.prefetch is not None:
+            if getattr(self, "_val_prefetch", None) is None:
+                self._val_prefetch = LatentPrefetcher(self.imodel, ahead=self.prefetch.ahead)
+            kw["prefetch"] = self._val_prefetch
+        elif kw.get("prefetch", True) is True:
+            kw["prefetch"] = False
+        if self.criterion is not None:
+            kw.setdefault("criterion", self.criterion)
+        return validate(self.imodel, self.stem, loader, **kw)
+
 
 def image_step(model, criterion, optimizer, aux_optimizer, x, clip_max_norm=1.0):
     """One batch of compressai_examples/train.py:127-143 for an I-frame model of the zoo:
@@ -374,3 +398,250 @@ def image_step(model, criterion, optimizer, aux_optimizer, x, clip_max_norm=1.0)
     aux_loss.backward()
     aux_optimizer.step()
     return out_criterion, aux_loss, grad_norm
+
+
+# ----------------------------------------------------------------------------- validation passes
+@contextlib.contextmanager
+def _eval_modes(*models):
+    """the models in eval() inside, the `training` flag of every module as found on entry afterwards (also when the body raises).
+    The reference's validation functions end with .train() on both models whatever they were (stem/trainSTEM.py:292-293); a frozen
+    I-frame model (:128) stays frozen here."""
+    modes = [(mod, mod.training) for m in models for mod in m.modules()]
+    try:
+        for m in models:
+            m.eval()
+        yield
+    finally:
+        for mod, flag in modes:
+            mod.training = flag
+
+
+@contextlib.contextmanager
+def _noise_offsets_kept(*models):
+    """A validation pass leaves the counter-based noise streams where it found them: mbt2018's getY draws noise in eval mode too
+    (priors.py:691), which would otherwise shift every later training draw by the size of the test set.  The pass's own draws are
+    a function of the offsets at entry: deterministic, the same on every rank."""
+    kept = [(mod, mod._noise_offset) for m in models for mod in m.modules() if hasattr(mod, "_noise_offset")]
+    try:
+        yield
+    finally:
+        for mod, off in kept:
+            mod._noise_offset = off
+
+
+def _stem_route(stem, route):
+    if route not in (None, "fused", "generic"):
+        raise ValueError(f"validate: unknown route {route!r}")
+    if route == "generic":
+        return None
+    if route is None and DEFAULT_VALIDATION_ROUTE != "fused":
+        return None
+    if route is None and tuple(stem.entropy_bottleneck.filters) != (3, 3, 3, 3):
+        return None                                  # no engine for this bottleneck: the module route
+    return stem.engine()                             # route="fused" on such a model: the engine's ValueError
+
+
+#: what validate(route=None) means for a model that has an engine: "fused" only while tools/validation_bench.py finds the fused pass
+#: at batch 1 not slower than the generic one beyond the run-to-run band (profiles/validation.json; the table and the reading of it
+#: are in DESIGN.md section 7), "generic" otherwise
+DEFAULT_VALIDATION_ROUTE = "fused"
+
+
+def validate(imodel, stem, loader, *, criterion=None, route=None, prefetch=True, lr_scheduler=None, max_items=None):
+    """The validation pass of stem/trainSTEM.py:265-295: both models in eval mode, under no_grad, over every item of `loader` (a
+    list of frame batches [B,3,H,W], any length >= 2):
+
+        _, y_cond = getY(frame 0);   for every later frame:  y_cur, _ = getY(frame) -> P step -> y_cond = y_hat
+
+    -> {"loss", "y_bpp_loss", "z_bpp_loss", "count"} (Python floats): the means of EMLoss over the P steps, each step weighted with
+    its batch size B -- the per-sample mean, i.e. what the reference's batch-1 test loader (:148) computes, whatever the loader's
+    batch size and however ragged its last batch; count = samples x P frames.
+
+    route "fused": engine.eval_rate (the elementwise work of a step in 4 kernels, the sums in a device accumulator); "generic": the
+    module call plus `criterion` (default losses.EMLoss()), the sums fp64 device tensors; None: DEFAULT_VALIDATION_ROUTE where the
+    model has an engine, else generic.  Either way the host reads the device ONCE, at the end.
+    prefetch: the latents through a LatentPrefetcher of this pass's own (a training loop's prefetcher keeps the next sequence's
+    opening latents it has already computed); a LatentPrefetcher instance is used as it is (a caller that validates repeatedly).  max_items: stop after that many loader items.
+    lr_scheduler: lr_scheduler.step(loss) at the end (:290).  Noise offsets and module modes are restored on exit.
+    Data parallel: every rank validates the whole set; the pass is deterministic, so the ranks' schedulers agree."""
+    eng = _stem_route(stem, route)
+    if eng is None and criterion is None:
+        from .losses import EMLoss
+        criterion = EMLoss()
+    pf = prefetch if isinstance(prefetch, LatentPrefetcher) else (LatentPrefetcher(imodel) if prefetch else None)
+    acc = None
+    with torch.no_grad(), _eval_modes(imodel, stem), _noise_offsets_kept(imodel, stem):
+        for n, images in enumerate(loader):
+            if max_items is not None and n >= max_items:
+                break
+            frames = list(images)
+            if len(frames) < 2:
+                raise ValueError(f"validate: loader item {n} has {len(frames)} frame(s); a P step needs two")
+            B, _, H, W = frames[0].shape
+            if acc is None:
+                acc = torch.zeros(4, dtype=torch.float64, device=frames[0].device)
+            if pf is not None:
+                pf.start(frames, frames_ready=True)
+                y_cond = pf.get(0)[1]
+            else:
+                y_cond = imodel.getY(frames[0])[1]
+            for t in range(1, len(frames)):
+                y_cur = pf.get(t)[0] if pf is not None else imodel.getY(frames[t])[0]
+                if eng is not None:
+                    y_cond = eng.eval_rate(y_cur, y_cond, B * H * W, acc=acc, weight=float(B))[0]
+                else:
+                    out = stem(y_cur, y_cond)
+                    oc = criterion(out, frames[t])
+                    y_cond = out["y_hat"]
+                    acc += float(B) * torch.stack([oc["y_bpp_loss"].double().reshape(()), oc["z_bpp_loss"].double().reshape(()),
+                                                   oc["loss"].double().reshape(()), torch.ones((), dtype=torch.float64, device=acc.device)])
+    if acc is None:
+        raise ValueError("validate: the loader is empty")
+    a = acc.cpu().tolist()                               # the pass's one device-to-host copy
+    res = {"y_bpp_loss": a[0] / a[3], "z_bpp_loss": a[1] / a[3], "loss": a[2] / a[3], "count": a[3]}
+    if lr_scheduler is not None:
+        lr_scheduler.step(res["loss"])
+    return res
+
+
+def _nchw_x_hat(out_net):
+    """the model's output with x_hat as a plain NCHW batch (an image model of the zoo returns NHWC memory): the criterion and the next
+    frame's analysis transform read NCHW -- the layout kernel, as in image_step"""
+    from .layers import to_nchw
+    if F.nhwc_ld(out_net["x_hat"]) is not None and not out_net["x_hat"].is_contiguous():
+        return dict(out_net, x_hat=to_nchw(out_net["x_hat"]))
+    return out_net
+
+
+def _mean_dict(sums, cnt):
+    vals = torch.stack([v.double().reshape(()) for v in sums.values()]).cpu().tolist()       # one copy per loader
+    return {k: v / cnt for k, v in zip(sums, vals)}
+
+
+def validate_pixel(model_i, model_p, loaders, criterion, *, criterion_rd=None):
+    """The validation passes of the pixel-domain models (stem_roi/train_stem_roi.py):
+
+    loaders = ONE loader of frame lists: _validation_stem_baseline (:348-391) -- frame 0 through model_i(x), later frames through
+    model_p(x, x_conditioned), criterion(out, x) for both, x_conditioned = out["x_hat"]; -> {"loss", "mse_loss", "bpp_loss"}, the
+    means over ALL frames (the I frame counts).
+    loaders = a list / tuple of loaders of (frames, Qmap), one per quality level: _validation_stem_roi (:658-716) -- the quality map
+    goes to both models, criterion(out, x, quality2lambda(Qmap)), and criterion_rd (default losses.RateDistortionLoss()) supplies
+    the unweighted "mse"; -> one dictionary per loader, in order.
+
+    Existing forwards and criteria only.  The sums stay device tensors until a loader is finished; modes are restored as in
+    `validate`, and so are the noise offsets."""
+    # a list of loaders, unless it is ONE loader given as a list of items (an item is a list of frame tensors)
+    first = loaders[0] if isinstance(loaders, (list, tuple)) and len(loaders) else None
+    roi = isinstance(loaders, (list, tuple)) and not (isinstance(first, (list, tuple)) and len(first) and torch.is_tensor(first[0]))
+    if roi and criterion_rd is None:
+        from .losses import RateDistortionLoss
+        criterion_rd = RateDistortionLoss()
+    from .losses import quality2lambda
+    results = []
+    with torch.no_grad(), _eval_modes(model_i, model_p), _noise_offsets_kept(model_i, model_p):
+        for loader in (loaders if roi else [loaders]):
+            sums, cnt = {}, 0
+            for item in loader:
+                images, qmap = item if roi else (item, None)
+                lmbdamap = quality2lambda(qmap) if roi else None
+                x_cond = None
+                for idx, x in enumerate(images):
+                    if roi:
+                        out = _nchw_x_hat(model_i(x, qmap) if idx == 0 else model_p(x, x_cond, qmap))
+                        oc = criterion(out, x, lmbdamap)
+                        vals = {"loss": oc["loss"], "mse_loss": oc["mse_loss"], "bpp_loss": oc["bpp_loss"], "mse": criterion_rd(out, x)["mse_loss"]}
+                    else:
+                        out = _nchw_x_hat(model_i(x) if idx == 0 else model_p(x, x_cond))
+                        oc = criterion(out, x)
+                        vals = {"loss": oc["loss"], "mse_loss": oc["mse_loss"], "bpp_loss": oc["bpp_loss"]}
+                    x_cond = out["x_hat"]
+                    for k, v in vals.items():
+                        sums[k] = v.detach().double() if k not in sums else sums[k] + v.detach().double()
+                    cnt += 1
+            if not cnt:
+                raise ValueError("validate_pixel: an empty loader")
+            results.append(_mean_dict(sums, cnt))
+    return results if roi else results[0]
+
+
+def validate_image(model, loader, criterion):
+    """test_epoch of compressai_examples/train.py:179-207 for an I-frame model of the zoo: the means over the loader's batches of
+    criterion(model(x), x)'s "loss", "bpp_loss", "mse_loss" and of model.aux_loss() ("aux_loss").  Sums on the device, one copy."""
+    sums, cnt = {}, 0
+    with torch.no_grad(), _eval_modes(model), _noise_offsets_kept(model):
+        for x in loader:
+            oc = criterion(_nchw_x_hat(model(x)), x)
+            vals = {"loss": oc["loss"], "bpp_loss": oc["bpp_loss"], "mse_loss": oc["mse_loss"], "aux_loss": model.aux_loss()}
+            for k, v in vals.items():
+                sums[k] = v.detach().double() if k not in sums else sums[k] + v.detach().double()
+            cnt += 1
+    if not cnt:
+        raise ValueError("validate_image: an empty loader")
+    return _mean_dict(sums, cnt)
+
+
+# ----------------------------------------------------------------------------- the epoch loop
+def fit(trainer, train_loader, test_loader, lr_scheduler, epochs, *, start_epoch=0, start_iterations=0, validate_every=20000, save=None,
+        save_every_epochs=2, on_validation=None):
+    """The epoch loop of stem/trainSTEM.py:172-262 around a SeptupletTrainer (or anything with train_septuplet(images), validate(loader,
+    lr_scheduler=), on_step and finish()):
+
+        for epoch in start_epoch .. epochs - 1:
+            for images in train_loader:  trainer.train_septuplet(images)
+                after EVERY P-frame step: iterations += 1; if iterations % validate_every == 0 (:226-228): the validation pass over
+                test_loader with lr_scheduler.step(loss) (:231, :290) -- inside the septuplet, so a lowered learning rate applies to
+                the very next step -- and, when the loss is the best so far, the checkpoint `save + f"checkpoint_best_epoch{epoch}.pth.tar"`
+            if epoch % save_every_epochs == 0:  the checkpoint `save + f"checkpoint_epoch{epoch}.pth.tar"` (:250-262)
+
+    Checkpoints go through utils.save_checkpoint with the reference's keys {"epoch", "iterations", "state_dict", "optimizer",
+    "aux_optimizer", "lr_scheduler"} (the trainer's .stem / .opt / .aux_opt); save=None writes none.  start_epoch / start_iterations:
+    `resume_state` of a loaded checkpoint.  on_validation(epoch, iterations, result, is_best) is called after every pass.
+    -> {"iterations", "best_loss", "validations": [(epoch, iterations, loss)]}."""
+    from .utils import save_checkpoint
+    state = {"iterations": int(start_iterations), "best": float("inf"), "epoch": int(start_epoch), "log": []}
+
+    def checkpoint(name):
+        if save is None:
+            return
+        trainer.finish()
+        save_checkpoint({"epoch": state["epoch"], "iterations": state["iterations"], "state_dict": trainer.stem.state_dict(),
+                         "optimizer": trainer.opt.state_dict(), "aux_optimizer": trainer.aux_opt.state_dict(),
+                         "lr_scheduler": lr_scheduler.state_dict()}, filename=save + name)
+
+    def after_step(*step):
+        if user_hook is not None:
+            user_hook(*step)
+        state["iterations"] += 1
+        if validate_every and state["iterations"] % validate_every == 0:
+            res = trainer.validate(test_loader, lr_scheduler=lr_scheduler)
+            best = res["loss"] < state["best"]
+            state["log"].append((state["epoch"], state["iterations"], res["loss"]))
+            if best:
+                state["best"] = res["loss"]
+                checkpoint(f"checkpoint_best_epoch{state['epoch']}.pth.tar")
+            if on_validation is not None:
+                on_validation(state["epoch"], state["iterations"], res, best)
+
+    user_hook = trainer.on_step
+    trainer.on_step = after_step
+    try:
+        for epoch in range(int(start_epoch), int(epochs)):
+            state["epoch"] = epoch
+            for images in train_loader:
+                trainer.train_septuplet(images)
+            if save_every_epochs and epoch % save_every_epochs == 0:
+                checkpoint(f"checkpoint_epoch{epoch}.pth.tar")
+    finally:
+        trainer.on_step = user_hook
+    trainer.finish()
+    return {"iterations": state["iterations"], "best_loss": state["best"], "validations": state["log"]}
+
+
+def resume_state(checkpoint, stem, optimizer, aux_optimizer, lr_scheduler):
+    """stem/trainSTEM.py:138-143: the three load_state_dict calls (plus the model's) of a checkpoint `fit` or the reference wrote
+    -> (start_epoch, start_iterations) = (checkpoint["epoch"] + 1, checkpoint["iterations"]) for fit()."""
+    stem.load_state_dict(checkpoint["state_dict"])
+    optimizer.load_state_dict(checkpoint["optimizer"])
+    aux_optimizer.load_state_dict(checkpoint["aux_optimizer"])
+    lr_scheduler.load_state_dict(checkpoint["lr_scheduler"])
+    return checkpoint["epoch"] + 1, checkpoint["iterations"]
