@@ -1,6 +1,6 @@
-"""ctypes loader for the three C-ABI libraries (include/stem_hip.h + include/stem_ar_batch.h + include/stem_blocks.h +
-include/stem_hyperprior.h + include/stem_eb_filters.h + include/stem_gdn1.h + include/stem_validation.h, include/stem_rans.h,
-include/stem_dp.h).
+"""ctypes loader for the C-ABI libraries (include/stem_hip.h + include/stem_ar_batch.h + include/stem_blocks.h +
+include/stem_hyperprior.h + include/stem_eb_filters.h + include/stem_gdn1.h + include/stem_validation.h, include/stem_frameio.h,
+include/stem_rans.h, include/stem_dp.h).
 
 The headers are the single statement of the ABI: every prototype and descriptor structure below is read from them (_abi.py).
 
@@ -21,10 +21,13 @@ HIP_SO = os.environ.get("STEM_HIP_LIBRARY") or os.path.join(_PKG, "libstem_hip.s
 # STEM_RANS_LIBRARY names another build of the host codec (`make sanitize` -> libstem_rans_asan.so, the sanitizer test)
 RANS_SO = os.environ.get("STEM_RANS_LIBRARY") or os.path.join(_PKG, "libstem_rans.so")
 
+# the frame ingest / emit kernels of the sequence codec (include/stem_frameio.h): a library of their own
+FRAMEIO_SO = os.path.join(_PKG, "libstem_frameio.so")
 DP_SO = os.environ.get("STEM_DP_LIBRARY") or os.path.join(_PKG, "libstem_dp.so")
 _hip = None
 _rans = None
 _dp = None
+_frameio = None
 
 
 class StemLibraryError(RuntimeError):
@@ -58,6 +61,8 @@ _HIP_EBF_PROTO, _HIP_EBF_SIG, _ = _tables("stem_eb_filters.h")
 _HIP_GDN1_PROTO, _HIP_GDN1_SIG, _ = _tables("stem_gdn1.h")
 # libstem_hip.so's eval-mode rate kernels and running loss sum of the validation pass (csrc/entropy.hip; not launch-tape entries either)
 _HIP_VALIDATION_PROTO, _HIP_VALIDATION_SIG, _ = _tables("stem_validation.h")
+# libstem_frameio.so's padded-frame ingest and window emit kernels (csrc/frameio.hip; not launch-tape entries either)
+_FRAMEIO_PROTO, _FRAMEIO_SIG, _ = _tables("stem_frameio.h")
 _RANS_PROTO, _RANS_SIG, _RANS_RESTYPE = _tables("stem_rans.h")
 _DP_PROTO, _DP_SIG, _ = _tables("stem_dp.h")
 _STRUCTS = _abi.structs(_header("stem_hip.h"))
@@ -111,6 +116,22 @@ def hip():
     return _hip
 
 
+def frameio():
+    """libstem_frameio.so (include/stem_frameio.h), or raise: like libstem_hip.so it has no fallback"""
+    global _frameio
+    if _frameio is None:
+        if not os.path.exists(FRAMEIO_SO):
+            raise StemLibraryError(f"{FRAMEIO_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                                   "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the frame kernels.")
+        _frameio = _bind(C.CDLL(FRAMEIO_SO), _FRAMEIO_PROTO)
+    return _frameio
+
+
+def check_frameio(rc: int):
+    if rc != 0:
+        raise RuntimeError((frameio().stem_frameio_last_error() or b"").decode() or f"libstem_frameio error {rc}")
+
+
 def rans():
     global _rans
     if _rans is None:
@@ -151,6 +172,10 @@ def declared_hip_gdn1_symbols():
 
 def declared_hip_validation_symbols():
     return sorted(_HIP_VALIDATION_SIG)
+
+
+def declared_frameio_symbols():
+    return sorted(_FRAMEIO_SIG)
 
 
 def header_macro(header, name):

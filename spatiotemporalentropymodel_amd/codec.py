@@ -260,45 +260,67 @@ def _decoder_on(string):
     return dec
 
 
-def _result(y_strings, z_strings, zshape, order):
-    """what compress returns; "order" only where it is not the reference's, so raster results are the dictionaries they were"""
+def _result(y_strings, z_strings, zshape, order, y_hat=None):
+    """what compress returns; "order" only where it is not the reference's and "y_hat" only where it was asked for, so default results
+    are the dictionaries they were"""
     res = {"strings": [y_strings, z_strings], "shape": zshape}
     if order != "raster":
         res["order"] = order
+    if y_hat is not None:
+        res["y_hat"] = y_hat
     return res
 
 
-def stem_compress(model, y_cur, y_cond, order="raster"):
+def _decoded(model, rec, yd):
+    """the encoder's reconstruction `rec` of the coded target as the latent `stem_decompress` returns: plus y_cond for the residual classes"""
+    return F.add(rec, _dense(yd)) if model.RESIDUAL else rec
+
+
+def stem_compress(model, y_cur, y_cond, order="raster", return_y_hat=False):
+    """return_y_hat=True: the result gains "y_hat", the latent `stem_decompress` of these strings returns, taken from the encoder's own
+    state (the coder's buffer, or the symbols still on the device for the one-shot models): no decoder runs"""
     _check_order(order, model)
     z_strings, zshape, hp, tp = _hyper(model, y_cur, y_cond)
     yc, yd = F.to_nhwc(y_cur.detach()), F.to_nhwc(y_cond.detach())
     target = F.sub(_dense(yc), _dense(yd)) if model.RESIDUAL else _dense(yc)
+    rec = None
     if not model.HAS_SPM:
         scales, means = _one_shot(model, hp, tp)
-        y_strings = model.gaussian_conditional.compress(target, None, means=means, scales=scales)
+        y_strings = model.gaussian_conditional.compress(target, None, means=means, scales=scales, return_y_hat=return_y_hat)
+        if return_y_hat:
+            y_strings, rec = y_strings
+    elif return_y_hat:
+        y_strings, rec = _encode_latents(model, target, hp, tp, order, want_y_hat=True)
     else:
         y_strings = _encode_latents(model, target, hp, tp, order)
-    return _result(y_strings, z_strings, zshape, order)
+    return _result(y_strings, z_strings, zshape, order, _decoded(model, rec, yd) if return_y_hat else None)
 
 
-def _encode_latents(model, target, hp, tp, order="raster"):
+def _encode_latents(model, target, hp, tp, order="raster", want_y_hat=False):
     """the raster-order coding of `target` (dense NHWC [B, M, H, W]) given the hyper prior `hp` and the temporal prior `tp` (or
     None): spatiotemporalpriors.py:916-961 / priors.py:586-631 -> one string per image.  order="wavefront": the same symbols and
-    indexes, handed to the host coder in the order of `wave_order`."""
+    indexes, handed to the host coder in the order of `wave_order`.  want_y_hat: -> (strings, the reconstruction the coding kernels left
+    in their padded buffers, dense NHWC [B, M, H, W]) -- what `_decode_latents` of the strings gives, under either order."""
     _check_order(order)
     B, M, H, W = target.shape
     dev = target.device
     ar = _ARContext(model, dev)
     tables = model.gaussian_conditional.host_tables()
     si = torch.empty((2, B, H * W, M), device=dev, dtype=torch.int32)             # symbols | indexes of the batch, raster order per image
+    y_hat = F.empty_nhwc(B, M, H, W, dev) if want_y_hat else None
     if B > 1 and not _config.runtime().ar_stepwise:
         # one queue of wavefront steps for the whole batch
         buf = torch.zeros((B, H + 2 * _P, W + 2 * _P, M), device=dev, dtype=torch.float32)
         buf[:, _P:_P + H, _P:_P + W].permute(0, 3, 1, 2).copy_(target)
         ar.encode_batch(buf, B, H, W, *_prior_addrs(tp, hp, 0, H, W, M), si[0], si[1])
+        if want_y_hat:
+            y_hat.copy_(buf[:, _P:_P + H, _P:_P + W].permute(0, 3, 1, 2))
     else:
         for b in range(B):
-            ar.encode_wavefront(_padded(target[b:b + 1], H, W, M, dev), H, W, *_prior_addrs(tp, hp, b, H, W, M), si[0, b], si[1, b])
+            buf = _padded(target[b:b + 1], H, W, M, dev)
+            ar.encode_wavefront(buf, H, W, *_prior_addrs(tp, hp, b, H, W, M), si[0, b], si[1, b])
+            if want_y_hat:
+                _unpad_into(y_hat, b, buf, H, W)
     if order == "wavefront":
         # one launch gathers symbols and indexes into step order
         sw = torch.empty_like(si)
@@ -311,7 +333,8 @@ def _encode_latents(model, target, hp, tp, order="raster"):
         enc.encode_with_indexes(sym[b], idx[b], tables)                        # one host call per image (:955-959); ctypes releases the GIL
         return enc.flush()
 
-    return list(_POOL.map(code, range(B))) if B > 1 else [code(0)]
+    strings = list(_POOL.map(code, range(B))) if B > 1 else [code(0)]
+    return (strings, y_hat) if want_y_hat else strings
 
 
 def stem_decompress(model, strings, shape, y_cond, order="raster"):
@@ -333,24 +356,27 @@ def _same_shapes(tensors, what):
         raise ValueError(f"{what}: one [1, ...] tensor per chain, all of one size, got {sorted(shapes)}")
 
 
-def stem_compress_each(model, y_curs, y_conds, order="raster"):
+def stem_compress_each(model, y_curs, y_conds, order="raster", return_y_hat=False):
     """`stem_compress` of several independent chains (the GOPs evaluation.eval_sequence codes side by side), one [1, M, H, W] pair per
     chain.  The transforms of every chain run at batch 1 -- at another batch size the hyper-prior convolutions may pick another tile /
     split-K plan and move a mean by an ulp, and a stream coded so need not decode at batch 1, which is how a stand-alone decoder runs --
     and only the raster-order coding is batched (`_encode_latents`: its per-image arithmetic is fixed).  -> one result per chain, with
-    the keys and the bits `stem_compress` gives for that chain alone."""
+    the keys and the bits `stem_compress` gives for that chain alone (return_y_hat: as there)."""
     _check_order(order, model)
     _same_shapes(list(y_curs) + list(y_conds), "stem_compress_each")
     if not model.HAS_SPM:
-        return [stem_compress(model, yc, yd) for yc, yd in zip(y_curs, y_conds)]
-    zs, hps, tps, targets = [], [], [], []
+        return [stem_compress(model, yc, yd, return_y_hat=return_y_hat) for yc, yd in zip(y_curs, y_conds)]
+    zs, hps, tps, targets, yds = [], [], [], [], []
     for y_cur, y_cond in zip(y_curs, y_conds):
         z_strings, zshape, hp, tp = _hyper(model, y_cur, y_cond)
         yc, yd = F.to_nhwc(y_cur.detach()), F.to_nhwc(y_cond.detach())
         targets.append(F.sub(_dense(yc), _dense(yd)) if model.RESIDUAL else _dense(yc))
-        zs.append((z_strings, zshape)), hps.append(hp), tps.append(tp)
-    y_strings = _encode_latents(model, _cat_nhwc(targets), _cat_nhwc(hps), _cat_nhwc(tps) if tps[0] is not None else None, order)
-    return [_result([y], z, zshape, order) for y, (z, zshape) in zip(y_strings, zs)]
+        zs.append((z_strings, zshape)), hps.append(hp), tps.append(tp), yds.append(yd)
+    args = (model, _cat_nhwc(targets), _cat_nhwc(hps), _cat_nhwc(tps) if tps[0] is not None else None, order)
+    if not return_y_hat:
+        return [_result([y], z, zshape, order) for y, (z, zshape) in zip(_encode_latents(*args), zs)]
+    y_strings, rec = _encode_latents(*args, want_y_hat=True)
+    return [_result([y], z, zshape, order, _decoded(model, _slice_nhwc(rec, i), yds[i])) for i, (y, (z, zshape)) in enumerate(zip(y_strings, zs))]
 
 
 def stem_decompress_each(model, strings, shapes, y_conds, order="raster"):
@@ -593,7 +619,7 @@ class _Decode:
 
 
 # ---- the I-frame codec: JointAutoregressiveHierarchicalPriors ("mbt2018") --------------------------------------------------------
-def iframe_compress(model, x, order="raster"):
+def iframe_compress(model, x, order="raster", return_y_hat=False):
     """compressai/models/priors.py:544-584: y = g_a(x), z = h_a(y) through the bottleneck's coder, params = h_s(z_hat), then the
     raster-order coding of y itself given params -- the same loop as a STEM model without temporal prior and without residual"""
     _check_order(order, model)
@@ -605,7 +631,10 @@ def iframe_compress(model, x, order="raster"):
     params = _dense(F.to_nhwc(model.h_s(z_hat)))
     yn = _dense(F.to_nhwc(y.detach()))
     _check_latent_size(yn, params, "images")
-    return _result(_encode_latents(model, yn, params, None, order), z_strings, z.shape[-2:], order)
+    if not return_y_hat:
+        return _result(_encode_latents(model, yn, params, None, order), z_strings, z.shape[-2:], order)
+    y_strings, y_hat = _encode_latents(model, yn, params, None, order, want_y_hat=True)       # "y_hat": what iframe_decompress returns as "y_hat"
+    return _result(y_strings, z_strings, z.shape[-2:], order, y_hat)
 
 
 def iframe_decompress(model, strings, shape, order="raster"):
@@ -620,7 +649,7 @@ def iframe_decompress(model, strings, shape, order="raster"):
     return {"x_hat": x_hat, "y_hat": y_hat}
 
 
-def iframe_compress_each(model, xs, order="raster"):
+def iframe_compress_each(model, xs, order="raster", return_y_hat=False):
     """`iframe_compress` of several independent images, one [1, 3, h, w] tensor each: g_a, h_a, h_s per image at batch 1 (see
     `stem_compress_each`), one batched raster-order coding.  -> one result per image, the bits of `iframe_compress` of it alone."""
     _check_order(order, model)
@@ -636,8 +665,11 @@ def iframe_compress_each(model, xs, order="raster"):
         yn = _dense(F.to_nhwc(y.detach()))
         _check_latent_size(yn, p, "images")
         zs.append((z_strings, z.shape[-2:])), ys.append(yn), params.append(p)
-    y_strings = _encode_latents(model, _cat_nhwc(ys), _cat_nhwc(params), None, order)
-    return [_result([y], z, zshape, order) for y, (z, zshape) in zip(y_strings, zs)]
+    if not return_y_hat:
+        y_strings = _encode_latents(model, _cat_nhwc(ys), _cat_nhwc(params), None, order)
+        return [_result([y], z, zshape, order) for y, (z, zshape) in zip(y_strings, zs)]
+    y_strings, y_hats = _encode_latents(model, _cat_nhwc(ys), _cat_nhwc(params), None, order, want_y_hat=True)
+    return [_result([y], z, zshape, order, _slice_nhwc(y_hats, i)) for i, (y, (z, zshape)) in enumerate(zip(y_strings, zs))]
 
 
 def iframe_decompress_each(model, strings, shapes, order="raster"):

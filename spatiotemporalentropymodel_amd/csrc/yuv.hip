@@ -22,62 +22,17 @@
 //     With source planes, each work item also takes the squared differences of its twelve integer samples; a workgroup reduces
 //     them in 64-bit integers to its own three slots of the workspace, a second launch (one workgroup per image) sums the slots.
 //     Integer sums: exact, so order-free and bit-reproducible; no atomics.
+//
+// The arithmetic of a work item is stated in yuv_elem.h, which csrc/frameio.hip shares (the same frames inside padded ones).
 #include "stem_common.h"
+#include "yuv_elem.h"
 
 namespace {
 
-constexpr int YUV_THREADS = 256;
-constexpr double KR = 0.2126, KG = 0.7152, KB = 0.0722;           // ITU-R BT.709 (functional.py:8-11)
+using namespace yuv_elem;
 
-template <typename T, int N>
-struct alignas(sizeof(T) * N) Pack {
-    T v[N];
-};
-
-// N consecutive samples; VEC: one aligned vector access (the caller guarantees alignment and that all N exist)
-template <bool VEC, typename T, int N>
-__device__ inline void load_n(const T *p, int valid, T (&out)[N])
-{
-    if (VEC) {
-        const Pack<T, N> q = *reinterpret_cast<const Pack<T, N> *>(p);
-#pragma unroll
-        for (int i = 0; i < N; ++i) out[i] = q.v[i];
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; ++i) out[i] = i < valid ? p[i] : T(0);
-    }
-}
-template <bool VEC, typename T, int N>
-__device__ inline void store_n(T *p, int valid, const T (&in)[N])
-{
-    if (VEC) {
-        Pack<T, N> q;
-#pragma unroll
-        for (int i = 0; i < N; ++i) q.v[i] = in[i];
-        *reinterpret_cast<Pack<T, N> *>(p) = q;
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; ++i)
-            if (i < valid) p[i] = in[i];
-    }
-}
-
-// the work item of this thread: chroma row cy, luma columns x0 .. x0 + 4 (the first `valid` of them exist)
-struct YuvItem {
-    int cy, x0, valid;
-    bool live;
-};
-__device__ inline YuvItem yuv_item(int Hc, int W)
-{
-    const int wq = (W + 3) >> 2;
-    const long long t = (long long)blockIdx.x * YUV_THREADS + threadIdx.x;
-    YuvItem it;
-    it.live = t < (long long)Hc * wq;
-    it.cy = (int)(t / wq);
-    it.x0 = (int)(t - (long long)it.cy * wq) * 4;
-    it.valid = W - it.x0 < 4 ? W - it.x0 : 4;                   // 4, or 2 in the last item of a row with W % 4 == 2
-    return it;
-}
+// the work item of this thread
+__device__ inline YuvItem yuv_item(int Hc, int W) { return yuv_item_at((long long)blockIdx.x * YUV_THREADS + threadIdx.x, Hc, W); }
 
 template <typename T, bool VEC>
 __global__ __launch_bounds__(YUV_THREADS) void yuv420_to_rgb_kernel(const T *__restrict__ yp, const T *__restrict__ up,
@@ -88,76 +43,8 @@ __global__ __launch_bounds__(YUV_THREADS) void yuv420_to_rgb_kernel(const T *__r
     const YuvItem it = yuv_item(Hc, W);
     if (!it.live) return;
     const size_t b = blockIdx.y, plane = (size_t)H * W, cplane = (size_t)Hc * Wc;
-    const int cy = it.cy, k0 = it.x0 >> 1;
-
-    // chroma of the item's 2 x 4 pixels, still in sample units: c[plane][row][column]
-    float c[2][2][4];
-    const T *cp[2] = {up + b * cplane, vp + b * cplane};
-    if (nearest) {
-        const int k1 = k0 + 1 < Wc ? k0 + 1 : Wc - 1;
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const float a = (float)cp[p][(size_t)cy * Wc + k0], d = (float)cp[p][(size_t)cy * Wc + k1];
-#pragma unroll
-            for (int r = 0; r < 2; ++r) c[p][r][0] = c[p][r][1] = a, c[p][r][2] = c[p][r][3] = d;
-        }
-    } else {
-        // rows cy - 1, cy, cy + 1 and columns k0 - 1 .. k0 + 2, clamped into the plane
-        const int rr[3] = {cy > 0 ? cy - 1 : 0, cy, cy + 1 < Hc ? cy + 1 : Hc - 1};
-        int cc[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int k = k0 - 1 + j;
-            cc[j] = k < 0 ? 0 : (k < Wc ? k : Wc - 1);
-        }
-        // torch's source index of output 0 is sample 0 with weight 1 (not 0.25 / 0.75 of the same sample twice: that sum rounds)
-        const float wl0 = k0 == 0 ? 1.f : 0.25f, wl1 = k0 == 0 ? 0.f : 0.75f;
-        const float wt0 = cy == 0 ? 1.f : 0.25f, wt1 = cy == 0 ? 0.f : 0.75f;
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            float h[3][4];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const T *row = cp[p] + (size_t)rr[r] * Wc;
-                const float s0 = (float)row[cc[0]], s1 = (float)row[cc[1]], s2 = (float)row[cc[2]], s3 = (float)row[cc[3]];
-                h[r][0] = wl0 * s0 + wl1 * s1;
-                h[r][1] = 0.75f * s1 + 0.25f * s2;
-                h[r][2] = 0.25f * s1 + 0.75f * s2;
-                h[r][3] = 0.75f * s2 + 0.25f * s3;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                c[p][0][j] = wt0 * h[0][j] + wt1 * h[1][j];
-                c[p][1][j] = 0.75f * h[1][j] + 0.25f * h[2][j];
-            }
-        }
-    }
-
-    const float c_r = (float)(2.0 - 2.0 * KR), c_b = (float)(2.0 - 2.0 * KB), kr = (float)KR, kg = (float)KG, kb = (float)KB;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const size_t off = (size_t)(2 * cy + r) * W + it.x0;
-        T ys[4];
-        load_n<VEC>(yp + b * plane + off, it.valid, ys);
-        float R[4], G[4], B[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float y = (float)ys[j] / peak, cb = c[0][r][j] / peak, cr = c[1][r][j] / peak;
-            float rv = y + c_r * (cr - 0.5f);
-            float bv = y + c_b * (cb - 0.5f);
-            float gv = (y - kr * rv - kb * bv) / kg;
-            if (clamp01) {
-                rv = fminf(fmaxf(rv, 0.f), 1.f);
-                gv = fminf(fmaxf(gv, 0.f), 1.f);
-                bv = fminf(fmaxf(bv, 0.f), 1.f);
-            }
-            R[j] = rv, G[j] = gv, B[j] = bv;
-        }
-        float *o = rgb + b * 3 * plane + off;
-        store_n<VEC>(o, it.valid, R);
-        store_n<VEC>(o + plane, it.valid, G);
-        store_n<VEC>(o + 2 * plane, it.valid, B);
-    }
+    yuv420_item_to_rgb<T, VEC, VEC>(yp + b * plane, up + b * cplane, vp + b * cplane, H, W, it, peak, nearest, clamp01, rgb + b * 3 * plane,
+                                    (size_t)W, plane);
 }
 
 // sum of three 64-bit counters over the workgroup; thread 0 gets it
@@ -202,54 +89,30 @@ __global__ __launch_bounds__(YUV_THREADS) void rgb_to_yuv420_kernel(const float 
 
     if (it.live) {
         const int nc = it.valid >> 1;                           // chroma samples of this item: 2, or 1
-        double du[2] = {0.0, 0.0}, dv[2] = {0.0, 0.0};          // sums of b - y and r - y over each 2 x 2 block
+        const size_t off = (size_t)(2 * it.cy) * W + it.x0;
+        YuvItemOut<T> o;
+        rgb_item_to_yuv420<T, VEC>(rgb + b * 3 * plane + off, (size_t)W, plane, it.valid, peak, o);
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
-            const size_t off = (size_t)(2 * it.cy + r) * W + it.x0;
-            const float *src = rgb + b * 3 * plane + off;
-            float R[4], G[4], B[4];
-            load_n<VEC>(src, it.valid, R);
-            load_n<VEC>(src + plane, it.valid, G);
-            load_n<VEC>(src + 2 * plane, it.valid, B);
-            float yo[4];
-            T yq[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const double rv = (double)R[j], gv = (double)G[j], bv = (double)B[j];
-                const double y = KR * rv + KG * gv + KB * bv;
-                du[j >> 1] += bv - y;
-                dv[j >> 1] += rv - y;
-                yo[j] = (float)y;
-                yq[j] = (T)rint(fmin(fmax(y, 0.0), 1.0) * peak);
-            }
-            if (FLT) store_n<VEC>(yf + b * plane + off, it.valid, yo);
-            if (INT) store_n<VEC>(yi + b * plane + off, it.valid, yq);
+            const size_t roff = b * plane + off + (size_t)r * W;
+            if (FLT) store_n<VEC>(yf + roff, it.valid, o.yo[r]);
+            if (INT) store_n<VEC>(yi + roff, it.valid, o.yq[r]);
             if (SSE) {
                 T s[4];
-                load_n<VEC>(ys + b * plane + off, it.valid, s);
+                load_n<VEC>(ys + roff, it.valid, s);
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    if (j < it.valid) sse[0] += sqdiff(yq[j], s[j]);
+                    if (j < it.valid) sse[0] += sqdiff(o.yq[r][j], s[j]);
             }
-        }
-        // cb = 0.5 * (b - y) / (1 - Kb) + 0.5 averaged over the block (:41-42, :90): the average commutes with the affine map
-        float uo[2], vo[2];
-        T uq[2], vq[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const double cb = (0.25 * du[k]) * (0.5 / (1.0 - KB)) + 0.5, cr = (0.25 * dv[k]) * (0.5 / (1.0 - KR)) + 0.5;
-            uo[k] = (float)cb, vo[k] = (float)cr;
-            uq[k] = (T)rint(fmin(fmax(cb, 0.0), 1.0) * peak);
-            vq[k] = (T)rint(fmin(fmax(cr, 0.0), 1.0) * peak);
         }
         const size_t coff = b * cplane + (size_t)it.cy * Wc + (it.x0 >> 1);
         if (FLT) {
-            store_n<VEC>(uf + coff, nc, uo);
-            store_n<VEC>(vf + coff, nc, vo);
+            store_n<VEC>(uf + coff, nc, o.uo);
+            store_n<VEC>(vf + coff, nc, o.vo);
         }
         if (INT) {
-            store_n<VEC>(ui + coff, nc, uq);
-            store_n<VEC>(vi + coff, nc, vq);
+            store_n<VEC>(ui + coff, nc, o.uq);
+            store_n<VEC>(vi + coff, nc, o.vq);
         }
         if (SSE) {
             T su[2], sv[2];
@@ -257,7 +120,7 @@ __global__ __launch_bounds__(YUV_THREADS) void rgb_to_yuv420_kernel(const float 
             load_n<VEC>(vs + coff, nc, sv);
 #pragma unroll
             for (int k = 0; k < 2; ++k)
-                if (k < nc) sse[1] += sqdiff(uq[k], su[k]), sse[2] += sqdiff(vq[k], sv[k]);
+                if (k < nc) sse[1] += sqdiff(o.uq[k], su[k]), sse[2] += sqdiff(o.vq[k], sv[k]);
         }
     }
     if (SSE) {
@@ -332,22 +195,6 @@ __global__ __launch_bounds__(YUV_THREADS) void plane_resample2_kernel(const floa
     }
     out[(size_t)blockIdx.y * Ho * Wo + i] = r;
 }
-
-// geometry checks shared by the entry points; no device needed.  nblk: workgroups per image.
-int yuv_plan(const char *who, int B, int H, int W, int sample_bytes, int bit_depth, int *nblk)
-{
-    STEM_CHECK_ARG(B > 0 && B <= 65535, "%s: the batch must be 1 .. 65535 images, got %d", who, B);
-    STEM_CHECK_ARG(H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "%s: 4:2:0 frames have even sides >= 2, got %d x %d", who, H, W);
-    STEM_CHECK_ARG(sample_bytes == 1 || sample_bytes == 2, "%s: samples are 1 or 2 bytes wide, got %d", who, sample_bytes);
-    STEM_CHECK_ARG((bit_depth == 8 || bit_depth == 10) && bit_depth <= 8 * sample_bytes, "%s: bit_depth %d in %d-byte samples (8, or 10 in two bytes)", who,
-                   bit_depth, sample_bytes);
-    const long long items = (long long)(H / 2) * ((W + 3) / 4);
-    STEM_CHECK_ARG(items <= (long long)YUV_THREADS * 0x7fffffff, "%s: %d x %d is too large", who, H, W);
-    *nblk = (int)((items + YUV_THREADS - 1) / YUV_THREADS);
-    return 0;
-}
-
-bool aligned_to(const void *p, size_t a) { return p == nullptr || (((uintptr_t)p) & (a - 1)) == 0; }
 
 template <typename T>
 int launch_to_rgb(const void *y, const void *u, const void *v, int B, int H, int W, int nblk, float peak, int nearest, int clamp01, float *rgb,

@@ -413,25 +413,30 @@ class EntropyModel(nn.Module):
             means = means.expand(shape).contiguous()
         return F.to_nhwc(means)
 
-    def _compress(self, inputs, indexes=None, means=None, chan_means=None, scales=None):
+    def _compress(self, inputs, indexes=None, means=None, chan_means=None, scales=None, return_y_hat=False):
         """One stem_symbols_pack launch -> symbols (and, with indexes=None, the indexes: of `scales`, else the channel numbers) in
-        the reference's flattening order, one copy to the host, the host coder once per batch element."""
+        the reference's flattening order, one copy to the host, the host coder once per batch element.  return_y_hat: -> (strings,
+        stem_symbols_unpack of the symbols still on the device: the values `_decompress` of the strings gives, NHWC memory)."""
         x = F.to_nhwc(inputs.detach())
         m = self._elementwise_means(means, inputs.shape)
         t = self.host_tables()
         if indexes is None:
             table, bound = self._scale_index_args() if scales is not None else (None, 0.0)
             sc = F.to_nhwc(scales.detach()) if scales is not None else None
-            sym, idx = F.symbols_pack(x, m, chan_means, sc, table, bound).cpu().numpy()
+            si = F.symbols_pack(x, m, chan_means, sc, table, bound)
+            sym, idx = si.cpu().numpy()
         else:
-            sym = F.symbols_pack(x, m, chan_means, want_indexes=False)[0].cpu().numpy()
+            si = F.symbols_pack(x, m, chan_means, want_indexes=False)
+            sym = si[0].cpu().numpy()
             idx = indexes.int().cpu().contiguous().numpy()
         enc = RansEncoder()
-        return [enc.encode_with_indexes(sym[i], idx[i], t) for i in range(sym.shape[0])]
+        strings = [enc.encode_with_indexes(sym[i], idx[i], t) for i in range(sym.shape[0])]
+        return (strings, F.symbols_unpack(si[0], m, chan_means)) if return_y_hat else strings
 
-    def compress(self, inputs, indexes, means=None, scales=None):
+    def compress(self, inputs, indexes, means=None, scales=None, return_y_hat=False):
         """symbols = round(inputs - means) coded with the host rANS, one string per batch element (:201-233).  indexes=None with
-        `scales` (not in the reference): the indexes build_indexes(scales) would give are computed by the launch that quantises."""
+        `scales` (not in the reference): the indexes build_indexes(scales) would give are computed by the launch that quantises.
+        return_y_hat=True: -> (strings, what `decompress` of them returns), the second from the encoder's own symbols."""
         if len(inputs.size()) != 4:
             raise ValueError("Invalid `inputs` size. Expected a 4-D tensor.")
         if indexes is None:
@@ -441,7 +446,7 @@ class EntropyModel(nn.Module):
             raise ValueError("`indexes` and `scales` are alternatives.")
         elif inputs.size() != indexes.size():
             raise ValueError("`inputs` and `indexes` should have the same size.")
-        return self._compress(inputs, indexes, means=means, scales=scales)
+        return self._compress(inputs, indexes, means=means, scales=scales, return_y_hat=return_y_hat)
 
     @staticmethod
     def _check_decompress_args(strings, indexes, means):
@@ -622,11 +627,11 @@ class EntropyBottleneck(EntropyModel):
         indexes = torch.arange(Cc).view(1, -1, 1, 1)
         return indexes.int().repeat(N, 1, H, W)
 
-    def compress(self, x):
+    def compress(self, x, return_y_hat=False):
         """the medians go in as one value per channel and the indexes are the channel numbers (`_build_indexes`), both inside the launch"""
         if len(x.size()) != 4:
             raise ValueError("Invalid `inputs` size. Expected a 4-D tensor.")
-        return self._compress(x, chan_means=self._medians_vec())
+        return self._compress(x, chan_means=self._medians_vec(), return_y_hat=return_y_hat)
 
     def decompress(self, strings, size):
         if not isinstance(strings, (tuple, list)):

@@ -1394,6 +1394,61 @@ def rgb_to_yuv420(x, bit_depth=None, source=None):
     return yo, uo, vo, sse
 
 
+def pad_geometry(h, w, multiple=64):
+    """bitstream.pad's centred geometry (codec.py:122-136): -> (Hp, Wp, top, left) of an h x w image in a frame whose sides are
+    multiples of `multiple`"""
+    Hp, Wp = (h + multiple - 1) // multiple * multiple, (w + multiple - 1) // multiple * multiple
+    return Hp, Wp, (Hp - h) // 2, (Wp - w) // 2
+
+
+def yuv420_to_rgb_padded(y, u, v, bit_depth=8, upsample="bilinear", clamp01=True, multiple=64, frame=None):
+    """`bitstream.pad(yuv420_to_rgb(y, u, v, ...), multiple)` as one kernel (stem_yuv420_to_rgb_padded): the integer planes go straight
+    into the zero-padded fp32 frame [B,3,Hp,Wp] an image model reads; the interior has yuv420_to_rgb's bits, the pad is +0.0.
+    frame=(Hp, Wp, top, left) places the image anywhere in a frame of any size instead.  No host synchronisation."""
+    y, u, v, B, H, W, sb = _yuv_planes_check(y, u, v, bit_depth, "yuv420_to_rgb_padded")
+    if upsample not in YUV_UPSAMPLE:
+        raise ValueError(f'Invalid upsampling mode "{upsample}".')
+    Hp, Wp, top, left = (int(a) for a in (frame if frame is not None else pad_geometry(H, W, int(multiple))))
+    if top < 0 or left < 0 or top + H > Hp or left + W > Wp:
+        raise ValueError(f"yuv420_to_rgb_padded: the {H} x {W} image at ({top}, {left}) does not fit a frame of {Hp} x {Wp}")
+    out = torch.empty((B, 3, Hp, Wp), dtype=torch.float32, device=y.device)
+    _lib.check_frameio(_lib.frameio().stem_yuv420_to_rgb_padded(y.data_ptr(), u.data_ptr(), v.data_ptr(), B, H, W, sb, bit_depth,
+                                                               YUV_UPSAMPLE[upsample], int(bool(clamp01)), out.data_ptr(), Hp, Wp, top, left,
+                                                               _stream()))
+    return out
+
+
+def rgb_window_to_yuv420(x, size, bit_depth=8, origin=None):
+    """`rgb_to_yuv420(bitstream.crop(x, size).contiguous(), bit_depth)` as one kernel (stem_rgb_window_to_yuv420): the integer planes
+    (uint8 | uint16) of the centred h x w window of the fp32 frame x [B,3,Hp,Wp], read in place -- x may be a view with wider rows.
+    origin=(top, left) names another window.  -> (y [B,h,w], u, v [B,h/2,w/2]).  No host synchronisation."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("rgb_window_to_yuv420: STEM HIP kernels need CUDA/ROCm tensors (no CPU fallback exists)")
+    if x.dtype != torch.float32:
+        raise TypeError(f"rgb_window_to_yuv420: the RGB batch is fp32, got {x.dtype}")
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
+        raise ValueError(f"rgb_window_to_yuv420 takes an RGB batch [B,3,H,W], got {tuple(x.shape)}")
+    B, _, Hp, Wp = x.shape
+    h, w = (int(s) for s in size)
+    if h % 2 or w % 2 or h < 2 or w < 2:
+        raise ValueError(f"rgb_window_to_yuv420: 4:2:0 frames have even sides >= 2, got {h} x {w}")
+    top, left = (int(a) for a in origin) if origin is not None else ((Hp - h) // 2, (Wp - w) // 2)
+    if top < 0 or left < 0 or top + h > Hp or left + w > Wp:
+        raise ValueError(f"rgb_window_to_yuv420: the {h} x {w} window at ({top}, {left}) does not fit a frame of {Hp} x {Wp}")
+    x = x.detach()
+    sb_, sc, sh, sw = x.stride()
+    if sw != 1 or sh < Wp or sc < (Hp - 1) * sh + Wp or (B > 1 and sb_ != 3 * sc):
+        x = x.contiguous()                                                           # not a row / plane pitched view: a dense copy
+        sb_, sc, sh, sw = x.stride()
+    dt = _yuv_dtype(bit_depth)
+    yo = torch.empty((B, h, w), dtype=dt, device=x.device)
+    uo = torch.empty((B, h // 2, w // 2), dtype=dt, device=x.device)
+    vo = torch.empty((B, h // 2, w // 2), dtype=dt, device=x.device)
+    _lib.check_frameio(_lib.frameio().stem_rgb_window_to_yuv420(x.data_ptr(), B, Hp, Wp, sh, sc, top, left, h, w, yo.data_ptr(), uo.data_ptr(),
+                                                               vo.data_ptr(), yo.element_size(), bit_depth, _stream()))
+    return yo, uo, vo
+
+
 def ycbcr_convert(x, to_rgb):
     """transforms.ycbcr2rgb (to_rgb) / rgb2ycbcr of an fp32 device tensor [3,H,W] or [N,3,H,W] (stem_ycbcr_convert)"""
     _require_cuda(x)

@@ -111,10 +111,14 @@ class FactorizedPrior(CompressionModel):
         x_hat = self.g_s(y_hat)
         return {"y": y, "y_hat": y_hat, "x_hat": x_hat, "likelihoods": {"y": y_likelihoods}}
 
-    def compress(self, x):
-        """priors.py:172-175 -> {"strings": [y_strings], "shape": y.shape[-2:]}"""
+    def compress(self, x, return_y_hat=False):
+        """priors.py:172-175 -> {"strings": [y_strings], "shape": y.shape[-2:]}; return_y_hat=True adds "y_hat", what `decompress` of the
+        strings returns as "y_hat", from the symbols the encoder still holds on the device"""
         with torch.no_grad():
             y = self.g_a(x)
+            if return_y_hat:
+                y_strings, y_hat = self.entropy_bottleneck.compress(y, return_y_hat=True)
+                return {"strings": [y_strings], "shape": y.size()[-2:], "y_hat": y_hat}
             y_strings = self.entropy_bottleneck.compress(y)
         return {"strings": [y_strings], "shape": y.size()[-2:]}
 
@@ -176,14 +180,18 @@ class ScaleHyperprior(CompressionModel):
         return {"y": y, "y_hat": y_hat, "x_hat": x_hat, "likelihoods": {"y": y_likelihoods, "z": z_likelihoods},
                 "entropy_params": {"scales_hat": scales_hat}}
 
-    def compress(self, x):
-        """priors.py:294-304, 364-376 -> {"strings": [y_strings, z_strings], "shape": z.shape[-2:]}"""
+    def compress(self, x, return_y_hat=False):
+        """priors.py:294-304, 364-376 -> {"strings": [y_strings, z_strings], "shape": z.shape[-2:]}; return_y_hat=True adds "y_hat", what
+        `decompress` of the strings returns as "y_hat", from the symbols the encoder still holds on the device"""
         with torch.no_grad():
             y = self.g_a(x)
             z = self.h_a(self._hyper_input(y))
             z_strings = self.entropy_bottleneck.compress(z)
             z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
             scales_hat, means_hat = self._gaussian_params(z_hat)
+            if return_y_hat:
+                y_strings, y_hat = self.gaussian_conditional.compress(y, None, means=means_hat, scales=scales_hat, return_y_hat=True)
+                return {"strings": [y_strings, z_strings], "shape": z.size()[-2:], "y_hat": y_hat}
             y_strings = self.gaussian_conditional.compress(y, None, means=means_hat, scales=scales_hat)
         return {"strings": [y_strings, z_strings], "shape": z.size()[-2:]}
 
@@ -283,11 +291,12 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
         return {"y": y, "y_hat": y_hat, "x_hat": x_hat, "likelihoods": {"y": y_likelihoods, "z": z_likelihoods},
                 "entropy_params": {"scales_hat": scales_hat, "means_hat": means_hat}}
 
-    def compress(self, x, order="raster"):
-        """priors.py:544-584 -> {"strings": [y_strings, z_strings], "shape": z.shape[-2:]}; order="wavefront" (codec.wave_order) adds "order" to it"""
+    def compress(self, x, order="raster", return_y_hat=False):
+        """priors.py:544-584 -> {"strings": [y_strings, z_strings], "shape": z.shape[-2:]}; order="wavefront" (codec.wave_order) adds "order" to
+        it, return_y_hat=True "y_hat": the latent `decompress` returns, left by the coding kernels in their buffer (no decoder runs)"""
         from ..codec import iframe_compress
         with torch.no_grad():
-            return iframe_compress(self, x, order=order)
+            return iframe_compress(self, x, order=order, return_y_hat=return_y_hat)
 
     def decompress(self, strings, shape, order="raster"):
         """priors.py:633-674 -> {"x_hat", "y_hat"}"""

@@ -104,10 +104,11 @@ class _StemBase(CompressionModel):
         return {"y_hat": y_hat, "likelihoods": {"y": lik_y, "z": lik_z}}
 
     # ---- bitstream side ----------------------------------------------------------------------
-    def compress(self, y_cur, y_conditioned, order="raster"):
-        """order: "raster" (the reference's) or "wavefront" (codec.wave_order; the result then carries "order")"""
+    def compress(self, y_cur, y_conditioned, order="raster", return_y_hat=False):
+        """order: "raster" (the reference's) or "wavefront" (codec.wave_order; the result then carries "order").  return_y_hat=True: the
+        result also carries "y_hat", the latent `decompress` of these strings returns, from the encoder's own state (no decoder runs)"""
         from ..codec import stem_compress
-        return stem_compress(self, y_cur, y_conditioned, order=order)
+        return stem_compress(self, y_cur, y_conditioned, order=order, return_y_hat=return_y_hat)
 
     def decompress(self, strings, shape, y_conditioned, order="raster"):
         from ..codec import stem_decompress
