@@ -1,5 +1,5 @@
 """ctypes loader for the C-ABI libraries (include/stem_hip.h + include/stem_ar_batch.h + include/stem_blocks.h +
-include/stem_hyperprior.h + include/stem_eb_filters.h + include/stem_gdn1.h + include/stem_validation.h, include/stem_frameio.h,
+include/stem_hyperprior.h + include/stem_eb_filters.h + include/stem_gdn1.h + include/stem_validation.h, include/stem_frameio.h, include/stem_roiio.h,
 include/stem_rans.h, include/stem_dp.h).
 
 The headers are the single statement of the ABI: every prototype and descriptor structure below is read from them (_abi.py).
@@ -23,11 +23,14 @@ RANS_SO = os.environ.get("STEM_RANS_LIBRARY") or os.path.join(_PKG, "libstem_ran
 
 # the frame ingest / emit kernels of the sequence codec (include/stem_frameio.h): a library of their own
 FRAMEIO_SO = os.path.join(_PKG, "libstem_frameio.so")
+# the per-frame passes of the pixel-domain sequence codec (include/stem_roiio.h): a library of their own as well
+ROIIO_SO = os.path.join(_PKG, "libstem_roiio.so")
 DP_SO = os.environ.get("STEM_DP_LIBRARY") or os.path.join(_PKG, "libstem_dp.so")
 _hip = None
 _rans = None
 _dp = None
 _frameio = None
+_roiio = None
 
 
 class StemLibraryError(RuntimeError):
@@ -63,6 +66,8 @@ _HIP_GDN1_PROTO, _HIP_GDN1_SIG, _ = _tables("stem_gdn1.h")
 _HIP_VALIDATION_PROTO, _HIP_VALIDATION_SIG, _ = _tables("stem_validation.h")
 # libstem_frameio.so's padded-frame ingest and window emit kernels (csrc/frameio.hip; not launch-tape entries either)
 _FRAMEIO_PROTO, _FRAMEIO_SIG, _ = _tables("stem_frameio.h")
+# libstem_roiio.so's recondition and ROI rasteriser kernels (csrc/roiio.hip; not launch-tape entries either)
+_ROIIO_PROTO, _ROIIO_SIG, _ = _tables("stem_roiio.h")
 _RANS_PROTO, _RANS_SIG, _RANS_RESTYPE = _tables("stem_rans.h")
 _DP_PROTO, _DP_SIG, _ = _tables("stem_dp.h")
 _STRUCTS = _abi.structs(_header("stem_hip.h"))
@@ -132,6 +137,22 @@ def check_frameio(rc: int):
         raise RuntimeError((frameio().stem_frameio_last_error() or b"").decode() or f"libstem_frameio error {rc}")
 
 
+def roiio():
+    """libstem_roiio.so (include/stem_roiio.h), or raise: like libstem_hip.so it has no fallback"""
+    global _roiio
+    if _roiio is None:
+        if not os.path.exists(ROIIO_SO):
+            raise StemLibraryError(f"{ROIIO_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                                   "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the frame kernels.")
+        _roiio = _bind(C.CDLL(ROIIO_SO), _ROIIO_PROTO)
+    return _roiio
+
+
+def check_roiio(rc: int):
+    if rc != 0:
+        raise RuntimeError((roiio().stem_roiio_last_error() or b"").decode() or f"libstem_roiio error {rc}")
+
+
 def rans():
     global _rans
     if _rans is None:
@@ -176,6 +197,10 @@ def declared_hip_validation_symbols():
 
 def declared_frameio_symbols():
     return sorted(_FRAMEIO_SIG)
+
+
+def declared_roiio_symbols():
+    return sorted(_ROIIO_SIG)
 
 
 def header_macro(header, name):

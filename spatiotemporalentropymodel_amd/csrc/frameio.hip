@@ -32,18 +32,8 @@ namespace {
 
 using namespace yuv_elem;
 
-// four (or fewer) zeros into each colour plane at o
-__device__ inline void zero_group(float *o, size_t plane, int n, bool vec)
-{
-    const float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (vec) {
-        store_n<true>(o, 4, z), store_n<true>(o + plane, 4, z), store_n<true>(o + 2 * plane, 4, z);
-    } else {
-        store_n<false>(o, n, z), store_n<false>(o + plane, n, z), store_n<false>(o + 2 * plane, n, z);
-    }
-}
-
-// blockIdx.x < nblk_img: image items; behind them: pad items.  pvec: a pad group of four aligned columns is one vector per plane.
+// blockIdx.x < nblk_img: image items; behind them: pad items (yuv_elem.h: pad_item_at).  pvec: a pad group of four aligned columns is one
+// vector per plane.
 template <typename T, bool LVEC, bool SVEC>
 __global__ __launch_bounds__(YUV_THREADS) void yuv420_to_rgb_padded_kernel(const T *__restrict__ yp, const T *__restrict__ up,
                                                                            const T *__restrict__ vp, int H, int W, float peak, int nearest,
@@ -61,30 +51,9 @@ __global__ __launch_bounds__(YUV_THREADS) void yuv420_to_rgb_padded_kernel(const
                                           frame + (size_t)top * Wp + left, (size_t)Wp, oplane);
         return;
     }
-    long long p = (long long)(blockIdx.x - nblk_img) * YUV_THREADS + threadIdx.x;
-    const int gW = (Wp + 3) >> 2;
-    const long long bands = (long long)(Hp - H) * gW;
-    int row, c0, c1;
-    if (p < bands) {                                            // the full rows above and below the image
-        const int r = (int)(p / gW);
-        row = r < top ? r : r + H;
-        c0 = (int)(p - (long long)r * gW) * 4;
-        c1 = c0 + 4 < Wp ? c0 + 4 : Wp;
-    } else {                                                    // left and right of the image
-        p -= bands;
-        const int right0 = left + W, gL = (left + 3) >> 2, gR = (Wp - right0 + 3) >> 2, gs = gL + gR;
-        if (gs == 0 || p >= (long long)H * gs) return;
-        const int r = (int)(p / gs), g = (int)(p - (long long)r * gs);
-        row = top + r;
-        if (g < gL) {
-            c0 = 4 * g;
-            c1 = c0 + 4 < left ? c0 + 4 : left;
-        } else {
-            c0 = right0 + 4 * (g - gL);
-            c1 = c0 + 4 < Wp ? c0 + 4 : Wp;
-        }
-    }
-    zero_group(frame + (size_t)row * Wp + c0, oplane, c1 - c0, pvec && c1 - c0 == 4 && (c0 & 3) == 0);
+    const PadItem pad = pad_item_at((long long)(blockIdx.x - nblk_img) * YUV_THREADS + threadIdx.x, Hp, Wp, top, left, H, W);
+    if (!pad.live) return;
+    zero_group(frame + (size_t)pad.row * Wp + pad.c0, oplane, pad.c1 - pad.c0, pvec && pad.c1 - pad.c0 == 4 && (pad.c0 & 3) == 0);
 }
 
 template <typename T, bool LVEC, bool SVEC>
@@ -92,29 +61,10 @@ __global__ __launch_bounds__(YUV_THREADS) void rgb_window_to_yuv420_kernel(const
                                                                            int top, int left, int H, int W, double peak, T *__restrict__ yi,
                                                                            T *__restrict__ ui, T *__restrict__ vi)
 {
-    const int Hc = H >> 1, Wc = W >> 1;
-    const YuvItem it = yuv_item_at((long long)blockIdx.x * YUV_THREADS + threadIdx.x, Hc, W);
+    const YuvItem it = yuv_item_at((long long)blockIdx.x * YUV_THREADS + threadIdx.x, H >> 1, W);
     if (!it.live) return;
-    const size_t b = blockIdx.y, plane = (size_t)H * W, cplane = (size_t)Hc * Wc;
-    const int nc = it.valid >> 1;                               // chroma samples of this item: 2, or 1
-    YuvItemOut<T> o;
-    rgb_item_to_yuv420<T, LVEC>(rgb + b * 3 * plane_pitch + (size_t)(top + 2 * it.cy) * row_pitch + left + it.x0, row_pitch, plane_pitch, it.valid,
-                                peak, o);
-    const size_t off = b * plane + (size_t)(2 * it.cy) * W + it.x0;
-    store_n<SVEC>(yi + off, it.valid, o.yq[0]);
-    store_n<SVEC>(yi + off + W, it.valid, o.yq[1]);
-    const size_t coff = b * cplane + (size_t)it.cy * Wc + (it.x0 >> 1);
-    store_n<SVEC>(ui + coff, nc, o.uq);
-    store_n<SVEC>(vi + coff, nc, o.vq);
-}
-
-// the window of H x W at (top, left) lies inside Hp x Wp
-int window_fits(const char *who, int Hp, int Wp, int top, int left, int H, int W)
-{
-    STEM_CHECK_ARG(Hp > 0 && Wp > 0 && Hp < (1 << 30) && Wp < (1 << 30), "%s: a frame of %d x %d", who, Hp, Wp);
-    STEM_CHECK_ARG(top >= 0 && left >= 0 && top <= Hp - H && left <= Wp - W, "%s: the %d x %d window at (%d, %d) does not fit a frame of %d x %d", who, H,
-                   W, top, left, Hp, Wp);
-    return 0;
+    const size_t b = blockIdx.y;
+    rgb_window_item_to_planes<T, LVEC, SVEC>(rgb + b * 3 * plane_pitch, row_pitch, plane_pitch, top, left, H, W, b, it, peak, yi, ui, vi);
 }
 
 template <typename T>
@@ -178,9 +128,7 @@ STEM_EXPORT int stem_yuv420_to_rgb_padded(const void *y, const void *u, const vo
     if (int rc = window_fits(who, Hp, Wp, top, left, H, W)) return rc;
     STEM_CHECK_ARG(aligned_to(y, sample_bytes) && aligned_to(u, sample_bytes) && aligned_to(v, sample_bytes) && aligned_to(rgb, 4),
                    "%s: misaligned pointer", who);
-    // pad items: the full rows, then the groups beside the image (yuv420_to_rgb_padded_kernel numbers them the same way)
-    const long long pad_items = (long long)(Hp - H) * ((Wp + 3) / 4) + (long long)H * ((left + 3) / 4 + (Wp - left - W + 3) / 4);
-    const long long nblk_pad = (pad_items + YUV_THREADS - 1) / YUV_THREADS;
+    const long long nblk_pad = (pad_item_count(Hp, Wp, left, H, W) + YUV_THREADS - 1) / YUV_THREADS;
     STEM_CHECK_ARG(nblk_img + nblk_pad <= 0x7fffffffLL, "%s: a frame of %d x %d is too large", who, Hp, Wp);
     const float peak = (float)((1 << bit_depth) - 1);
     hipStream_t st = (hipStream_t)stream;

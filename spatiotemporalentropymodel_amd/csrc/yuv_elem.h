@@ -1,6 +1,7 @@
 // The arithmetic of the raw-frame kernels, stated once: yuv.hip (dense frames: stem_yuv420_to_rgb, stem_rgb_to_yuv420) and frameio.hip
 // (a frame inside a padded one: stem_yuv420_to_rgb_padded, stem_rgb_window_to_yuv420) include this file and differ only in where a
-// work item's samples live -- row and plane pitches, and which accesses may be vectors.  A work item is 2 rows x 4 columns of luma
+// work item's samples live -- row and plane pitches, and which accesses may be vectors; roiio.hip (stem_rgb_window_recondition) takes
+// the emit kernel's image item and the ingest kernel's pad items from here as well.  A work item is 2 rows x 4 columns of luma
 // = 1 row x 2 columns of chroma, in IMAGE coordinates: the chroma taps clamp at the image's edge whatever surrounds the image in
 // memory, and the 2 x 2 chroma blocks are aligned to the image.  The orders of operations are those yuv.hip documents; the integer
 // planes and fp32 pixels of the two files are the same bits because they come out of these functions.
@@ -182,6 +183,91 @@ __device__ inline void rgb_item_to_yuv420(const float *__restrict__ src, size_t 
         o.uq[k] = (T)rint(fmin(fmax(cb, 0.0), 1.0) * peak);
         o.vq[k] = (T)rint(fmin(fmax(cr, 0.0), 1.0) * peak);
     }
+}
+
+// ---- a window inside a padded frame (frameio.hip, roiio.hip) -------------------------------------------------------------------------
+// One image item of the window of H x W at (top, left) of image b's frame (rows row_pitch floats apart, colour planes plane_pitch)
+// -> its samples in the dense integer planes yi [B][H][W], ui and vi [B][H/2][W/2].
+template <typename T, bool LVEC, bool SVEC>
+__device__ inline void rgb_window_item_to_planes(const float *frame, size_t row_pitch, size_t plane_pitch, int top, int left, int H, int W, size_t b,
+                                                 const YuvItem it, double peak, T *__restrict__ yi, T *__restrict__ ui, T *__restrict__ vi)
+{
+    const int Hc = H >> 1, Wc = W >> 1;
+    const size_t plane = (size_t)H * W, cplane = (size_t)Hc * Wc;
+    const int nc = it.valid >> 1;                               // chroma samples of this item: 2, or 1
+    YuvItemOut<T> o;
+    rgb_item_to_yuv420<T, LVEC>(frame + (size_t)(top + 2 * it.cy) * row_pitch + left + it.x0, row_pitch, plane_pitch, it.valid, peak, o);
+    const size_t off = b * plane + (size_t)(2 * it.cy) * W + it.x0;
+    store_n<SVEC>(yi + off, it.valid, o.yq[0]);
+    store_n<SVEC>(yi + off + W, it.valid, o.yq[1]);
+    const size_t coff = b * cplane + (size_t)it.cy * Wc + (it.x0 >> 1);
+    store_n<SVEC>(ui + coff, nc, o.uq);
+    store_n<SVEC>(vi + coff, nc, o.vq);
+}
+
+// Pad item p of a frame of Hp x Wp around a window of H x W at (top, left): columns c0 .. c1 (at most four) of row `row`.  The items
+// are numbered over the pad alone: first the Hp - H full rows above and below the window in groups of four columns, then, row by row
+// of the window, the groups left and right of it (the right ones start at left + W, whatever its alignment).  No element belongs to
+// two items and none to no item, so a poisoned pad comes back clean.
+struct PadItem {
+    int row, c0, c1;
+    bool live;
+};
+__device__ inline PadItem pad_item_at(long long p, int Hp, int Wp, int top, int left, int H, int W)
+{
+    const int gW = (Wp + 3) >> 2;
+    const long long bands = (long long)(Hp - H) * gW;
+    PadItem it;
+    it.live = true;
+    if (p < bands) {                                            // the full rows above and below the window
+        const int r = (int)(p / gW);
+        it.row = r < top ? r : r + H;
+        it.c0 = (int)(p - (long long)r * gW) * 4;
+        it.c1 = it.c0 + 4 < Wp ? it.c0 + 4 : Wp;
+        return it;
+    }
+    p -= bands;                                                 // left and right of the window
+    const int right0 = left + W, gL = (left + 3) >> 2, gR = (Wp - right0 + 3) >> 2, gs = gL + gR;
+    if (gs == 0 || p >= (long long)H * gs) {
+        it.live = false, it.row = it.c0 = it.c1 = 0;
+        return it;
+    }
+    const int r = (int)(p / gs), g = (int)(p - (long long)r * gs);
+    it.row = top + r;
+    if (g < gL) {
+        it.c0 = 4 * g;
+        it.c1 = it.c0 + 4 < left ? it.c0 + 4 : left;
+    } else {
+        it.c0 = right0 + 4 * (g - gL);
+        it.c1 = it.c0 + 4 < Wp ? it.c0 + 4 : Wp;
+    }
+    return it;
+}
+
+// a pad item's zeros, into each colour plane at o; vec: four aligned columns are one vector per plane
+__device__ inline void zero_group(float *o, size_t plane, int n, bool vec)
+{
+    const float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (vec) {
+        store_n<true>(o, 4, z), store_n<true>(o + plane, 4, z), store_n<true>(o + 2 * plane, 4, z);
+    } else {
+        store_n<false>(o, n, z), store_n<false>(o + plane, n, z), store_n<false>(o + 2 * plane, n, z);
+    }
+}
+
+// host side: how many pad items `pad_item_at` numbers
+inline long long pad_item_count(int Hp, int Wp, int left, int H, int W)
+{
+    return (long long)(Hp - H) * ((Wp + 3) / 4) + (long long)H * ((left + 3) / 4 + (Wp - left - W + 3) / 4);
+}
+
+// host side: the window of H x W at (top, left) lies inside Hp x Wp
+inline int window_fits(const char *who, int Hp, int Wp, int top, int left, int H, int W)
+{
+    STEM_CHECK_ARG(Hp > 0 && Wp > 0 && Hp < (1 << 30) && Wp < (1 << 30), "%s: a frame of %d x %d", who, Hp, Wp);
+    STEM_CHECK_ARG(top >= 0 && left >= 0 && top <= Hp - H && left <= Wp - W, "%s: the %d x %d window at (%d, %d) does not fit a frame of %d x %d", who, H,
+                   W, top, left, Hp, Wp);
+    return 0;
 }
 
 // ---- host side: the geometry checks of every entry point; no device needed.  nblk: workgroups per image. ---------------------------

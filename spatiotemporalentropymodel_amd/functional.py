@@ -1449,6 +1449,113 @@ def rgb_window_to_yuv420(x, size, bit_depth=8, origin=None):
     return yo, uo, vo
 
 
+def rgb_window_recondition(x, size, bit_depth=None, origin=None):
+    """`x[...] = bitstream.pad(bitstream.crop(x, size), ...)` IN PLACE as one kernel (stem_rgb_window_recondition): the centred h x w
+    window of the fp32 frame x [B,3,Hp,Wp] stays, every other element becomes +0.0 -- the decoded padded frame turns into the next P
+    frame's condition.  x may be a view with wider rows (the gap is not touched), but not one that needs a copy.  bit_depth 8 | 10: the
+    same pass also returns the window's integer planes, `rgb_window_to_yuv420(x, size, bit_depth, origin)` bit for bit; None: no planes.
+    origin=(top, left) names another window.  -> (y [B,h,w], u, v [B,h/2,w/2]) or None.  No launch when there is neither a border nor
+    planes to write.  No host synchronisation."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("rgb_window_recondition: STEM HIP kernels need CUDA/ROCm tensors (no CPU fallback exists)")
+    if x.dtype != torch.float32:
+        raise TypeError(f"rgb_window_recondition: the RGB batch is fp32, got {x.dtype}")
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
+        raise ValueError(f"rgb_window_recondition takes an RGB batch [B,3,H,W], got {tuple(x.shape)}")
+    B, _, Hp, Wp = x.shape
+    h, w = (int(s) for s in size)
+    if h % 2 or w % 2 or h < 2 or w < 2:
+        raise ValueError(f"rgb_window_recondition: 4:2:0 frames have even sides >= 2, got {h} x {w}")
+    top, left = (int(a) for a in origin) if origin is not None else ((Hp - h) // 2, (Wp - w) // 2)
+    if top < 0 or left < 0 or top + h > Hp or left + w > Wp:
+        raise ValueError(f"rgb_window_recondition: the {h} x {w} window at ({top}, {left}) does not fit a frame of {Hp} x {Wp}")
+    x = x.detach()
+    sb_, sc, sh, sw = x.stride()
+    if sw != 1 or sh < Wp or sc < (Hp - 1) * sh + Wp or (B > 1 and sb_ != 3 * sc):
+        raise ValueError(f"rgb_window_recondition works in place: strides {tuple(x.stride())} are no row / plane pitched view of {tuple(x.shape)}")
+    if bit_depth is None:
+        if (h, w) == (Hp, Wp):
+            return None
+        _lib.check_roiio(_lib.roiio().stem_rgb_window_recondition(x.data_ptr(), B, Hp, Wp, sh, sc, top, left, h, w, None, None, None, 1, 8, _stream()))
+        return None
+    dt = _yuv_dtype(bit_depth)
+    yo = torch.empty((B, h, w), dtype=dt, device=x.device)
+    uo = torch.empty((B, h // 2, w // 2), dtype=dt, device=x.device)
+    vo = torch.empty((B, h // 2, w // 2), dtype=dt, device=x.device)
+    _lib.check_roiio(_lib.roiio().stem_rgb_window_recondition(x.data_ptr(), B, Hp, Wp, sh, sc, top, left, h, w, yo.data_ptr(), uo.data_ptr(),
+                                                             vo.data_ptr(), yo.element_size(), bit_depth, _stream()))
+    return yo, uo, vo
+
+
+def roi_boxes_check(boxes, background=0.0):
+    """the host side of roi_map_padded's contract: boxes (x0, y0, x1, y1, value[, feather]) with integer corners in int32, x0 < x1,
+    y0 < y1, an integer feather >= 0, value and background in [0, 1] (a NaN is outside it), at most STEM_ROI_MAX_BOXES of them
+    -> ([(x0, y0, x1, y1, feather)], [value], background)"""
+    import math
+    import operator
+    cap = _lib.header_macro("stem_roiio.h", "STEM_ROI_MAX_BOXES")
+    boxes = list(boxes)
+    if len(boxes) > cap:
+        raise ValueError(f"roi_map_padded takes at most {cap} boxes, got {len(boxes)}")
+    background = float(background)
+    if not 0.0 <= background <= 1.0:
+        raise ValueError(f"roi_map_padded: the background level is in [0, 1], got {background}")
+    geo, values = [], []
+    for k, box in enumerate(boxes):
+        box = tuple(box)
+        if len(box) not in (5, 6):
+            raise ValueError(f"roi_map_padded: box {k} is (x0, y0, x1, y1, value[, feather]), got {box!r}")
+        try:
+            x0, y0, x1, y1 = (operator.index(a) for a in box[:4])
+            feather = operator.index(box[5]) if len(box) == 6 else 0
+        except TypeError:
+            raise ValueError(f"roi_map_padded: box {k} has corners or a feather that are no integers: {box!r}") from None
+        value = float(box[4])
+        if math.isnan(value) or not 0.0 <= value <= 1.0:
+            raise ValueError(f"roi_map_padded: the value of box {k} is in [0, 1], got {value}")
+        if not (x0 < x1 and y0 < y1):
+            raise ValueError(f"roi_map_padded: box {k} is empty or reversed: x {x0} .. {x1}, y {y0} .. {y1}")
+        if feather < 0:
+            raise ValueError(f"roi_map_padded: the feather of box {k} is >= 0, got {feather}")
+        if any(not -2 ** 31 <= a < 2 ** 31 for a in (x0, y0, x1, y1, feather)):
+            raise ValueError(f"roi_map_padded: box {k} does not fit 32-bit integers: {box!r}")
+        geo.append((x0, y0, x1, y1, feather))
+        values.append(value)
+    return geo, values, background
+
+
+def roi_map_padded(boxes, size, background=0.0, multiple=64, frame=None, device=None):
+    """The ROI rasteriser (stem_roi_map_padded): rectangles (x0, y0, x1, y1, value[, feather]) -- half-open, in the coordinates of the
+    h x w frame, free to reach outside it -- over a background level, straight into the zero-padded fp32 quality map [1,1,Hp,Wp] a model
+    reads: `bitstream.pad(map, multiple)` of the map include/stem_roiio.h defines (later boxes override earlier ones; within `feather`
+    pixels of its edge a box blends from what lies under it), with no host map and no eager pad.  frame=(Hp, Wp, top, left) places the
+    window anywhere in a frame of any size instead.  The boxes travel in one small host-to-device copy.  No host synchronisation."""
+    import numpy as np
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None and torch.cuda.is_available() else (
+        None if device is None else torch.device(device))
+    if dev is None or dev.type != "cuda":
+        raise RuntimeError("roi_map_padded: STEM HIP kernels write CUDA/ROCm tensors (no CPU fallback exists)")
+    geo, values, background = roi_boxes_check(boxes, background)
+    h, w = (int(s) for s in size)
+    if h < 1 or w < 1:
+        raise ValueError(f"roi_map_padded: a frame of {h} x {w}")
+    Hp, Wp, top, left = (int(a) for a in (frame if frame is not None else pad_geometry(h, w, int(multiple))))
+    if top < 0 or left < 0 or top + h > Hp or left + w > Wp:
+        raise ValueError(f"roi_map_padded: the {h} x {w} window at ({top}, {left}) does not fit a frame of {Hp} x {Wp}")
+    n = len(geo)
+    with torch.cuda.device(dev):
+        out = torch.empty((1, 1, Hp, Wp), dtype=torch.float32, device=dev)
+        bptr = vptr = None
+        if n:
+            host = np.empty(6 * n, dtype=np.int32)                                   # [n][5] corners and feathers, then [n] values
+            host[:5 * n] = np.asarray(geo, dtype=np.int64).reshape(-1)
+            host[5 * n:].view(np.float32)[:] = np.asarray(values, dtype=np.float32)
+            packed = torch.from_numpy(host).to(dev)
+            bptr, vptr = packed.data_ptr(), packed.data_ptr() + 20 * n
+        _lib.check_roiio(_lib.roiio().stem_roi_map_padded(bptr, vptr, n, background, out.data_ptr(), Hp, Wp, top, left, h, w, _stream()))
+    return out
+
+
 def ycbcr_convert(x, to_rgb):
     """transforms.ycbcr2rgb (to_rgb) / rgb2ycbcr of an fp32 device tensor [3,H,W] or [N,3,H,W] (stem_ycbcr_convert)"""
     _require_cuda(x)

@@ -9,7 +9,7 @@ state-dict keys:
     stem_roi_i         :1017-1325 the I-frame counterpart (no temporal prior)
 
     forward(x_cur[, x_conditioned][, Qmap]) -> {"x_hat", "y_hat", "likelihoods": {"y", "z"}}
-    compress(...) -> {"strings": [y_strings, z_strings], "shape"};  decompress(strings, shape[, x_conditioned])
+    compress(..., return_x_hat=False) -> {"strings": [y_strings, z_strings], "shape"[, "x_hat"]};  decompress(strings, shape[, x_conditioned])
         -> {"x_hat", "y_hat", "entropy_params": {"scales_hat", "means_hat"}}
 
 All tensors between the modules stay NHWC in HBM; torch.cat / chunk are channel slices of one buffer.  Every
@@ -125,12 +125,17 @@ class _PixelStem(CompressionModel):
         x_hat = to_nchw(self._synthesis(y_hat, z_hat))         # plain NCHW image batch, differentiable
         return {"x_hat": x_hat, "y_hat": y_hat, "likelihoods": {"y": y_likelihoods, "z": z_likelihoods}}
 
-    def compress(self, *args):
+    def compress(self, *args, return_x_hat=False):
+        """return_x_hat=True: the result gains "x_hat", the tensor `decompress` of these strings returns, from the encoder's own symbols
+        (the one-shot coder's `return_y_hat=True`, then the synthesis transform): no decoder call"""
         x_cur, x_cond, Qmap = self._split_args(args)
         y_cur, y_conditioned, z = self._latents(x_cur, x_cond, Qmap)
         z_strings = self.entropy_bottleneck.compress(z)
         z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
         scales_hat, means_hat = self._gaussian_params(z_hat, y_conditioned).chunk(2, 1)
+        if return_x_hat:
+            y_strings, y_hat = self.gaussian_conditional.compress(y_cur, None, means=means_hat, scales=scales_hat, return_y_hat=True)
+            return {"strings": [y_strings, z_strings], "shape": z.size()[-2:], "x_hat": F.to_nchw(self._synthesis(y_hat, z_hat), clamp01=True)}
         y_strings = self.gaussian_conditional.compress(y_cur, None, means=means_hat, scales=scales_hat)
         return {"strings": [y_strings, z_strings], "shape": z.size()[-2:]}
 

@@ -31,7 +31,7 @@ would decode garbage without noticing, so it refuses instead.  It is a check aga
 
 Frames enter through functional.yuv420_to_rgb_padded (integer planes of a data.YUVSequence -> the padded fp32 frame, one kernel) and
 leave through functional.rgb_window_to_yuv420 (the window of the padded x_hat -> integer planes, one kernel): no eager-torch pad, crop
-or copy of a frame on the device.  The pixel-domain (stem_roi) models are not handled here.
+or copy of a frame on the device.  The pixel-domain (stem_roi) models have a codec of their own: video_pixel.py.
 """
 from __future__ import annotations
 
