@@ -1,5 +1,5 @@
 """ctypes loader for the C-ABI libraries (include/stem_hip.h + include/stem_ar_batch.h + include/stem_blocks.h +
-include/stem_hyperprior.h + include/stem_eb_filters.h + include/stem_gdn1.h + include/stem_validation.h, include/stem_frameio.h, include/stem_roiio.h,
+include/stem_hyperprior.h + include/stem_eb_filters.h + include/stem_gdn1.h + include/stem_validation.h, include/stem_tail.h, include/stem_frameio.h, include/stem_roiio.h,
 include/stem_rans.h, include/stem_dp.h).
 
 The headers are the single statement of the ABI: every prototype and descriptor structure below is read from them (_abi.py).
@@ -23,6 +23,8 @@ RANS_SO = os.environ.get("STEM_RANS_LIBRARY") or os.path.join(_PKG, "libstem_ran
 
 # the frame ingest / emit kernels of the sequence codec (include/stem_frameio.h): a library of their own
 FRAMEIO_SO = os.path.join(_PKG, "libstem_frameio.so")
+# the optimiser pass over a table of chunk ranges (include/stem_tail.h): a library of its own too
+TAIL_SO = os.path.join(_PKG, "libstem_tail.so")
 # the per-frame passes of the pixel-domain sequence codec (include/stem_roiio.h): a library of their own as well
 ROIIO_SO = os.path.join(_PKG, "libstem_roiio.so")
 DP_SO = os.environ.get("STEM_DP_LIBRARY") or os.path.join(_PKG, "libstem_dp.so")
@@ -30,6 +32,7 @@ _hip = None
 _rans = None
 _dp = None
 _frameio = None
+_tail = None
 _roiio = None
 
 
@@ -50,7 +53,7 @@ def _tables(header):
     return protos, {n: args for n, (_, args) in protos.items()}, {n: res for n, (res, _) in protos.items() if res is not C.c_int}
 
 
-# tape.py classifies the argument slots of a recorded call by _HIP_SIG and leaves the entries of _RESTYPE out of a schedule
+# tape.py classifies the argument slots of a recorded call by _HIP_SIG (with stem_tail.h's: _TAPE_SIG below) and leaves the entries of _RESTYPE out of a schedule
 _HIP_PROTO, _HIP_SIG, _RESTYPE = _tables("stem_hip.h")
 # libstem_hip.so's batched coding entry points (not launch-tape entries: tape.py does not see them)
 _HIP_BATCH_PROTO, _HIP_BATCH_SIG, _ = _tables("stem_ar_batch.h")
@@ -64,6 +67,11 @@ _HIP_EBF_PROTO, _HIP_EBF_SIG, _ = _tables("stem_eb_filters.h")
 _HIP_GDN1_PROTO, _HIP_GDN1_SIG, _ = _tables("stem_gdn1.h")
 # libstem_hip.so's eval-mode rate kernels and running loss sum of the validation pass (csrc/entropy.hip; not launch-tape entries either)
 _HIP_VALIDATION_PROTO, _HIP_VALIDATION_SIG, _ = _tables("stem_validation.h")
+# libstem_tail.so's optimiser pass over a table of chunk ranges (csrc/tail.hip): a launch-tape entry like stem_hip.h's, checked and
+# listed by its own library (csrc/tape_entries_tail.inc, stem_tail_entry_recordable)
+_TAIL_PROTO, _TAIL_SIG, _ = _tables("stem_tail.h")
+#: every entry point a launch tape may hold: what tape.py classifies the argument slots of a recorded call by
+_TAPE_SIG = {**_HIP_SIG, **{n: a for n, a in _TAIL_SIG.items() if not n.startswith("stem_tail_")}}
 # libstem_frameio.so's padded-frame ingest and window emit kernels (csrc/frameio.hip; not launch-tape entries either)
 _FRAMEIO_PROTO, _FRAMEIO_SIG, _ = _tables("stem_frameio.h")
 # libstem_roiio.so's recondition and ROI rasteriser kernels (csrc/roiio.hip; not launch-tape entries either)
@@ -132,6 +140,22 @@ def frameio():
     return _frameio
 
 
+def tail():
+    """libstem_tail.so (include/stem_tail.h), or raise: like libstem_hip.so it has no fallback"""
+    global _tail
+    if _tail is None:
+        if not os.path.exists(TAIL_SO):
+            raise StemLibraryError(f"{TAIL_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                                   "(hipcc --offload-arch=gfx950).  There is no fallback for the ordered optimiser tail's kernel.")
+        _tail = _bind(C.CDLL(TAIL_SO), _TAIL_PROTO)
+    return _tail
+
+
+def check_tail(rc: int):
+    if rc != 0:
+        raise RuntimeError((tail().stem_tail_last_error() or b"").decode() or f"libstem_tail error {rc}")
+
+
 def check_frameio(rc: int):
     if rc != 0:
         raise RuntimeError((frameio().stem_frameio_last_error() or b"").decode() or f"libstem_frameio error {rc}")
@@ -193,6 +217,10 @@ def declared_hip_gdn1_symbols():
 
 def declared_hip_validation_symbols():
     return sorted(_HIP_VALIDATION_SIG)
+
+
+def declared_tail_symbols():
+    return sorted(_TAIL_SIG)
 
 
 def declared_frameio_symbols():

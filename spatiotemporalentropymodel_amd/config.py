@@ -45,6 +45,7 @@ class StemRuntimeConfig:
     engine_split_pack: bool = True       #: input-gradient weight images packed on the side stream
     engine_pack_pair: bool = True        #: both images of a layer from one read of its weights (after an optimiser pass with maxima)
     engine_branch: bool = True           #: hyper path on its own stream
+    engine_tail_ordered: bool = True     #: optimiser pass + weight packing in the order the next forward first uses the layers: the forward starts after the first group
     stream_prio: str = ""                #: "latents=0,side=-1,compute=-1" (trainer.tuned_schedule installs it)
     stream_cumask: str = ""              #: "latents=block:160"
     # ---- data parallel
@@ -69,6 +70,7 @@ _ENV = {
     "layers_f16x3_maxpix": "STEM_LAYERS_F16X3_MAXPIX", "layers_wide_minpix": "STEM_LAYERS_WIDE_MINPIX",
     "adam_block_max": "STEM_ADAM_BLOCK_MAX", "trainer_overwrite_grads": "STEM_TRAINER_OVERWRITE_GRADS", "engine_overlap": "STEM_ENGINE_OVERLAP",
     "engine_split_pack": "STEM_ENGINE_SPLIT_PACK", "engine_pack_pair": "STEM_ENGINE_PACK_PAIR", "engine_branch": "STEM_ENGINE_BRANCH",
+    "engine_tail_ordered": "STEM_ENGINE_TAIL_ORDERED",
     "stream_prio": "STEM_STREAM_PRIO", "stream_cumask": "STEM_STREAM_CUMASK", "dp_min_bytes": "STEM_DP_MIN_BYTES", "dp_threaded": "STEM_DP_THREADED",
     "dist_backend": "STEM_DIST_BACKEND", "dist_single": "STEM_DIST_SINGLE", "pin_ranks": "STEM_PIN_RANKS",
     "ar_persistent": "STEM_AR_PERSISTENT", "ar_stepwise": "STEM_AR_STEPWISE",

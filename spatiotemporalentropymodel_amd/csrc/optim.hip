@@ -3,6 +3,7 @@
 // stem/trainSTEM.py:213-218 (utils.py:127-134): 41 tensors x ~6 elementwise passes become one
 // HBM-bound pass (16 B read + 12 B written per parameter).
 #include "stem_common.h"
+#include "adam_chunk.h"
 
 namespace {
 
@@ -75,48 +76,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float *p, float *g, float *m,
 // in bmax[4 * chunk .. 4 * chunk + 3] (one value per wavefront): the fp16 weight packing that follows an optimiser step (f16x3_pack.hip) takes its power-of-two scale from the
 // maxima of the chunks a tensor touches instead of a reduction pass of its own (a chunk shared with a neighbouring tensor can
 // only raise the bound).  Same arithmetic per element as adam_kernel.
+// (adam_chunk.h states the chunk's pass once, for this kernel and libstem_tail.so's kernel over a table of chunk ranges)
 __global__ __launch_bounds__(256) void adam_bmax_kernel(float *p, float *g, float *m, float *v, size_t n, const double *sumsq,
                                                         float max_norm, float gscale, float step_size, float b1, float b2,
                                                         float inv_sqrt_bc2, float eps, int zero_g, float *bmax)
 {
-    float coef = gscale;
-    if (max_norm > 0.f && sumsq) {
-        const float total = (float)sqrt(sumsq[0]) * gscale;
-        coef *= fminf(max_norm / (total + 1e-6f), 1.0f);
-    }
-    const size_t base = (size_t)blockIdx.x * STEM_ADAM_CHUNK;
-    float mx = 0.f;
-    // four elements per thread and pass, all sixteen loads issued before the first use (the pass is HBM-bound: 28 B per parameter)
-#pragma unroll 1
-    for (int k0 = 0; k0 < STEM_ADAM_CHUNK / 256; k0 += 4) {
-        float gi[4], mi[4], vi[4], pi[4];
-        size_t idx[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            idx[u] = base + (size_t)(k0 + u) * 256 + threadIdx.x;
-            const bool ok = idx[u] < n;
-            const size_t j = ok ? idx[u] : 0;
-            gi[u] = ok ? g[j] : 0.f;
-            mi[u] = ok ? m[j] : 0.f;
-            vi[u] = ok ? v[j] : 0.f;
-            pi[u] = ok ? p[j] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (idx[u] >= n) continue;
-            const float gs = gi[u] * coef;
-            if (zero_g) g[idx[u]] = 0.f;
-            const float mn = mi[u] + (gs - mi[u]) * (1.f - b1);
-            const float vn = vi[u] * b2 + (1.f - b2) * gs * gs;
-            m[idx[u]] = mn;
-            v[idx[u]] = vn;
-            const float pn = pi[u] - step_size * (mn / (sqrtf(vn) * inv_sqrt_bc2 + eps));
-            p[idx[u]] = pn;
-            mx = fmaxf(mx, fabsf(pn));
-        }
-    }
-    mx = wave_max(mx);                                         // one slot per wavefront: no barrier in an HBM-bound pass
-    if ((threadIdx.x & 63) == 0) bmax[blockIdx.x * 4 + (threadIdx.x >> 6)] = mx;
+    adam_chunk_pass(p, g, m, v, n, sumsq, max_norm, gscale, step_size, b1, b2, inv_sqrt_bc2, eps, zero_g, bmax, blockIdx.x);
 }
 
 // One thread: ++step (device-resident), then the two scalars of this step's update exactly as stem_adam_step derives them

@@ -22,10 +22,10 @@
 #include <vector>
 
 #include "stem_common.h"
+#include "tape_contract.h"                 // TAPE_MAXI, TAPE_MAXF, tape_recordable()
 
 namespace {
 
-constexpr int TAPE_MAXI = 40, TAPE_MAXF = 6;
 enum { TAPE_CALL = 0, TAPE_WAIT = 1, TAPE_EVENT_RECORD = 2, TAPE_EVENT_WAIT = 3 };
 
 struct TapeEntry {
@@ -73,23 +73,8 @@ constexpr auto make_callers(std::index_sequence<N...>) -> std::array<Caller, siz
 const auto kCallers = make_callers(std::make_index_sequence<TAPE_MAXI + 1>{});
 
 // ---- the trampolines' contract, checked per entry point at COMPILE time -----------------------------------------------------------
-// call_seq() calls f(a0, f0, a1, ...) through int(long long..., double...): that lands every argument where the callee reads it
-// only if (1) each parameter is a scalar of the INTEGER class (integers, enums, pointers; <= 8 bytes) or of the SSE class (float,
-// double) -- no struct / union / long double / vector by value, whose classification interleaves the two files --, (2) at most
-// TAPE_MAXF <= 8 SSE arguments (all in xmm0-7: none on the stack, where they would interleave with the integer overflow), and
-// (3) at most TAPE_MAXI integer ones (the trampoline table's size).  tape_entries.inc (tools/gen_tape_table.py) lists every
+// tape_recordable() (tape_contract.h) states the contract.  tape_entries.inc (tools/gen_tape_table.py) lists every
 // int-returning declaration of include/stem_hip.h; a new entry point that breaks the contract fails the build here.
-static_assert(TAPE_MAXF <= 8, "SSE arguments beyond xmm7 go to the stack and would interleave with the integer overflow area");
-template <class T>
-constexpr bool tape_int_class = (std::is_integral<T>::value || std::is_enum<T>::value || std::is_pointer<T>::value) && sizeof(T) <= 8;
-template <class T>
-constexpr bool tape_sse_class = std::is_same<T, float>::value || std::is_same<T, double>::value;
-template <class... A>
-constexpr bool tape_recordable(int (*)(A...))
-{
-    constexpr int ni = (0 + ... + (tape_int_class<A> ? 1 : 0)), nf = (0 + ... + (tape_sse_class<A> ? 1 : 0));
-    return ni + nf == (int)sizeof...(A) && ni <= TAPE_MAXI && nf <= TAPE_MAXF;
-}
 #define STEM_TAPE_ENTRY(name) \
     static_assert(tape_recordable(&name), #name ": prototype outside the launch tape's calling contract (csrc/tape.hip)");
 #include "tape_entries.inc"

@@ -89,6 +89,8 @@ class _Layer:
         self._slabs = {}
         self.pending = None       # (dwp, splits) of the last wgrad, consumed by StemEngine.unpack_all
         self.lane = 0             # which weight-gradient stream this layer's wgrad / unpack runs on (StemEngine.side_stream)
+        self.tail_event = None    # the event behind this layer's images when an ordered optimiser tail packed them off the compute stream
+        self.tail_group = 0       # ... and the group of that tail (StemEngine.tail_plan)
 
     def fx3_eligible(self):
         return self.kind == "conv" and not self.masked and _layers.f16x3_same_shape(self.stride, self.R, self.pad, self.C, self.K)
@@ -186,6 +188,8 @@ class _Layer:
         """a: _Act -> _Act of the (activated) output; `out` may be a channel slice of a wider NHWC buffer; planes: the fp16
         kernels write the output's planes next to the fp32 copy (the fp32 kernels cannot: the consumer splits)"""
         self.eng.ensure_packed()
+        if self.tail_event is not None:
+            self.eng._wait_tail(self)
         face, m = self.faces[0], self.mod
         epi = F.GEN_EPI_LRELU if act == F.ACT_LRELU else F.GEN_EPI_BIAS
         if face.kind == "gen":
@@ -207,6 +211,8 @@ class _Layer:
     def input_grad(self, dy, xact=None, planes=False, x_shape=None):
         """dy: _Act -> _Act of the gradient of the layer's input; xact: the activated input (its leaky-ReLU derivative is folded
         in); x_shape: the input's shape where there is no xact (only the fp32 kernels ask)"""
+        if self.tail_event is not None:
+            self.eng._wait_tail(self)
         face = self.faces[1]
         epi = F.GEN_EPI_DACT if xact is not None else F.GEN_EPI_BIAS
         if face.kind == "gen":            # stride 1: the mirrored weight; a ConvTranspose2d: the strided convolution of dy with the stored weight
@@ -321,6 +327,26 @@ def _attach_block_maxima(d, numel, maxima, flat, ch=None):
     return True
 
 
+def tail_chunk_ranges(tensors, numel, ch, ngroups):
+    """tensors: (offset, elements, group) of every tensor of a flat buffer of `numel` elements -> per group the list of chunk ranges
+    [c0, c1) (chunks of `ch` elements) it owns.  A chunk belongs to the earliest group of any tensor it touches (one that touches
+    none -- padding -- to group 0); the ranges of all groups together cover every chunk exactly once."""
+    nch = (numel + ch - 1) // ch
+    cgroup = [ngroups] * nch
+    for off, n, gi in tensors:
+        for c in range(off // ch, (off + max(n, 1) - 1) // ch + 1):
+            cgroup[c] = min(cgroup[c], gi)
+    out = [[] for _ in range(ngroups)]
+    c = 0
+    while c < nch:
+        gi, c1 = cgroup[c], c
+        while c1 < nch and cgroup[c1] == gi:
+            c1 += 1
+        out[0 if gi == ngroups else gi].append((c, c1))
+        c = c1
+    return out
+
+
 def _grad_of(p):
     if p.grad is None:
         owner = getattr(p, "_flat_grad_view", None)
@@ -361,6 +387,9 @@ class StemEngine:
         #: (no clearing pass, no read of the old value: 144 MB less HBM traffic per P-frame step of the big model)
         self.accumulate_grads = True
         self._events = {}
+        self._tail_cache = None             # (key, plan) of tail_plan
+        self._tail_last = None              # the last group's event of the latest ordered tail: every group is done when it is
+        self._tail_waited = set()           # (stream, group) pairs that have waited for that tail's events already
         self._select_fx3()
 
     def _select_fx3(self):
@@ -464,6 +493,7 @@ class StemEngine:
             return
         if self._weights_key() == self._pack_key:
             return
+        self._drop_tail()                 # whatever an ordered tail still holds on the weight-gradient stream comes first
         have = [l.wp_fwd if l.faces[0].kind == "f32" else l.wp6_fwd for l in self.layers]        # the forward face's copy of each layer
         if any(h is None or h.device != l.mod.weight.device for h, l in zip(have, self.layers)):
             for l in self.layers:
@@ -534,6 +564,122 @@ class StemEngine:
         F.pack_weights_f16x2_pair_multi((_lib.F16PairDesc * len(descs))(*descs))
         self._dgrad_pack_event = None
         return True
+
+    #: the optimiser tail of the fused P-frame step in the order the next forward first uses the layers (tail_plan / run_tail): the
+    #: forward starts after the first group, the rest of the optimiser pass and of the packing runs under its first kernels on the
+    #: weight-gradient stream.  STEM_ENGINE_TAIL_ORDERED=0: one optimiser pass, one pair pack, the forward behind both
+    tail_ordered = _Switch("engine_tail_ordered")
+
+    #: optional callable(): invoked with the weight-gradient stream current just before the later groups of an ordered tail are
+    #: enqueued on it (a test delays the stream there: a consumer that does not wait for its group's event then reads stale images)
+    tail_hook = None
+
+    _TailGroup = collections.namedtuple("_TailGroup", "index table descs layers event")
+
+    def _tail_order(self):
+        """the layers by first use in the forward: TPM.0 / HE.0 open it, the stride-2 hyper encoder and the temporal prior follow
+        side by side, then the hyper decoder, the context model and the entropy-parameter network.  Three groups: HE.2 / TPM.2
+        apart from HE.4 / TPM.4 (four groups: three more entries for the host in front of the next forward's first launch)
+        measured no better, 0.12 against 0.15 ms per bench step gained over the single pass"""
+        tpm = self.TPM or [None] * 3
+        groups = [[tpm[0], self.HE[0]], [self.HE[1], tpm[1], self.HE[2], tpm[2]], self.HD + [self.CTX] + self.EPM]
+        return [[l for l in g if l is not None] for g in groups]
+
+    def tail_plan(self, opt):
+        """The ordered optimiser tail for `opt` (optim.FusedClipAdam with chunk maxima), or None when it does not apply (a layer with an
+        fp32 face, a weight outside the flat buffer, more chunk ranges than a table holds): the groups of _tail_order, each one table
+        of chunk ranges for stem_adam_step_bmax_ranges and the pair-pack descriptors of its layers.  Group 0 also holds every
+        parameter that is no layer's weight (biases, the bottleneck's tensors: forward kernels read them in place).  A chunk that
+        touches tensors of several groups belongs to the EARLIEST of them, so every chunk covering a tensor is final when the
+        tensor's group packs it and its scale -- the maximum over those chunks -- is the number one whole pass leaves."""
+        flat, maxima = opt.flat, opt.block_maxima
+        if any((l.wp_fwd if l.faces[0].kind == "f32" else l.wp6_fwd) is None for l in self.layers):
+            return None
+        key = (flat.data.data_ptr(), flat.numel, maxima.data_ptr(), tuple(flat.offsets),
+               tuple((l.mod.weight.data_ptr(), l.faces, l.taps, l.wp6_fwd.data_ptr() if l.wp6_fwd is not None else 0,
+                      l.wp6_dgrad.data_ptr() if l.wp6_dgrad is not None else 0) for l in self.layers))
+        if self._tail_cache is not None and self._tail_cache[0] == key:
+            return self._tail_cache[1]
+        self._tail_cache = (key, self._build_tail_plan(flat, maxima))
+        return self._tail_cache[1]
+
+    def _build_tail_plan(self, flat, maxima, max_ranges=40):
+        ch = F.adam_chunk()
+        order = self._tail_order()
+        group_of = {id(l.mod.weight): gi for gi, g in enumerate(order) for l in g}
+        in_flat = {id(p) for p in flat.params}
+        if any(id(l.mod.weight) not in in_flat for l in self.layers):
+            return None
+        all_ranges = tail_chunk_ranges([(off, p.numel(), group_of.get(id(p), 0)) for p, off in zip(flat.params, flat.offsets)],
+                                       flat.numel, ch, len(order))
+        plan = []
+        for gi, layers in enumerate(order):
+            ranges = all_ranges[gi]
+            descs = [l.pair_desc() for l in layers]
+            if len(ranges) > max_ranges or any(d is None for d in descs):
+                return None
+            if not all(_attach_block_maxima(d, d.A * d.B * d.R * d.S, maxima, flat.data, ch) for d in descs):
+                return None
+            if not layers and not ranges:
+                continue
+            if not layers and plan:           # chunks without a layer of their own (cannot happen past group 0): to the group before
+                return None
+            plan.append(self._TailGroup(len(plan), F.adam_ranges(ranges), (_lib.F16PairDesc * len(descs))(*descs) if descs else None, layers,
+                                        self._events.setdefault(("tail", len(plan)), torch.cuda.Event())))
+        return plan
+
+    def run_tail(self, plan, adam):
+        """Issue the groups of `plan`; adam(table): the optimiser's launch over one table of chunk ranges on the current stream.
+        Group 0 runs on the current stream, the others on the weight-gradient stream behind group 0's optimiser launch (a tensor
+        of a later group may share a chunk with one of group 0), each followed by its event: _Layer.forward / input_grad wait for
+        it on their own stream before the layer's first launch of the next step."""
+        dev = self.layers[0].mod.weight.device
+        main, side = F.cur_stream(dev), self.side_stream(dev)
+        adam(plan[0].table)
+        F.stream_wait(side, main)
+        if plan[0].descs is not None:
+            F.pack_weights_f16x2_pair_multi(plan[0].descs)
+        with F.on_stream(side):
+            if self.tail_hook is not None:
+                F.tape_py(self.tail_hook)
+            for g in plan[1:]:
+                adam(g.table)
+                F.pack_weights_f16x2_pair_multi(g.descs)
+                F.event_record(g.event, side)
+        self.mark_tail(plan)
+        self._dgrad_pack_event = None
+        self._pack_key = self._weights_key()
+
+    def mark_tail(self, plan):
+        """the host-side state run_tail(plan) leaves (a launch tape that replayed one calls this: trainer.FusedPFrameStep.after_replay)"""
+        self._tail_waited.clear()
+        for l in self.layers:
+            l.tail_event = None
+        for g in plan[1:]:
+            for l in g.layers:
+                l.tail_event, l.tail_group = g.event, g.index
+        self._tail_last = plan[-1].event if len(plan) > 1 else None
+
+    def _wait_tail(self, layer):
+        """a consumer of `layer`'s images: the current stream waits for the layer's group of the ordered tail, once per stream"""
+        st = F.cur_stream()
+        key = (st.cuda_stream, layer.tail_group)
+        if key not in self._tail_waited:
+            self._tail_waited.add(key)
+            F.event_wait(st, layer.tail_event)
+
+    def join_tail(self):
+        """order the current stream after every group of the latest ordered tail (a reader or writer of the parameters themselves)"""
+        if self._tail_last is not None:
+            F.event_wait(F.cur_stream(), self._tail_last)
+
+    def _drop_tail(self):
+        """the images are about to be packed another way: the current stream goes behind the ordered tail, whose events retire"""
+        self.join_tail()
+        self._tail_last = None
+        self._tail_waited.clear()
+        for l in self.layers:
+            l.tail_event = None
 
     def unpack_all(self):
         for lane in sorted({l.lane for l in self.layers}):

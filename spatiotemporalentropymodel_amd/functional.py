@@ -1903,6 +1903,19 @@ def adam_step_bmax(p, g, m, v, sumsq_acc, max_norm, gscale, lr, beta1, beta2, ep
                                         max_norm, gscale, lr, beta1, beta2, eps, step, int(bool(zero_grad)), bmax.data_ptr(), _stream()))
 
 
+def adam_ranges(ranges):
+    """[(c0, c1), ...] chunk ranges -> the host table adam_step_bmax_ranges takes (a ctypes array: a launch tape keeps it alive)"""
+    flat = [int(c) for r in ranges for c in r]
+    return (C.c_int * len(flat))(*flat)
+
+
+def adam_step_bmax_ranges(p, g, m, v, sumsq_acc, max_norm, gscale, lr, beta1, beta2, eps, step, bmax, table, zero_grad=False):
+    """adam_step_bmax over the chunks of `table` (adam_ranges(...)) only, on the current stream"""
+    _lib.check_tail(_lib.tail().stem_adam_step_bmax_ranges(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), _ptr(sumsq_acc),
+                                                           max_norm, gscale, lr, beta1, beta2, eps, step, int(bool(zero_grad)),
+                                                           bmax.data_ptr(), table, len(table) // 2, _stream()))
+
+
 def adam_chunk():
     return int(_lib.hip().stem_adam_chunk())
 

@@ -161,9 +161,7 @@ class FusedClipAdam(torch.optim.Optimizer):
                             float(self.max_norm) if use_clip else 0.0, float(grad_scale), d["lr"], g["betas"][0], g["betas"][1],
                             float(g["eps"]), d["step"], d["scal"])
         elif block_max:
-            if getattr(self, "block_maxima", None) is None:
-                ch = F.adam_chunk()
-                self.block_maxima = torch.empty(4 * ((self.flat.data.numel() + ch - 1) // ch), device=self.flat.data.device, dtype=torch.float32)
+            self.ensure_block_maxima()
             F.adam_step_bmax(self.flat.data, self.flat.grad, self.m, self.v, self._sumsq if use_clip else None,
                              float(self.max_norm) if use_clip else 0.0, float(grad_scale), float(g["lr"]), g["betas"][0], g["betas"][1],
                              float(g["eps"]), self.t, self.block_maxima, zero_grad=zero_grad)
@@ -179,6 +177,35 @@ class FusedClipAdam(torch.optim.Optimizer):
                                         float(g["betas"][1]), float(g["eps"])))
         bump_weight_epoch(self.flat.params)
         return loss
+
+    def ensure_block_maxima(self):
+        if getattr(self, "block_maxima", None) is None:
+            ch = F.adam_chunk()
+            self.block_maxima = torch.empty(4 * ((self.flat.data.numel() + ch - 1) // ch), device=self.flat.data.device, dtype=torch.float32)
+        return self.block_maxima
+
+    def begin_ranges(self, grad_scale: float = 1.0):
+        """step(block_max=True, norm_is_current=True) in pieces: this call counts the step, every step_ranges(table, ...) that
+        follows updates the chunks of one table of ranges (F.adam_ranges) on the stream that is current THEN.  The tables of one
+        step must cover every chunk exactly once; the caller orders the launches after the gradient norm and each reader of a
+        parameter after the launch that updates it (engine.StemEngine.run_tail).  Host-resident state only."""
+        assert self._dev is None, "begin_ranges: the step count lives in device memory (enable_device_state)"
+        join_wgrad_stream()
+        self.t += 1
+        self.ensure_block_maxima()
+        bump_weight_epoch(self.flat.params)
+        g, gs = self.param_groups[0], float(grad_scale)
+        use_clip = self.max_norm is not None and self.max_norm > 0
+        # ONE provider for the launches of this step: a launch tape reads it again at every replay, as for step(), and knows the
+        # launches that share it as one optimiser step (tape.LaunchTape.bind_floats)
+        self._ranges_floats = (use_clip, lambda: (float(self.max_norm) if use_clip else 0.0, gs, float(g["lr"]), float(g["betas"][0]),
+                                                  float(g["betas"][1]), float(g["eps"])))
+
+    def step_ranges(self, table, zero_grad: bool = False):
+        use_clip, floats = self._ranges_floats
+        F.adam_step_bmax_ranges(self.flat.data, self.flat.grad, self.m, self.v, self._sumsq if use_clip else None, *floats(), self.t,
+                                self.block_maxima, table, zero_grad=zero_grad)
+        F.tape_bind_floats(floats)
 
     # ---- torch.optim.Adam-compatible (de)serialisation ----------------------------------------------------------
     def _views(self, buf):

@@ -66,17 +66,20 @@ class LaunchTape:
         self.foreign = []           # torch operators on device memory seen by the recording's guard (a replay would drop them)
         self.problems = []          # calls that could not be recorded
         self.float_bindings = {}    # entry index -> provider() of that call's float arguments (functional.tape_bind_floats)
+        self.float_followers = {}   # entry index -> the entry in float_bindings whose provider this call shares (one optimiser step in several launches)
         self._bound_now = {}        # entry index -> the patterns the native tape holds now
         self._native = None
         self._segments = None
 
     # ---- recording ---------------------------------------------------------------------------------------------------------------
     def add_call(self, name, fn, args):
-        sig = _lib._HIP_SIG[name]
+        sig = _lib._TAPE_SIG[name]
         addr = C.cast(fn, C.c_void_p).value
         # the call itself has already run (the step goes on whatever happens here): what cannot be recorded is noted and makes
         # finalize() refuse the tape
-        if not _lib.hip().stem_tape_entry_recordable(addr):
+        known = (_lib.tail().stem_tail_entry_recordable(addr) if name in _lib._TAIL_SIG      # each library answers for its own entry points
+                 else _lib.hip().stem_tape_entry_recordable(addr))
+        if not known:
             self.problems.append(f"{name} is not in the library's table of recordable entry points (csrc/tape_entries.inc)")
             return
         if len(args) != len(sig):
@@ -110,18 +113,28 @@ class LaunchTape:
         nf = sum(1 for k in self.entries[i][3] if k != 0)
         if len(provider()) != nf:
             raise RuntimeError(f"tape_bind_floats: {self.entries[i][1]} has {nf} float arguments, the provider returns {len(provider())}")
+        for j, other in self.float_bindings.items():
+            if other is provider:       # the same provider again: a further launch of the step that bound it
+                self.float_followers[i] = j
+                return
         self.float_bindings[i] = provider
+
+    def _provider(self, i):
+        return self.float_bindings[self.float_followers.get(i, i)]
+
+    def _bound_entries(self):
+        return list(self.float_bindings) + list(self.float_followers)
 
     def _float_patterns(self, i):
         x = self.entries[i]
-        sig = _lib._HIP_SIG[x[1]]
+        sig = _lib._TAPE_SIG[x[1]]
         ftys = [ty for ty in sig if ty is C.c_float or ty is C.c_double]
-        return [_pattern(ty, v) for ty, v in zip(ftys, self.float_bindings[i]())]
+        return [_pattern(ty, v) for ty, v in zip(ftys, self._provider(i)())]
 
     def refresh_floats(self):
         """bound float arguments whose provider moved since the last replay -> patched into the native tape; returns how many"""
         lib, n = _lib.hip(), 0
-        for i in self.float_bindings:
+        for i in self._bound_entries():
             now = self._float_patterns(i)
             old = self._bound_now[i]
             if now != old and [struct.pack("<d", v) for v in now] != [struct.pack("<d", v) for v in old]:
@@ -144,7 +157,7 @@ class LaunchTape:
         if self.foreign or second.foreign:
             ops = sorted(set(self.foreign + second.foreign))
             raise TapeRefused("LaunchTape: the step runs torch operators on device memory that a replay would drop: " + ", ".join(ops))
-        if set(self.float_bindings) != set(second.float_bindings):
+        if set(self.float_bindings) != set(second.float_bindings) or self.float_followers != second.float_followers:
             raise TapeRefused("LaunchTape: the two recordings bound different launches to float providers")
         lib = _lib.hip()
         nat = lib.stem_tape_create()
@@ -171,7 +184,7 @@ class LaunchTape:
                 _, name, addr, kinds, iv, fv, _keep, isptr = x
                 self.native_index.append(lib.stem_tape_length(nat))
                 deltas = [0] * len(iv)
-                bound = ei in self.float_bindings
+                bound = ei in self.float_bindings or ei in self.float_followers
                 if bound:                       # the provider is the source of truth from here on (it may have moved since step A)
                     cur = self._float_patterns(ei)
                     self._bound_now[ei] = cur
@@ -254,8 +267,8 @@ class _RecordingLibrary:
         if w is not None:
             return w
         fn = getattr(self._lib, name)
-        if (name not in _lib._HIP_SIG or name in _lib._RESTYPE or name.startswith("stem_tape_") or name.startswith("stem_tuning")
-                or name.startswith("stem_stream_flag_")):
+        if (name not in _lib._TAPE_SIG or name in _lib._RESTYPE or name.startswith("stem_tape_") or name.startswith("stem_tuning")
+                or name.startswith("stem_stream_flag_") or name.startswith("stem_tail_")):
             # size queries, error strings, the tape API itself: not part of a schedule.  Stream flags carry a step counter and are
             # written by the data-parallel helper THREAD (distributed._CollectiveIssuer): they belong to the reducer's Python
             # entries, which a replay calls again
@@ -316,6 +329,8 @@ class recording:
             raise RuntimeError("a launch tape is already recording")
         self._real = _lib.hip()
         _lib._hip = _RecordingLibrary(self._real, self.tape)
+        self._real_tail = _lib.tail()
+        _lib._tail = _RecordingLibrary(self._real_tail, self.tape)
         F._TAPE = self.tape
         self._guard = _ForeignOpGuard(self.tape)
         self._guard.__enter__()
@@ -343,6 +358,7 @@ class recording:
     def __exit__(self, *exc):
         self._guard.__exit__(*exc)
         _lib._hip = self._real
+        _lib._tail = self._real_tail
         F._TAPE = None
         for n, real in self._saved.items():
             setattr(torch, n, real)
@@ -395,7 +411,7 @@ class TapedPFrameStep:
         clip = tuple(bool(o.max_norm is not None and o.max_norm > 0) for o in (f.opt, f.aux_opt))
         return (tuple(y_cur.shape), tuple(y_cond.shape), tuple(y_cur.stride()), tuple(y_cond.stride()), y_cur.dtype, y_cond.dtype, y_cur.device,
                 int(num_pixels), float(grad_scale), id(reducer), F.cur_stream(y_cur.device).cuda_stream, clip, bool(f.clear_grad_in_adam),
-                bool(f.adam_block_max), bool(f.overwrite_grads))
+                bool(f.adam_block_max), bool(f.overwrite_grads), bool(f.eng.tail_ordered))
 
     def step(self, y_cur, y_cond, num_pixels, grad_scale=1.0, reducer=None):
         key = self._key(y_cur, y_cond, num_pixels, grad_scale, reducer)
@@ -500,6 +516,7 @@ class TapedPFrameStep:
         them; a write since then (a checkpoint load) still shows in the key and is packed."""
         if self.tape is not None and self.replays > 1:
             self.fused.eng._pack_key = self._weights_key
+        self.fused.eng.join_tail()           # an ordered tail's later groups may still be updating the parameters
 
     def finish(self):
         self.fused.finish()

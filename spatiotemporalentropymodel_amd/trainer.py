@@ -195,7 +195,8 @@ class FusedPFrameStep:
         # = the four hardware queues of that priority; with a fifth the one-rank RCCL run took 14.86 instead of 14.69 ms per step)
         self._aux_stream = self.eng.side_stream(eb.quantiles.device) or F.make_stream(eb.quantiles.device, "side")
         self._aux_pending = False
-        self._done_event = torch.cuda.Event()            # re-recorded every step: the LazyScalars of the LATEST step wait on it
+        self._tail_plan = None            # the ordered optimiser tail of the latest ordinary step (engine.StemEngine.tail_plan), or None
+        self._done_event = torch.cuda.Event()           # re-recorded every step: the LazyScalars of the LATEST step wait on it
 
     def step(self, y_cur, y_cond, num_pixels, grad_scale=1.0, reducer=None):
         """y_cur / y_cond: the frame's and the conditioning latents [B,C,h,w]; num_pixels = N*H*W of the FRAMES (EMLoss
@@ -227,7 +228,19 @@ class FusedPFrameStep:
         F.sumsq(opt.flat.grad, opt._sumsq, overwrite=True)
         clean = opt._dev is None and self.clear_grad_in_adam and not overwrite
         use_bmax = opt._dev is None and eng.use_fx3 and self.adam_block_max
-        opt.step(grad_scale=grad_scale, norm_is_current=True, zero_grad=clean, block_max=use_bmax)
+        # the tail in first-use order: the next forward's first kernels need TPM.0 / HE.0 (and the small tensors kernels read in
+        # place) only -- that group runs here, the others on the auxiliary stream under the forward (engine.StemEngine.run_tail)
+        plan = None
+        if (use_bmax and eng.tail_ordered and eng.pack_pair and eng.side_stream(main.device) is self._aux_stream
+                and not torch.cuda.is_current_stream_capturing()):
+            opt.ensure_block_maxima()
+            plan = eng.tail_plan(opt)
+        self._tail_plan = plan
+        if plan is not None:
+            opt.begin_ranges(grad_scale)
+            eng.run_tail(plan, lambda table: opt.step_ranges(table, zero_grad=clean))
+        else:
+            opt.step(grad_scale=grad_scale, norm_is_current=True, zero_grad=clean, block_max=use_bmax)
         self._grad_clean = clean
         # auxiliary loss on the UPDATED parameters (stem/trainSTEM.py:216-218); its gradient goes straight into the aux
         # optimiser's flat buffer (the only aux parameter is `entropy_bottleneck.quantiles`).  One workgroup of latency-bound
@@ -258,10 +271,13 @@ class FusedPFrameStep:
         from .layers import bump_weight_epoch
         bump_weight_epoch(self.opt.flat.params)
         self._aux_pending = True
+        if self._tail_plan is not None:          # the replay recorded the events of its ordered tail again: nobody has waited for these
+            self.eng.mark_tail(self._tail_plan)
 
     def finish(self):
         """order everything the step left on its auxiliary stream before the current stream (end of training, checkpointing,
-        evaluation: anything that reads `entropy_bottleneck.quantiles` or the aux optimiser's state)"""
+        evaluation: anything that reads `entropy_bottleneck.quantiles` or the aux optimiser's state -- or the parameters themselves:
+        the later groups of an ordered optimiser tail run on that stream)"""
         if self._aux_pending:
             F.stream_wait(F.cur_stream(self._aux_loss.device), self._aux_stream)
             self._aux_pending = False
