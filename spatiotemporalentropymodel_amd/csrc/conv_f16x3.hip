@@ -14,9 +14,15 @@
 //
 // Tile: 128 pixels x 192 channels per workgroup, 8 wavefronts as 4 (M) x 2 (N), each 32 x 96 = three 32x32 accumulators;
 // K chunk = one tap x 32 input channels = 2 k-steps x 3 tiles x 3 products = 18 MFMAs per wavefront.  LDS rows are 64 B
-// (32 fp16) per plane with the 16-byte piece index XOR-swizzled by (row >> 2) & 3: ds_read_b128 / ds_write_b128 are
-// conflict-free without padding.  Staging is register-based, two chunks ahead, woven between the MFMA groups as in igemm.hip;
-// with three LDS stages (DEPTH 3) the next k-step's fragments are read and the stores issued between the MFMAs of the current one.
+// (32 fp16) per plane with the 16-byte piece index XOR-swizzled by (row >> 2) & 3: ds_read_b128 is conflict-free without
+// padding.  The ring is filled by LDS-DMA (global -> LDS, no vector registers; "LDS-DMA" below): the packed weight chunk IS the
+// LDS image and is copied linearly, an activation row's swizzle is applied on the source side (the lane at LDS slot s fetches piece
+// s ^ ((row >> 2) & 3) of its pixel), taps outside the image and rows beyond M read as zeros through an offset the buffer view
+// rejects.  With three LDS stages (DEPTH 3) a copy has two chunks' time to land: the step of chunk c reads the second k-step of
+// chunk c, waits (counted vmcnt: all but the youngest chunk's copies) and meets the barrier in its middle, then issues the copy
+// of chunk c + 3 into the stage chunk c released, between the MFMAs of its second half, which also carry the reads of chunk
+// c + 1's first k-step.  With two stages (DEPTH 2, and the general kernel below) the copy of chunk c + 1 is issued at the top of
+// chunk c and has landed at the barrier that ends it.  Every reuse of the ring behind the loop waits for the copies still in flight.
 // The same products are also instantiated on v_mfma_f32_16x16x32_f16 (MS 16: one k-step per chunk, twice the instructions of
 // half the size, a permuted accumulator layout that keeps ds_read_b128 conflict-free on the same LDS image): equal or slower
 // alone, faster on a loaded, power-limited chip -- which is where these kernels run.
@@ -96,10 +102,12 @@ struct Fx3Args {
 
 
 // BM = pixels per workgroup: 128 (8 wavefronts) or 64 (4 wavefronts, for layers with too few 128-pixel tiles to fill the chip).
-// DEPTH 2: two LDS stages, two chunks in flight in registers; the fragments of a 16-channel step are read right before its MFMAs.
-// DEPTH 3: three LDS stages -- chunk c + 2 is written while chunk c is multiplied, so the fragments of the NEXT 16-channel step
-//          (the first one of chunk c + 1 included) are read and the LDS stores issued between the MFMAs of the current one; only
-//          the barrier itself is left between two chunks.  120 KB of LDS with 128-pixel tiles (one workgroup per CU either way).
+// DEPTH 2: two LDS stages, the copy of chunk c + 1 in flight while chunk c is multiplied; the fragments of a 16-channel step are
+//          read right before its MFMAs.
+// DEPTH 3: three LDS stages -- chunks c + 1 (landed) and c + 2 (in flight) are in the ring while chunk c is multiplied, and the
+//          copy of chunk c + 3 is issued in the second half of chunk c's step; the fragments of the NEXT 16-channel step (the first
+//          one of chunk c + 1 included) are read between the MFMAs of the current one; only the wait and the barrier are left
+//          between the two halves.  120 KB of LDS with 128-pixel tiles (one workgroup per CU either way).
 // MS = rows of the MFMA shape: 32 (v_mfma_f32_32x32x16_f16) or 16 (v_mfma_f32_16x16x32_f16, three-stage loop only): the same
 //      operands, LDS traffic and flop in twice as many instructions of half the size, which the chip runs at a higher clock where a
 //      launch fills it and sits at the power limit (g_a.2: -6 %); smaller launches lose with it (more issue slots), so it is a
@@ -108,17 +116,45 @@ struct Fx3Args {
 //      channels 16 nj + 4 PI[(l & 15) >> 2] + (l & 3) and pixel rows 16 mi + 4 PI[l >> 4] + i of the wavefront's 32 x 96 tile.
 __device__ inline int pi4(int x) { return (0x78 >> (2 * x)) & 3; }
 
+// LDS-DMA: the ring of both kernels is filled global -> LDS without a pass through the vector registers.  One instruction
+// copies 1 KiB per wavefront: lane l's 16 bytes at (voff, soff) of the buffer view land at LDS byte lds_base + 16 l; an offset
+// the view rejects (OOR) lands as zeros.  Issued as inline assembly, as in wgrad_f16x3.hip: the compiler orders every LDS read
+// after ALL pending LDS-DMA it knows of, which would collapse the look-ahead; the ring is kept consistent by counted
+// s_waitcnt vmcnt + barrier instead (LDS-DMA retires in issue order).  Vector-memory instructions of the compiler's own that
+// are still pending only make a counted wait stricter.  M0 is reserved (not allocatable, not declarable as a clobber); these
+// kernels have no other user of it.
+typedef int rsrc4 __attribute__((ext_vector_type(4)));
+__device__ inline rsrc4 dma_rsrc(const void *p, int bytes)
+{
+    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+    return rsrc4{(int)(unsigned)v, (int)(unsigned)(v >> 32), bytes, 0x00020000};
+}
+__device__ inline void dma16(const rsrc4 r, unsigned lds_base, int voff, int soff)
+{
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_base), "v"(voff), "s"(r), "s"(soff) : "memory");
+}
+#define DMA_WAIT_BARRIER(n) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(n) : "memory")
+// every LDS read of this wavefront has returned: as a builtin between two scheduling fences, so that the compiler's own
+// wait-count pass knows it (conv_f16x3_img.hip)
+#define LDS_READS_DONE()                            \
+    do {                                            \
+        __builtin_amdgcn_sched_barrier(0);          \
+        __builtin_amdgcn_s_waitcnt(0xC07F);         \
+        __builtin_amdgcn_sched_barrier(0);          \
+    } while (0)
+
 template <int BM, int DEPTH, int MS>
 __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
 {
     static_assert(DEPTH == 2 || DEPTH == 3, "two or three LDS stages");
     static_assert(MS == 32 || (MS == 16 && DEPTH == 3), "the 16-row MFMA shape exists for the three-stage loop");
-    constexpr int NSET = 2;                             // register sets (chunks on their way to LDS)
     constexpr int NT = BM * 4;
     constexpr int A_PLANE = BM * 64, A_BUF = NPL * A_PLANE;
     constexpr int PL = NPL;
-    constexpr int WPIECES = PL * BN * 4;                // 16-byte pieces of the weight chunk that are read
-    constexpr int BP = (WPIECES + NT - 1) / NT;         // ... per thread
+    constexpr int WPIECES = PL * BN * 4;                // 16-byte pieces of the weight chunk
+    static_assert(WPIECES % NT == 0, "every wavefront copies whole 1 KiB pieces of the weight chunk");
+    constexpr int BP = WPIECES / NT;                    // ... per thread = LDS-DMA instructions per wavefront
+    constexpr int NI = PL + BP;                         // LDS-DMA instructions per wavefront and chunk
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NST = lds_stages(DEPTH);
     unsigned char *As = smem;                       // [NST][NPL][BM][64 B]
@@ -134,8 +170,10 @@ __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
     const int bm0 = tile_m * BM;
     const int nslab = a.C / KC, pixbytes = nslab * SLAB;
 
-    // ---- staging assignment.  Activations: thread -> (row = tid / 4, 16-byte column = tid % 4) of all three planes ---------
-    const int srow = tid >> 2, scol = tid & 3;
+    // ---- staging assignment.  Activations: thread -> (row = tid / 4, 16-byte LDS slot = tid % 4) of both planes: wavefront w's
+    // 1 KiB of a plane is rows 16 w .. 16 w + 15, lane-linear.  The image's XOR swizzle permutes the pieces inside a row, so the
+    // lane at slot s fetches piece s ^ ((row >> 2) & 3) of its pixel ------------------------------------------------------------
+    const int srow = tid >> 2, scol = (tid & 3) ^ ((srow >> 2) & 3);
     int pb;
     unsigned pmask = 0;
     {
@@ -150,36 +188,31 @@ __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
             if (ok && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) pmask |= 1u << t;
         }
     }
-    const int a_st = srow * 64 + ((scol ^ ((srow >> 2) & 3)) << 4);          // LDS byte offset inside a plane
-    // weights: the chunk image is copied linearly, 16 bytes per thread and pass; the last pass may be partial
-    constexpr int WFULL = WPIECES / NT;                 // full passes
-    const int wv0 = tid * 16, wvl = WFULL * NT + tid < WPIECES ? (WFULL * NT + tid) * 16 : OOR;
+    // weights: the chunk image is copied linearly, pass j = bytes [j NT 16, (j + 1) NT 16), wavefront w its 1 KiB of each pass
+    const int wv0 = tid * 16;
     const int nchunks = a.ntaps * nslab;
     const int q_last = nchunks - 1;
     __syncthreads();
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.xp), 0, a.xbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.wp), 0, a.wbytes, 0x00020000);
-
-    f32x4 rsa[NSET][PL], rsb[NSET][BP];         // register set s holds a chunk on its way to LDS
-    auto gload = [&](int t, int tA, int kc, int q, f32x4 (&ra)[PL], f32x4 (&rb)[BP]) {
+    const rsrc4 rx = dma_rsrc(a.xp, a.xbytes), rw = dma_rsrc(a.wp, a.wbytes);
+    const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char *)smem;
+    const unsigned ldsw = __builtin_amdgcn_readfirstlane(lds0 + wave * 1024);       // this wavefront's 1 KiB inside a piece group
+    // chunk q = (tap t at byte offset tA, slab kc) -> LDS stage `stage`: NI instructions per wavefront, the planes first;
+    // dma_range issues instructions [lo, hi) of them
+    auto dma_range = [&](int stage, int t, int tA, int kc, int q, int lo, int hi) {
         const int sA = kc * SLAB, sB = q * B_BUF;
         const int mk = __builtin_amdgcn_sbfe((int)pmask, (unsigned)t, 1u);                 // 0 / -1: tap t inside the image
         const int off = ((pb + tA) & mk) | (OOR & ~mk);
+        const unsigned la = ldsw + stage * A_BUF, lb = ldsw + NST * A_BUF + stage * B_BUF;
 #pragma unroll
-        for (int pl = 0; pl < PL; ++pl) ra[pl] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, off + pl * 64, sA, 0));
-#pragma unroll
-        for (int j = 0; j < WFULL; ++j)
-            rb[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, wv0 + j * (NT * 16), sB, 0));
-        if (BP > WFULL) rb[BP - 1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, wvl, sB, 0));
+        for (int i = lo; i < hi; ++i) {
+            if (i < PL)
+                dma16(rx, la + i * A_PLANE, off + i * 64, sA);
+            else
+                dma16(rw, lb + (i - PL) * (NT * 16), wv0 + (i - PL) * (NT * 16), sB);
+        }
     };
-    auto sstore = [&](int buf, f32x4 (&ra)[PL], f32x4 (&rb)[BP]) {
-#pragma unroll
-        for (int pl = 0; pl < PL; ++pl) *reinterpret_cast<f32x4 *>(As + buf * A_BUF + pl * A_PLANE + a_st) = ra[pl];
-#pragma unroll
-        for (int j = 0; j < WFULL; ++j) *reinterpret_cast<f32x4 *>(Bs + buf * B_BUF + j * (NT * 16) + tid * 16) = rb[j];
-        if (BP > WFULL && WFULL * NT + tid < WPIECES) *reinterpret_cast<f32x4 *>(Bs + buf * B_BUF + (WFULL * NT + tid) * 16) = rb[BP - 1];
-    };
+    auto dma = [&](int stage, int t, int tA, int kc, int q) { dma_range(stage, t, tA, kc, q, 0, NI); };
 
     // ---- wave tile -----------------------------------------------------------------------------------------------------
     const int wm0 = (wave >> 1) * 32, wn0 = (wave & 1) * 96;
@@ -204,10 +237,13 @@ __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
     // registers (pf_ts = t % S): a table lookup in LDS would drain the wavefront's LDS queue in the middle of the woven block.
     int pf_q = 0, pf_t = 0, pf_kc = 0, pf_ts = 0, pf_to = 0;
     const int tw_T = a.ntaps, tw_S = a.S, tw_col = pixbytes, tw_line = a.W * pixbytes, tw_first = (a.dy[0] * a.W + a.dx[0]) * pixbytes;
-    auto step = [&](int cur, f32x4 (&ra)[PL], f32x4 (&rb)[BP]) {
+    // DEPTH 2: chunk c + 1 is copied into the other stage (free since the barrier that ended chunk c - 1) while chunk c is
+    // multiplied; it has landed, for every wavefront, behind the wait and the barrier that end the step
+    auto step = [&](int cur) {
         const unsigned char *Ab = As + cur * A_BUF + rdA, *Bb = Bs + cur * B_BUF + rdB;
         const int t = __builtin_amdgcn_readfirstlane(pf_t), kc = __builtin_amdgcn_readfirstlane(pf_kc), q = __builtin_amdgcn_readfirstlane(pf_q);
         const int to = __builtin_amdgcn_readfirstlane(pf_to);
+        dma(cur ^ 1, t, to, kc, q);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const int pk = ks ? pk1 : pk0;
@@ -224,12 +260,9 @@ __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
                 acc[j] = STEM_MFMA16(af[0], bf[1][j], acc[j]);
                 acc[j] = STEM_MFMA16(af[0], bf[0][j], acc[j]);
             }
-            if (ks == 0)
-                sstore(cur ^ 1, ra, rb);           // the register set holds the next chunk
-            else
-                gload(t, to, kc, q, ra, rb);       // refill it two chunks ahead
         }
         if (pf_q < q_last) TAP_WALK_NEXT();
+        DMA_WAIT_BARRIER(0);
     };
     // DEPTH 3: F0 holds the fragments of (stage rd, channels 0..15) on entry and of (stage nx, channels 0..15) on exit
     h16x8 f0a[PL], f0b[PL][3], f1a[PL], f1b[PL][3];
@@ -253,38 +286,45 @@ __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
             acc[j] = STEM_MFMA16(af[0], bf[0][j], acc[j]);
         }
     };
-    auto step3 = [&](int rd, int nx, int wr, f32x4 (&ra)[PL], f32x4 (&rb)[BP]) {
+    // The three stages hold chunks c (rd), c + 1 (nx) and c + 2 (in flight).  The step of chunk c:
+    //   X: MFMAs (c, 0)  +  reads (c, 1)
+    //      wait: this wavefront's reads of chunk c are done, its share of chunk c + 1 has landed (all but the youngest chunk's
+    //      NI instructions); barrier: everybody's
+    //   Y: copy of chunk c + 3 into the stage chunk c has just released, MFMAs (c, 1)  +  reads (c + 1, 0)
+    // so a copy has two chunks' time to land.  Beyond the last chunk the copy re-fetches the last chunk into a free stage and the
+    // look-ahead reads fetch fragments nobody multiplies: vmcnt(NI) always means "everything but the youngest chunk".
+    auto step3 = [&](int rd, int nx) {
         const int t = __builtin_amdgcn_readfirstlane(pf_t), kc = __builtin_amdgcn_readfirstlane(pf_kc), q = __builtin_amdgcn_readfirstlane(pf_q);
         const int to = __builtin_amdgcn_readfirstlane(pf_to);
         lfrag(rd, pk1, f1a, f1b);
         mfma9(f0a, f0b);
-        sstore(wr, ra, rb);
-        lfrag(nx, pk0, f0a, f0b);
-        mfma9(f1a, f1b);
-        gload(t, to, kc, q, ra, rb);
-        // issue order: one LDS read behind each MFMA of the first half; the stores, then the reads, behind those of the second
+        // issue order: one LDS read behind each of the first eight MFMAs
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         }
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        constexpr int NW = PL + BP;                                  // LDS stores per thread and chunk
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x200, (NW + 3) / 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x200, (NW + 2) / 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x200, (NW + 1) / 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x200, NW / 4, 0);
+        LDS_READS_DONE();
+        DMA_WAIT_BARRIER(NI);
+        // Y: one of the copy's NI <= 8 instructions and one read in front of each of the first eight MFMAs -- every wavefront leaves
+        // the barrier at the same moment, and NI copies in a row from each of them would queue in front of the MFMAs
+        static_assert(NI <= 8, "one copy instruction per MFMA of the second half");
+        const unsigned char *Ab = As + nx * A_BUF + rdA + pk0, *Bb = Bs + nx * B_BUF + rdB + pk0;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < 9; ++i) {
+            const int j = i / 3, k = i % 3;            // mfma9's order
+            if (i < NI) dma_range(rd, t, to, kc, q, i, i + 1);
+            if (i == 0) f0a[1] = *reinterpret_cast<const h16x8 *>(Ab + A_PLANE);        // lfrag's order
+            if (i == 1) f0b[0][0] = *reinterpret_cast<const h16x8 *>(Bb);
+            if (i == 2) f0a[0] = *reinterpret_cast<const h16x8 *>(Ab);
+            if (i == 3) f0b[1][0] = *reinterpret_cast<const h16x8 *>(Bb + B_PLANE);
+            if (i >= 4 && i < 8) f0b[i & 1][(i - 2) >> 1] = *reinterpret_cast<const h16x8 *>(Bb + (i & 1) * B_PLANE + ((i - 2) >> 1) * 32 * 64);
+            acc[j] = STEM_MFMA16(k == 0 ? f1a[1] : f1a[0], k == 1 ? f1b[1][j] : f1b[0][j], acc[j]);
+            if (i < 8) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
         }
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, PL + BP, 0);
+        LDS_READS_DONE();          // said here, so that the wait-count pass does not drain the NEXT step's reads in front of its MFMAs
         if (pf_q < q_last) TAP_WALK_NEXT();
     };
 
@@ -322,37 +362,49 @@ __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
                     d[mi][half * 3 + n3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[mi][prod == 0 ? 1 : 0], B[n3][prod == 1 ? 1 : 0],
                                                                                    d[mi][half * 3 + n3], 0, 0, 0);
     };
-    auto step3_16 = [&](int rd, int nx, int wr, f32x4 (&ra)[PL], f32x4 (&rb)[BP], h16x8 (&Acur)[2][PL], h16x8 (&Anext)[2][PL]) {
+    // the X / wait + barrier / Y form of step3: X = first half's 18 MFMAs + the 6 reads of the second half's weights, Y = the copy
+    // of chunk c + 3, the second half's 18 MFMAs + the 10 reads of chunk c + 1's pixels and first-half weights
+    auto step3_16 = [&](int rd, int nx, h16x8 (&Acur)[2][PL], h16x8 (&Anext)[2][PL]) {
         const int t = __builtin_amdgcn_readfirstlane(pf_t), kc = __builtin_amdgcn_readfirstlane(pf_kc), q = __builtin_amdgcn_readfirstlane(pf_q);
         const int to = __builtin_amdgcn_readfirstlane(pf_to);
         lfragB16(Bs + rd * B_BUF, 1, gb1);
         mma18(Acur, gb0, 0, a16);
-        sstore(wr, ra, rb);
-        lfragA16(As + nx * A_BUF, Anext);
-        lfragB16(Bs + nx * B_BUF, 0, gb0);
-        mma18(Acur, gb1, 1, a16);
-        gload(t, to, kc, q, ra, rb);
-        // issue order: 18 MFMAs + 6 LDS reads, then 18 MFMAs + the stores + 10 reads, the global loads last
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         }
-        constexpr int NW = PL + BP;
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x200, (NW + 3) / 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x200, (NW + 2) / 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x200, (NW + 1) / 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x200, NW / 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+        LDS_READS_DONE();
+        DMA_WAIT_BARRIER(NI);
+        // Y in five groups of (a share of the copy's instructions, 3 / 3 / 2 / 2 / 0 reads, 4 or 3 MFMAs): every wavefront leaves
+        // the barrier at the same moment, and NI copies in a row from each of them would queue in front of the MFMAs
+        auto ygroup = [&](auto group_tag) {
+            constexpr int g = decltype(group_tag)::value;
+            constexpr int r0 = g < 2 ? 3 * g : g < 4 ? 2 * g + 2 : 10, r1 = g < 1 ? 3 : g < 3 ? 2 * g + 4 : 10;
+            constexpr int m0 = (g * 18 + 4) / 5, m1 = ((g + 1) * 18 + 4) / 5;
+            dma_range(rd, t, to, kc, q, (g * NI + 4) / 5, ((g + 1) * NI + 4) / 5);
 #pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x020, PL + BP, 0);
+            for (int r = r0; r < r1; ++r) {                                         // lfragA16's, then lfragB16's order
+                if (r < 4)
+                    Anext[r >> 1][r & 1] = *reinterpret_cast<const h16x8 *>(As + nx * A_BUF + rdA16 + (r >> 1) * 16 * 64 + (r & 1) * A_PLANE);
+                else
+                    gb0[(r - 4) >> 1][r & 1] = *reinterpret_cast<const h16x8 *>(Bs + nx * B_BUF + rdB16 + ((r - 4) >> 1) * 16 * 64 + (r & 1) * B_PLANE);
+            }
+#pragma unroll
+            for (int m = m0; m < m1; ++m) {                                         // mma18's order: product, channel block, pixel block
+                const int prod = m / 6, n3 = (m % 6) >> 1, mi = m & 1;
+                a16[mi][3 + n3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Acur[mi][prod == 0 ? 1 : 0], gb1[n3][prod == 1 ? 1 : 0], a16[mi][3 + n3], 0, 0, 0);
+            }
+            if constexpr (r1 > r0) __builtin_amdgcn_sched_group_barrier(0x100, r1 - r0, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, m1 - m0, 0);
+        };
+        ygroup(std::integral_constant<int, 0>{});
+        ygroup(std::integral_constant<int, 1>{});
+        ygroup(std::integral_constant<int, 2>{});
+        ygroup(std::integral_constant<int, 3>{});
+        ygroup(std::integral_constant<int, 4>{});
+        LDS_READS_DONE();
         if (pf_q < q_last) TAP_WALK_NEXT();
     };
 
@@ -365,19 +417,13 @@ __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
     };
     {
         int t, kc, q;
-        constexpr int PRE = NST - 1;               // chunks that are in LDS before the loop starts
+        constexpr int PRE = DEPTH == 3 ? 3 : 1;    // chunks on their way to stages 0 .. PRE - 1 before the loop starts
 #pragma unroll
         for (int c = 0; c < PRE; ++c) {
             q = chunk_of(c, t, kc);
-            gload(t, TAP_OFFSET(t), kc, q, rsa[0], rsb[0]);
-            sstore(c, rsa[0], rsb[0]);
+            dma(c, t, TAP_OFFSET(t), kc, q);
         }
-#pragma unroll
-        for (int s = 0; s < NSET; ++s) {           // set s <- chunk PRE + s
-            q = chunk_of(PRE + s, t, kc);
-            gload(t, TAP_OFFSET(t), kc, q, rsa[s], rsb[s]);
-        }
-        pf_q = chunk_of(PRE + NSET, pf_t, pf_kc);
+        pf_q = chunk_of(PRE, pf_t, pf_kc);
         pf_ts = pf_t % tw_S;
         pf_to = TAP_OFFSET(pf_t);
     }
@@ -405,24 +451,22 @@ __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
         oscale = q_pow2(oe);
         if (blockIdx.x == 0 && tid == 0) a.yq[1] = q_pow2(-oe);
     }
+    // chunk 0 has landed: this wavefront's share (everything but the two younger chunks of the three-stage ring), then everybody's
     __syncthreads();
+    DMA_WAIT_BARRIER(DEPTH == 3 ? 2 * NI : 0);
     if constexpr (MS == 16) {
         int rd = 0, nx = 1, wr = 2;
         lfragA16(As, ga[0]);
         lfragB16(Bs, 0, gb0);
+        LDS_READS_DONE();
         int q = 0;
         for (; q + 1 < nchunks; q += 2) {
-            step3_16(rd, nx, wr, rsa[0], rsb[0], ga[0], ga[1]);
-            __syncthreads();
-            step3_16(nx, wr, rd, rsa[1], rsb[1], ga[1], ga[0]);
-            __syncthreads();
+            step3_16(rd, nx, ga[0], ga[1]);
+            step3_16(nx, wr, ga[1], ga[0]);
             const int o = rd;
             rd = wr; wr = nx; nx = o;
         }
-        if (q < nchunks) {
-            step3_16(rd, nx, wr, rsa[0], rsb[0], ga[0], ga[1]);
-            __syncthreads();
-        }
+        if (q < nchunks) step3_16(rd, nx, ga[0], ga[1]);
 #pragma unroll
         for (int j = 0; j < 3; ++j)
 #pragma unroll
@@ -430,34 +474,29 @@ __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
     } else if constexpr (DEPTH == 3) {
         int rd = 0, nx = 1, wr = 2;
         lfrag(0, pk0, f0a, f0b);
+        LDS_READS_DONE();
         int q = 0;
         for (; q + 1 < nchunks; q += 2) {
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                step3(rd, nx, wr, rsa[s], rsb[s]);
-                __syncthreads();
+                step3(rd, nx);
                 const int o = rd;
                 rd = nx; nx = wr; wr = o;
             }
         }
-        if (q < nchunks) {
-            step3(rd, nx, wr, rsa[0], rsb[0]);
-            __syncthreads();
-        }
+        if (q < nchunks) step3(rd, nx);
     } else {
         int q = 0;
         for (; q + 1 < nchunks; q += 2) {
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                step(s, rsa[s], rsb[s]);
-                __syncthreads();
-            }
+            for (int s = 0; s < 2; ++s) step(s);
         }
-        if (q < nchunks) {
-            step(0, rsa[0], rsb[0]);
-            __syncthreads();
-        }
+        if (q < nchunks) step(0);
     }
+    // the look-ahead copies of the last chunks still write LDS, and other wavefronts still read their last fragments: the fused
+    // GDN, the planes pass and the scale reductions below reuse the ring
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
 
     // ---- epilogue: element (j, r) of the lane is local pixel row ROWL(r), local channel COLL(j, r) (MS == 32: column
     // wn0 + 32 j + lr, rows (r & 3) + 8 (r >> 2) + 4 lh of each 32x32 tile; MS == 16: two channels per j, selected by r >> 3) ---
@@ -525,15 +564,13 @@ __global__ __launch_bounds__(BM * 4) void conv_f16x3_kernel(const Fx3Args a)
         f32x4 gb[BP];
         auto gload_g = [&](int kc) {
 #pragma unroll
-            for (int u = 0; u < WFULL; ++u) gb[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rg, wv0 + u * (NT * 16), kc * B_BUF, 0));
-            if (BP > WFULL) gb[BP - 1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rg, wvl, kc * B_BUF, 0));
+            for (int u = 0; u < BP; ++u) gb[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rg, wv0 + u * (NT * 16), kc * B_BUF, 0));
         };
         gload_g(0);
         for (int kc = 0; kc < nkg; ++kc) {
             __syncthreads();                               // squares written (kc = 0) / previous chunk's fragments read
 #pragma unroll
-            for (int u = 0; u < WFULL; ++u) *reinterpret_cast<f32x4 *>(Bg + u * (NT * 16) + tid * 16) = gb[u];
-            if (BP > WFULL && WFULL * NT + tid < WPIECES) *reinterpret_cast<f32x4 *>(Bg + (WFULL * NT + tid) * 16) = gb[BP - 1];
+            for (int u = 0; u < BP; ++u) *reinterpret_cast<f32x4 *>(Bg + u * (NT * 16) + tid * 16) = gb[u];
             __syncthreads();
             if (kc + 1 < nkg) gload_g(kc + 1);
             if constexpr (MS == 16) {
@@ -681,7 +718,7 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
     const int bm0 = bxt * GBM, bn0 = blockIdx.y * GBN, zsplit = blockIdx.z;
     const int nslab = a.C / KC, pixbytes = a.xpix;
 
-    const int srow = tid >> 2, scol = tid & 3;
+    const int srow = tid >> 2, scol = (tid & 3) ^ ((srow >> 2) & 3);          // LDS row; source piece of this lane's slot (see conv_f16x3_kernel)
     int pb;
     unsigned pmask = 0;
     {
@@ -696,7 +733,6 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
             if (ok && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) pmask |= 1u << t;
         }
     }
-    const int a_st = srow * 64 + ((scol ^ ((srow >> 2) & 3)) << 4);
     const int nchunks = ntaps * nslab;
     const int q_begin = zsplit * cps;
     const int q_end = q_begin + cps < nchunks ? q_begin + cps : nchunks;
@@ -704,24 +740,19 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
     const int wbase = blockIdx.y * nchunks;          // this N tile's chunk sequence inside the packed weights
     __syncthreads();
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.xp), 0, a.xbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.wp), 0, a.wbytes, 0x00020000);
-
-    f32x4 raA[PL], rbA[BPC], raB[PL], rbB[BPC];
-    auto gload = [&](int t, int tA, int kc, int q, f32x4 (&ra)[PL], f32x4 (&rb)[BPC]) {
+    const rsrc4 rx = dma_rsrc(a.xp, a.xbytes), rw = dma_rsrc(a.wp, a.wbytes);
+    const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char *)smem;
+    const unsigned ldsw = __builtin_amdgcn_readfirstlane(lds0 + wave * 1024);
+    // chunk q -> LDS stage `stage` by LDS-DMA (see conv_f16x3_kernel): PL + BPC instructions per wavefront
+    auto dma = [&](int stage, int t, int tA, int kc, int q) {
         const int sA = kc * SLAB, sB = wofs + (wbase + q) * GB_BUF;
         const int mk = __builtin_amdgcn_sbfe((int)pmask, (unsigned)t, 1u);
         const int off = ((pb + tA) & mk) | (OOR & ~mk);
+        const unsigned la = ldsw + stage * GA_BUF, lb = ldsw + 2 * GA_BUF + stage * GB_BUF;
 #pragma unroll
-        for (int pl = 0; pl < PL; ++pl) ra[pl] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, off + pl * 64, sA, 0));
+        for (int pl = 0; pl < PL; ++pl) dma16(rx, la + pl * GA_PLANE, off + pl * 64, sA);
 #pragma unroll
-        for (int j = 0; j < BPC; ++j) rb[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, tid * 16 + j * (GNT * 16), sB, 0));
-    };
-    auto sstore = [&](int buf, f32x4 (&ra)[PL], f32x4 (&rb)[BPC]) {
-#pragma unroll
-        for (int pl = 0; pl < PL; ++pl) *reinterpret_cast<f32x4 *>(As + buf * GA_BUF + pl * GA_PLANE + a_st) = ra[pl];
-#pragma unroll
-        for (int j = 0; j < BPC; ++j) *reinterpret_cast<f32x4 *>(Bs + buf * GB_BUF + j * (GNT * 16) + tid * 16) = rb[j];
+        for (int j = 0; j < BPC; ++j) dma16(rw, lb + j * (GNT * 16), tid * 16 + j * (GNT * 16), sB);
     };
 
     const int wm0 = (wave >> 1) * 32, wn0 = (wave & 1) * 64;
@@ -743,10 +774,14 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
 
     int pf_q = 0, pf_t = 0, pf_kc = 0, pf_ts = 0, pf_to = 0;          // see conv_f16x3_kernel
     const int tw_T = ntaps, tw_S = tapS, tw_col = pixbytes, tw_line = a.W * pixbytes, tw_first = (pdy0 * a.W + pdx0) * pixbytes;
-    auto step = [&](int cur, f32x4 (&ra)[PL], f32x4 (&rb)[BPC]) {
+    // Two stages: chunk c + 1 is copied into the other stage (free since the barrier that ended chunk c - 1) while chunk c is
+    // multiplied, and has landed for every wavefront behind the wait and the barrier that end the step; the other workgroups of
+    // the CU cover what the one chunk of look-ahead does not
+    auto step = [&](int cur) {
         const unsigned char *Ab = As + cur * GA_BUF + rdA, *Bb = Bs + cur * GB_BUF + rdB;
         const int t = __builtin_amdgcn_readfirstlane(pf_t), kc = __builtin_amdgcn_readfirstlane(pf_kc), q = __builtin_amdgcn_readfirstlane(pf_q);
         const int to = __builtin_amdgcn_readfirstlane(pf_to);
+        dma(cur ^ 1, t, to, kc, q);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const int pk = ks ? pk1 : pk0;
@@ -763,12 +798,9 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
                 acc[j] = STEM_MFMA16(af[0], bf[1][j], acc[j]);
                 acc[j] = STEM_MFMA16(af[0], bf[0][j], acc[j]);
             }
-            if (ks == 0)
-                sstore(cur ^ 1, ra, rb);
-            else
-                gload(t, to, kc, q, ra, rb);
         }
         if (pf_q < q_last) TAP_WALK_NEXT();
+        DMA_WAIT_BARRIER(0);
     };
     // MS == 16: a chunk is one k-step of the 16x16x32 instruction; 2 x 4 accumulators of four registers, the eight independent
     // accumulators of a product back to back
@@ -779,10 +811,11 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
 #pragma unroll
             for (int nj = 0; nj < 4; ++nj) a16[mi][nj] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    auto step16 = [&](int cur, f32x4 (&ra)[PL], f32x4 (&rb)[BPC]) {
+    auto step16 = [&](int cur) {
         const unsigned char *Ab = As + cur * GA_BUF + rdA16, *Bb = Bs + cur * GB_BUF + rdB16;
         const int t = __builtin_amdgcn_readfirstlane(pf_t), kc = __builtin_amdgcn_readfirstlane(pf_kc), q = __builtin_amdgcn_readfirstlane(pf_q);
         const int to = __builtin_amdgcn_readfirstlane(pf_to);
+        dma(cur ^ 1, t, to, kc, q);
         h16x8 A[2][PL], B[4][PL];
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
@@ -793,27 +826,25 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
 #pragma unroll
             for (int pl = 0; pl < PL; ++pl) B[nj][pl] = *reinterpret_cast<const h16x8 *>(Bb + nj * 16 * 64 + pl * GB_PLANE);
 #pragma unroll
-        for (int prod = 0; prod < 3; ++prod) {          // smallest terms first
+        for (int prod = 0; prod < 3; ++prod)            // smallest terms first
 #pragma unroll
             for (int nj = 0; nj < 4; ++nj)
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
                     a16[mi][nj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[mi][prod == 0 ? 1 : 0], B[nj][prod == 1 ? 1 : 0], a16[mi][nj], 0, 0, 0);
-            if (prod == 0) sstore(cur ^ 1, ra, rb);
-        }
-        gload(t, to, kc, q, ra, rb);
         if (pf_q < q_last) TAP_WALK_NEXT();
+        DMA_WAIT_BARRIER(0);
     };
     // A wavefront whose 64 columns lie entirely beyond N (the second column pair of the last tile of a 320-channel layer: a
-    // sixth of the launch's matrix work) only takes part in the staging: same loads, LDS writes and barriers, no LDS reads and
+    // sixth of the launch's matrix work) only takes part in the staging: same copies and barriers, no LDS reads and
     // no MFMAs.  The choice is made once per wavefront, OUTSIDE the woven block (a per-sub-tile branch inside it was slower).
     const bool dead = bn0 + wn0 >= a.N;
-    auto step_dead = [&](int cur, f32x4 (&ra)[PL], f32x4 (&rb)[BPC]) {
+    auto step_dead = [&](int cur) {
         const int t = __builtin_amdgcn_readfirstlane(pf_t), kc = __builtin_amdgcn_readfirstlane(pf_kc), q = __builtin_amdgcn_readfirstlane(pf_q);
         const int to = __builtin_amdgcn_readfirstlane(pf_to);
-        sstore(cur ^ 1, ra, rb);
-        gload(t, to, kc, q, ra, rb);
+        dma(cur ^ 1, t, to, kc, q);
         if (pf_q < q_last) TAP_WALK_NEXT();
+        DMA_WAIT_BARRIER(0);
     };
     auto chunk_of = [&](int q, int &t, int &kc) {
         q = q < q_last ? q : q_last;
@@ -824,13 +855,8 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
     if (q_begin < q_end) {
         int t, kc, q;
         q = chunk_of(q_begin, t, kc);
-        gload(t, TAP_OFFSET(t), kc, q, raA, rbA);
-        sstore(0, raA, rbA);
-        q = chunk_of(q_begin + 1, t, kc);
-        gload(t, TAP_OFFSET(t), kc, q, raA, rbA);
-        q = chunk_of(q_begin + 2, t, kc);
-        gload(t, TAP_OFFSET(t), kc, q, raB, rbB);
-        pf_q = chunk_of(q_begin + 3, pf_t, pf_kc);
+        dma(0, t, TAP_OFFSET(t), kc, q);
+        pf_q = chunk_of(q_begin + 1, pf_t, pf_kc);
         pf_ts = pf_t % tw_S;
         pf_to = TAP_OFFSET(pf_t);
     }
@@ -840,18 +866,14 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
     const float fac = q_inv(a.xq) * q_inv(a.wq);                   // the operands were stored times 2^ex, 2^ew
     const float oscale = tail_oscale<GNT>(a.yp != nullptr, a.xq, a.wq, a.bias, a.N, a.C * (PH ? a.btaps : ntaps), a.yq, blockIdx.x == 0 && blockIdx.y == 0, qred);
     __syncthreads();
+    DMA_WAIT_BARRIER(0);            // the first chunk has landed, for every wavefront
     if (!dead && MS == 16) {
         int q = q_begin;
         for (; q + 1 < q_end; q += 2) {
-            step16(0, raA, rbA);
-            __syncthreads();
-            step16(1, raB, rbB);
-            __syncthreads();
+            step16(0);
+            step16(1);
         }
-        if (q < q_end) {
-            step16(0, raA, rbA);
-            __syncthreads();
-        }
+        if (q < q_end) step16(0);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -859,28 +881,19 @@ __global__ __launch_bounds__(GBM * 4, 2) void conv_f16x3_gen_kernel(const Fx3Arg
     } else if (!dead) {
         int q = q_begin;
         for (; q + 1 < q_end; q += 2) {
-            step(0, raA, rbA);
-            __syncthreads();
-            step(1, raB, rbB);
-            __syncthreads();
+            step(0);
+            step(1);
         }
-        if (q < q_end) {
-            step(0, raA, rbA);
-            __syncthreads();
-        }
+        if (q < q_end) step(0);
     } else {
         int q = q_begin;
         for (; q + 1 < q_end; q += 2) {
-            step_dead(0, raA, rbA);
-            __syncthreads();
-            step_dead(1, raB, rbB);
-            __syncthreads();
+            step_dead(0);
+            step_dead(1);
         }
-        if (q < q_end) {
-            step_dead(0, raA, rbA);
-            __syncthreads();
-        }
+        if (q < q_end) step_dead(0);
     }
+    // every step ends with its copy landed and a barrier: nothing is in flight, and nobody still reads the ring the tail reuses
 
     // ---- the tail (f16x3_tail.h).  Stated here: the scatter of the accumulators, tile row -> output row (OROW), the slab sum ----
     float *T = reinterpret_cast<float *>(smem);                     // [GBM][GTP]
