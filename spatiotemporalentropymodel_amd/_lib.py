@@ -1,5 +1,5 @@
 """ctypes loader for the C-ABI libraries (include/stem_hip.h + include/stem_ar_batch.h + include/stem_blocks.h +
-include/stem_hyperprior.h + include/stem_eb_filters.h + include/stem_gdn1.h + include/stem_validation.h, include/stem_tail.h, include/stem_frameio.h, include/stem_roiio.h,
+include/stem_hyperprior.h + include/stem_eb_filters.h + include/stem_gdn1.h + include/stem_validation.h, include/stem_tail.h, include/stem_frameio.h, include/stem_roiio.h, include/stem_statehash.h,
 include/stem_rans.h, include/stem_dp.h).
 
 The headers are the single statement of the ABI: every prototype and descriptor structure below is read from them (_abi.py).
@@ -27,6 +27,8 @@ FRAMEIO_SO = os.path.join(_PKG, "libstem_frameio.so")
 TAIL_SO = os.path.join(_PKG, "libstem_tail.so")
 # the per-frame passes of the pixel-domain sequence codec (include/stem_roiio.h): a library of their own as well
 ROIIO_SO = os.path.join(_PKG, "libstem_roiio.so")
+# the conditioning-state hash of the sequence codecs (include/stem_statehash.h): a library of its own as well
+STATEHASH_SO = os.path.join(_PKG, "libstem_statehash.so")
 DP_SO = os.environ.get("STEM_DP_LIBRARY") or os.path.join(_PKG, "libstem_dp.so")
 _hip = None
 _rans = None
@@ -34,6 +36,7 @@ _dp = None
 _frameio = None
 _tail = None
 _roiio = None
+_statehash = None
 
 
 class StemLibraryError(RuntimeError):
@@ -76,6 +79,8 @@ _TAPE_SIG = {**_HIP_SIG, **{n: a for n, a in _TAIL_SIG.items() if not n.startswi
 _FRAMEIO_PROTO, _FRAMEIO_SIG, _ = _tables("stem_frameio.h")
 # libstem_roiio.so's recondition and ROI rasteriser kernels (csrc/roiio.hip; not launch-tape entries either)
 _ROIIO_PROTO, _ROIIO_SIG, _ = _tables("stem_roiio.h")
+# libstem_statehash.so's per-image hash of a conditioning state (csrc/statehash.hip; not a launch-tape entry either)
+_STATEHASH_PROTO, _STATEHASH_SIG, _ = _tables("stem_statehash.h")
 _RANS_PROTO, _RANS_SIG, _RANS_RESTYPE = _tables("stem_rans.h")
 _DP_PROTO, _DP_SIG, _ = _tables("stem_dp.h")
 _STRUCTS = _abi.structs(_header("stem_hip.h"))
@@ -177,6 +182,22 @@ def check_roiio(rc: int):
         raise RuntimeError((roiio().stem_roiio_last_error() or b"").decode() or f"libstem_roiio error {rc}")
 
 
+def statehash():
+    """libstem_statehash.so (include/stem_statehash.h), or raise: like libstem_hip.so it has no fallback"""
+    global _statehash
+    if _statehash is None:
+        if not os.path.exists(STATEHASH_SO):
+            raise StemLibraryError(f"{STATEHASH_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                                   "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the state hash.")
+        _statehash = _bind(C.CDLL(STATEHASH_SO), _STATEHASH_PROTO)
+    return _statehash
+
+
+def check_statehash(rc: int):
+    if rc != 0:
+        raise RuntimeError((statehash().stem_statehash_last_error() or b"").decode() or f"libstem_statehash error {rc}")
+
+
 def rans():
     global _rans
     if _rans is None:
@@ -229,6 +250,10 @@ def declared_frameio_symbols():
 
 def declared_roiio_symbols():
     return sorted(_ROIIO_SIG)
+
+
+def declared_statehash_symbols():
+    return sorted(_STATEHASH_SIG)
 
 
 def header_macro(header, name):

@@ -672,9 +672,9 @@ def iframe_compress_each(model, xs, order="raster", return_y_hat=False):
     return [_result([y], z, zshape, order, _slice_nhwc(y_hats, i)) for i, (y, (z, zshape)) in enumerate(zip(y_strings, zs))]
 
 
-def iframe_decompress_each(model, strings, shapes, order="raster"):
+def iframe_decompress_each(model, strings, shapes, order="raster", latents_only=False):
     """`iframe_decompress` of several independent images: h_s and g_s per image at batch 1, one batched `_decode_latents` call.
-    -> one {"x_hat", "y_hat"} per image."""
+    -> one {"x_hat", "y_hat"} per image; latents_only=True: {"y_hat"} alone, g_s does not run (video.verify_sequence)."""
     _check_order(order, model)
     dev = next(model.parameters()).device
     params = []
@@ -687,7 +687,7 @@ def iframe_decompress_each(model, strings, shapes, order="raster"):
     res = []
     for i in range(len(params)):
         y_hat = _slice_nhwc(y_hats, i)
-        res.append({"x_hat": F.to_nchw(model.g_s(y_hat), clamp01=True), "y_hat": y_hat})
+        res.append({"y_hat": y_hat} if latents_only else {"x_hat": F.to_nchw(model.g_s(y_hat), clamp01=True), "y_hat": y_hat})
     return res
 
 

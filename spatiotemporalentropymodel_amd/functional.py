@@ -1556,6 +1556,63 @@ def roi_map_padded(boxes, size, background=0.0, multiple=64, frame=None, device=
     return out
 
 
+def state_hash_strides(shape, stride):
+    """The strides stem_state_hash is handed for a [B,C,H,W] tensor with those strides (pure): planar rows (sw == 1) or channels-last
+    pixels (sc == 1), dense or pitched; a dimension of extent 1 has no stride of its own and gets the dense one.  ValueError for
+    every other layout -- one that would need a copy."""
+    B, Cc, H, W = (int(s) for s in shape)
+    sb, sc, sh, sw = (int(s) for s in stride)
+    if min(B, Cc, H, W) < 1:
+        raise ValueError(f"state_hash: an empty tensor {tuple(shape)} has no state")
+    for planar in ((True, False) if W >= Cc else (False, True)):     # both fit where extents are 1: the longer unit-stride runs first
+        if planar:
+            h_ = sh if H > 1 else W
+            c_ = sc if Cc > 1 else (H - 1) * h_ + W
+            ok = (W == 1 or sw == 1) and h_ >= W and c_ >= (H - 1) * h_ + W
+            span, got = (Cc - 1) * c_ + (H - 1) * h_ + W, (c_, h_, 1)
+        else:
+            w_ = sw if W > 1 else Cc
+            h_ = sh if H > 1 else (W - 1) * w_ + Cc
+            ok = (Cc == 1 or sc == 1) and w_ >= Cc and h_ >= (W - 1) * w_ + Cc
+            span, got = (H - 1) * h_ + (W - 1) * w_ + Cc, (1, h_, w_)
+        if ok and (B == 1 or sb >= span):
+            return (sb if B > 1 else span,) + got
+    raise ValueError(f"state_hash: strides {tuple(stride)} of {tuple(shape)} are neither planar rows nor channels-last pixels (dense or "
+                     "pitched, images apart)")
+
+
+def state_hash(t, out=None):
+    """The conditioning-state hash (stem_state_hash; include/stem_statehash.h): 64 bits per image of a 4-D fp32 device tensor, a
+    function of its values at their logical NCHW positions and not of its layout -- channels-last or planar, dense or a pitched view,
+    read in place.  -> int64 [B] holding the 64 bits (state_hash_ints turns them into Python ints); out= an int64 device tensor of B
+    elements to write instead, e.g. a slice of a longer buffer that one copy fetches.  No host synchronisation."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("state_hash: STEM HIP kernels need CUDA/ROCm tensors (no CPU fallback exists)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"state_hash: the state is fp32, got {t.dtype}")
+    if t.dim() != 4:
+        raise ValueError(f"state_hash takes a [B,C,H,W] tensor, got {tuple(t.shape)}")
+    t = t.detach()
+    B, Cc, H, W = t.shape
+    sb, sc, sh, sw = state_hash_strides(t.shape, t.stride())
+    if out is None:
+        out = torch.empty(B, dtype=torch.int64, device=t.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or out.device != t.device or tuple(out.shape) != (B,)
+          or not out.is_contiguous()):
+        raise ValueError(f"state_hash: out= is a contiguous int64 tensor of {B} elements on {t.device}")
+    lib = _lib.statehash()
+    need = int(lib.stem_state_hash_workspace_bytes(B, Cc, H, W))
+    ws = torch.empty(need // 8, dtype=torch.int64, device=t.device) if need else None
+    with torch.cuda.device(t.device):
+        _lib.check_statehash(lib.stem_state_hash(t.data_ptr(), B, Cc, H, W, sb, sc, sh, sw, out.data_ptr(), _ptr(ws) or None, need, _stream()))
+    return out
+
+
+def state_hash_ints(hashes):
+    """an int64 tensor of state hashes -> Python ints in [0, 2^64) (one device-to-host copy when it lives on the device)"""
+    return [int(v) & 0xFFFFFFFFFFFFFFFF for v in hashes.detach().cpu().reshape(-1).tolist()]
+
+
 def ycbcr_convert(x, to_rgb):
     """transforms.ycbcr2rgb (to_rgb) / rgb2ycbcr of an fp32 device tensor [3,H,W] or [N,3,H,W] (stem_ycbcr_convert)"""
     _require_cuda(x)

@@ -122,11 +122,13 @@ class FactorizedPrior(CompressionModel):
             y_strings = self.entropy_bottleneck.compress(y)
         return {"strings": [y_strings], "shape": y.size()[-2:]}
 
-    def decompress(self, strings, shape):
-        """priors.py:177-181 -> {"x_hat"} and, not in the reference, "y_hat" """
+    def decompress(self, strings, shape, latents_only=False):
+        """priors.py:177-181 -> {"x_hat"} and, not in the reference, "y_hat"; latents_only=True: {"y_hat"} alone, g_s does not run"""
         assert isinstance(strings, list) and len(strings) == 1
         with torch.no_grad():
             y_hat = self.entropy_bottleneck.decompress(strings[0], shape)
+            if latents_only:
+                return {"y_hat": y_hat}
             x_hat = F.to_nchw(self.g_s(y_hat), clamp01=True)
         return {"x_hat": x_hat, "y_hat": y_hat}
 
@@ -195,13 +197,16 @@ class ScaleHyperprior(CompressionModel):
             y_strings = self.gaussian_conditional.compress(y, None, means=means_hat, scales=scales_hat)
         return {"strings": [y_strings, z_strings], "shape": z.size()[-2:]}
 
-    def decompress(self, strings, shape):
-        """priors.py:306-313, 378-388 -> {"x_hat"} and, not in the reference's ScaleHyperprior, "y_hat" """
+    def decompress(self, strings, shape, latents_only=False):
+        """priors.py:306-313, 378-388 -> {"x_hat"} and, not in the reference's ScaleHyperprior, "y_hat"; latents_only=True: {"y_hat"}
+        alone, g_s does not run"""
         assert isinstance(strings, list) and len(strings) == 2
         with torch.no_grad():
             z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
             scales_hat, means_hat = self._gaussian_params(z_hat)
             y_hat = self.gaussian_conditional.decompress(strings[0], None, means=means_hat, scales=scales_hat)
+            if latents_only:
+                return {"y_hat": y_hat}
             x_hat = F.to_nchw(self.g_s(y_hat), clamp01=True)
         return {"x_hat": x_hat, "y_hat": y_hat}
 

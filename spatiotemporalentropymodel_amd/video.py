@@ -3,7 +3,8 @@ that has nothing but that file and the two models.
 
     encode_sequence(imodel, stem, frames, out, gop=12, ...)     frames -> file; g_s never runs, no decompress is called
     decode_sequence(imodel, stem, src, write_to=None, ...)      file -> planar 4:2:0 frames (and the cropped x_hat tensors)
-    python -m spatiotemporalentropymodel_amd.video encode|decode ...
+    verify_sequence(imodel, stem, src, ...)                     file -> a report: every frame's state hash checked, latents only
+    python -m spatiotemporalentropymodel_amd.video encode|decode|verify ...
 
 evaluation.eval_gop / eval_sequence compress a frame and decompress it at once with the same objects, because the next P frame is
 conditioned on the DECODED latents.  The encoder already holds those: the raster-order coding kernels leave the reconstruction in their
@@ -24,6 +25,16 @@ frame is a frame of that image model's latent space -- its g_s turns the decoded
 byte the record the reference's tool writes for that image.  Bit 7 of the second header byte marks wavefront symbol order
 (bitstream.ORDER_BIT).  A record is skipped without parsing its strings, by the length prefixes (`record_ranges`): decoding
 frames=(start, stop) touches only the GOPs that cover the range.
+
+State hashes (opt-in: encode_sequence(state_hash=True), `encode --state-hash`).  The codec is closed-loop: frame t is decoded under
+priors computed from the decoder's own y_hat of frame t - 1, so a decoder whose arithmetic differs in one last bit -- another tile plan,
+another build of the library -- decodes plausible garbage from there to the end of the GOP.  A hashed file carries bit 7 in its version
+byte (STATE_HASH_BIT, in the manner of bitstream.ORDER_BIT) and, behind the last record, a trailer of `frames` u64: per frame in display
+order, functional.state_hash of the y_hat the next P frame is conditioned on, from the encoder's own reconstruction.  Header and records
+are byte for byte the un-hashed file's but for that bit; the trailer sits 8 * frames bytes from the end, so a partial decode finds its
+entries without parsing further.  decode_sequence compares every decoded frame's hash BEFORE the state becomes a condition and raises
+StateMismatch; verify_sequence checks a whole file on latents alone.  The hash covers the conditioning state: it proves that every
+symbol and every prior matched, not that g_s of an equal y_hat gives equal pixels.
 
 The fingerprint is zlib.crc32 over a model's state_dict in key order: each key's name, then the tensor's bytes (a masked convolution's
 weight through its mask: `fingerprint`).  It covers the weights and the integer CDF tables (buffers of the entropy models): a decoder with other weights, or with tables rebuilt on another host's libm,
@@ -47,6 +58,8 @@ from . import bitstream
 
 MAGIC = b"STMV"
 VERSION = 1
+#: bit 7 of the version byte: behind the last record the file has a trailer of one u64 state hash per frame
+STATE_HASH_BIT = 0x80
 #: the P-frame model's index in the file header
 STEM_CLASSES = ("SpatioTemporalPriorModelWithoutSPMTPM", "SpatioTemporalPriorModelWithoutSPM", "SpatioTemporalPriorModelWithoutTPM",
                 "SpatioTemporalPriorModel", "SpatioTemporalPriorModel_Res")
@@ -58,27 +71,29 @@ _FIELDS = ("width", "height", "bit_depth", "frames", "gop", "all_intra", "qualit
 
 
 class FileHeader:
-    """the file header as attributes (`_FIELDS`); `pack()` <-> `unpack(bytes)`"""
+    """the file header as attributes (`_FIELDS`); `pack()` <-> `unpack(bytes)`.  `state_hash` (outside `_FIELDS`: it is a bit of the
+    version byte, not a field of the struct) says that the file ends in a trailer of state hashes."""
 
-    def __init__(self, **kw):
+    def __init__(self, state_hash=False, **kw):
         missing = set(_FIELDS) - set(kw)
         if missing or set(kw) - set(_FIELDS):
             raise TypeError(f"FileHeader takes exactly {_FIELDS}, got {sorted(kw)}")
         for k in _FIELDS:
             setattr(self, k, int(kw[k]))
+        self.state_hash = bool(state_hash)
 
     def astuple(self):
         return tuple(getattr(self, k) for k in _FIELDS)
 
     def __eq__(self, other):
-        return isinstance(other, FileHeader) and self.astuple() == other.astuple()
+        return isinstance(other, FileHeader) and self.astuple() == other.astuple() and self.state_hash == other.state_hash
 
     def __repr__(self):
-        return "FileHeader(" + ", ".join(f"{k}={getattr(self, k)}" for k in _FIELDS) + ")"
+        return "FileHeader(" + ", ".join(f"{k}={getattr(self, k)}" for k in _FIELDS) + (", state_hash=True" if self.state_hash else "") + ")"
 
     def pack(self):
         self.check()
-        return _HEADER.pack(MAGIC, VERSION, *self.astuple())
+        return _HEADER.pack(MAGIC, VERSION | (STATE_HASH_BIT if self.state_hash else 0), *self.astuple())
 
     @classmethod
     def unpack(cls, data):
@@ -87,9 +102,9 @@ class FileHeader:
         magic, version, *rest = _HEADER.unpack(data[:HEADER_BYTES])
         if magic != MAGIC:
             raise ValueError(f"not a sequence file: magic {magic!r}, expected {MAGIC!r}")
-        if version != VERSION:
-            raise ValueError(f"sequence file version {version}, this module reads version {VERSION}")
-        hdr = cls(**dict(zip(_FIELDS, rest)))
+        if version & ~STATE_HASH_BIT != VERSION:
+            raise ValueError(f"sequence file version {version & ~STATE_HASH_BIT}, this module reads version {VERSION}")
+        hdr = cls(state_hash=bool(version & STATE_HASH_BIT), **dict(zip(_FIELDS, rest)))
         hdr.check()
         return hdr
 
@@ -212,12 +227,12 @@ def _record_order(model, order):
     return order if getattr(model, "HAS_SPM", False) else "raster"
 
 
-def _header_for(imodel, stem, h, w, bit_depth, n, gop, all_intra, quality):
+def _header_for(imodel, stem, h, w, bit_depth, n, gop, all_intra, quality, state_hash=False):
     types = frame_types(n, gop, all_intra)
     name, sidx = _check_models(imodel, stem, "P" in types)
     use_stem = sidx != NO_STEM and "P" in types
-    return FileHeader(width=w, height=h, bit_depth=bit_depth, frames=n, gop=gop, all_intra=int(bool(all_intra)), quality=quality,
-                      imodel_id=bitstream.model_ids[name], imodel_n=imodel.N, imodel_m=imodel.M, imodel_crc=fingerprint(imodel),
+    return FileHeader(state_hash=state_hash, width=w, height=h, bit_depth=bit_depth, frames=n, gop=gop, all_intra=int(bool(all_intra)),
+                      quality=quality, imodel_id=bitstream.model_ids[name], imodel_n=imodel.N, imodel_m=imodel.M, imodel_crc=fingerprint(imodel),
                       stem_class=sidx if use_stem else NO_STEM, stem_n=stem.entropy_bottleneck.channels if use_stem else 0,
                       stem_m=stem.in_channels if use_stem else 0, stem_crc=fingerprint(stem) if use_stem else 0)
 
@@ -285,6 +300,88 @@ def _read_record(data, rng, hdr, index):
     return bitstream.stream_order(header), tuple(shape), strings
 
 
+# ---- the state-hash trailer (shared with video_pixel.py) ------------------------------------------------------------------------
+class StateMismatch(ValueError):
+    """a decoded frame's conditioning state is not the one the encoder hashed: .frame, .gop_start (the index of its GOP's I frame),
+    .want (the file's hash) and .got (the decoder's), both ints in [0, 2^64)"""
+
+    def __init__(self, frame, gop_start, want, got):
+        super().__init__(f"state mismatch at frame {frame} (its GOP starts at frame {gop_start}): the file says {want:016x}, this decoder "
+                         f"computed {got:016x}; nothing decoded from this state on can be trusted")
+        self.frame, self.gop_start, self.want, self.got = int(frame), int(gop_start), int(want), int(got)
+
+
+def trailer_bytes(hashes):
+    """the trailer of a hashed file: one big-endian u64 per frame in display order"""
+    return struct.pack(f">{len(hashes)}Q", *hashes)
+
+
+def split_trailer(data, hdr, header_bytes=HEADER_BYTES):
+    """(header + records, state hashes) of the whole file `data`: the trailer is the last 8 * frames bytes of a hashed file (hdr.state_hash)
+    -> (data, None) for an un-hashed one.  ValueError when a hashed file has no room for its trailer; a trailer of another length shows
+    as records that end early or late (`hashed_record_ranges`)."""
+    if not hdr.state_hash:
+        return data, None
+    n = 8 * hdr.frames
+    if len(data) < header_bytes + n:
+        raise ValueError(f"truncated file: a state-hash trailer of {n} bytes ({hdr.frames} frames) does not fit {len(data) - header_bytes} bytes "
+                         "behind the header")
+    return data[:len(data) - n], list(struct.unpack_from(f">{hdr.frames}Q", data, len(data) - n))
+
+
+def hashed_record_ranges(data, hdr, header_bytes=HEADER_BYTES):
+    """record_ranges over the file without its trailer -> (ranges, state hashes or None).  ValueError when the records do not end
+    exactly where the trailer (or, in an un-hashed file, the file's end) begins."""
+    body, hashes = split_trailer(data, hdr, header_bytes)
+    try:
+        return record_ranges(body, hdr.frames, header_bytes), hashes
+    except ValueError as e:
+        if hashes is None:
+            raise
+        raise ValueError(f"the state-hash trailer is not the {8 * hdr.frames} bytes behind the last record: {e}") from None
+
+
+def _read_state_hashes(data, header_cls, header_bytes):
+    data = bytes(data)
+    hdr = header_cls.unpack(data)
+    return hashed_record_ranges(data, hdr, header_bytes)[1]
+
+
+def read_state_hashes(data):
+    """the state hashes of a sequence file (its bytes): a list of `frames` ints in display order, or None for an un-hashed file;
+    ValueError for a file whose trailer does not sit right behind its last record"""
+    return _read_state_hashes(data, FileHeader, HEADER_BYTES)
+
+
+def gop_starts(types):
+    """per frame, the index of its GOP's I frame"""
+    out, last = [], 0
+    for i, t in enumerate(types):
+        last = i if t == "I" else last
+        out.append(last)
+    return out
+
+
+def _hash_states(states):
+    """functional.state_hash of every tensor in `states` ([1,C,H,W] each) into one device buffer, fetched with one copy -> ints"""
+    from . import functional as F
+    buf = torch.empty(len(states), dtype=torch.int64, device=states[0].device)
+    for k, t in enumerate(states):
+        F.state_hash(t, out=buf[k:k + 1])
+    return F.state_hash_ints(buf)
+
+
+def _read_all(src):
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        return bytes(src)
+    fd, close = _open(src, "rb")
+    try:
+        return fd.read()
+    finally:
+        if close:
+            fd.close()
+
+
 # ---- sources -------------------------------------------------------------------------------------------------------------------
 class _Source:
     """the frames of encode_sequence: a data.YUVSequence (integer planes through the ingest kernel) or a sequence of [3,h,w] tensors"""
@@ -331,17 +428,20 @@ def _open(target, mode):
 
 # ---- the encoder ---------------------------------------------------------------------------------------------------------------
 @torch.no_grad()
-def encode_sequence(imodel, stem, frames, out, gop=12, concurrent_gops=8, all_intra=False, order="raster", quality=4):
+def encode_sequence(imodel, stem, frames, out, gop=12, concurrent_gops=8, all_intra=False, order="raster", quality=4, state_hash=False):
     """Code `frames` (a data.YUVSequence, or a sequence of [3,h,w] tensors in [0,1] of one size; plain tensors make an 8-bit file) into
     `out` (a path or a binary file object).  Frame types and the walk through the GOPs are evaluation.gop_schedule's; every record holds
     the strings evaluation.eval_gop gives for that frame.  No decoder and no synthesis transform runs: the next frame's condition is the
     encoder's own reconstruction of the latent (`return_y_hat=True`).  stem may be None with all_intra=True.  quality: the 4 bits of the
-    records' header the reference's tool fills from its --quality.
-    -> {"frames": [{"type", "bytes", "bpp"}] in display order, "bytes": the file's size, "bpp_ave"}"""
+    records' header the reference's tool fills from its --quality.  state_hash=True: a hashed file -- bit 7 of the version byte and,
+    behind the last record, every frame's functional.state_hash of its y_hat (the next condition); a step's chains hash into one device
+    buffer that one copy fetches.  The records are those of the un-hashed file.
+    -> {"frames": [{"type", "bytes", "bpp"}] in display order, "bytes": the file's size, "bpp_ave"} and, with state_hash, "state_hash":
+    the hashes in display order"""
     from . import codec, evaluation
     codec._check_order(order)
     src = _Source(frames, _device_of(imodel))
-    hdr = _header_for(imodel, stem, src.h, src.w, src.bit_depth, src.n, gop, all_intra, quality)
+    hdr = _header_for(imodel, stem, src.h, src.w, src.bit_depth, src.n, gop, all_intra, quality, state_hash)
     name = hdr.imodel_name
     coders = [imodel] + ([stem] if hdr.stem_class != NO_STEM else [])
     if order == "wavefront" and not any(getattr(m, "HAS_SPM", False) for m in coders):
@@ -351,7 +451,7 @@ def encode_sequence(imodel, stem, frames, out, gop=12, concurrent_gops=8, all_in
     try:
         fd.write(hdr.pack())
         writer = evaluation._InOrder(fd)
-        per_frame, y_cond = [None] * src.n, {}
+        per_frame, y_cond, hashes = [None] * src.n, {}, [None] * src.n
         for step in steps:
             padded = [src.padded(i) for i, _, _ in step]
             ipos = [k for k, (_, kind, _) in enumerate(step) if kind == "I"]
@@ -376,12 +476,20 @@ def encode_sequence(imodel, stem, frames, out, gop=12, concurrent_gops=8, all_in
                 bits = sum(len(s[0]) for s in enc[k]["strings"]) * 8.0
                 per_frame[index] = {"type": kind, "bytes": len(rec), "bpp": bits / (src.h * src.w)}
                 writer.put(index, rec)
+            if state_hash:
+                for (index, _, _), v in zip(step, _hash_states([e["y_hat"] for e in enc])):
+                    hashes[index] = v
             y_cond = {chain: enc[k]["y_hat"] for k, (_, _, chain) in enumerate(step)}     # a chain that left the step has ended
+        if state_hash:
+            fd.write(trailer_bytes(hashes))                                               # behind the last record: the writer is done
     finally:
         if close:
             fd.close()
-    return {"frames": per_frame, "bytes": HEADER_BYTES + sum(f["bytes"] for f in per_frame),
-            "bpp_ave": sum(f["bpp"] for f in per_frame) / len(per_frame)}
+    res = {"frames": per_frame, "bytes": HEADER_BYTES + sum(f["bytes"] for f in per_frame) + (8 * src.n if state_hash else 0),
+           "bpp_ave": sum(f["bpp"] for f in per_frame) / len(per_frame)}
+    if state_hash:
+        res["state_hash"] = hashes
+    return res
 
 
 # ---- the decoder ---------------------------------------------------------------------------------------------------------------
@@ -392,30 +500,56 @@ def _planes_bytes(planes):
     return buf.getvalue()
 
 
+def _decode_step(imodel, stem, hdr, step, recs, y_cond, latents_only=False):
+    """the records `recs` of one step of decode_steps -> (y_hat, x_hat) per position: I frames by the image model's decompress (x_hat
+    with it, unless latents_only: then no synthesis transform runs), P frames by the STEM model's given their chain's condition (x_hat
+    None: the caller runs getX once the state is accepted)"""
+    from . import codec
+    y_hat, x_hat = [None] * len(step), [None] * len(step)
+    for kind in ("I", "P"):
+        pos = [k for k, (_, t, _) in enumerate(step) if t == kind]
+        if not pos:
+            continue
+        orders = {recs[k][0] for k in pos}
+        if len(orders) != 1:
+            raise ValueError(f"the {kind} records of frames {[step[k][0] for k in pos]} mix symbol orders")
+        o = orders.pop()
+        strings, shapes = [recs[k][2] for k in pos], [recs[k][1] for k in pos]
+        more = {"latents_only": True} if latents_only else {}
+        if kind == "I" and getattr(imodel, "HAS_SPM", False):
+            outs = codec.iframe_decompress_each(imodel, strings, shapes, order=o, **more)
+        elif kind == "I":
+            if o != "raster":
+                raise ValueError(f"{hdr.imodel_name} codes in one shot: its records cannot be in wavefront order")
+            outs = [imodel.decompress(s, sh, **more) for s, sh in zip(strings, shapes)]
+        else:
+            ys = codec.stem_decompress_each(stem, strings, shapes, [y_cond[step[k][2]] for k in pos], order=o)
+            outs = [{"y_hat": y} for y in ys]
+        for k, d in zip(pos, outs):
+            y_hat[k], x_hat[k] = d["y_hat"], d.get("x_hat")
+    return y_hat, x_hat
+
+
 @torch.no_grad()
-def decode_sequence(imodel, stem, src, write_to=None, concurrent_gops=8, frames=None, return_frames=True):
+def decode_sequence(imodel, stem, src, write_to=None, concurrent_gops=8, frames=None, return_frames=True, verify=True):
     """Decode the file `src` (a path, bytes, or a binary file object) with nothing else: its header is checked against the two models
     (`check_header`), then every GOP is rebuilt from its records -- I frames by the image model's decompress, P frames by the STEM model's
     given the previous frame's decoded latent, pixels by getX -- with up to `concurrent_gops` GOPs side by side.  write_to (a path or a
     binary file object) receives the frames in display order as raw planar 4:2:0 at the file's bit depth, quantised from the padded
     x_hat by one kernel per frame (functional.rgb_window_to_yuv420).  frames=(start, stop): only those frames are emitted, and only the
-    GOPs that cover them are decoded; the other records are stepped over.
+    GOPs that cover them are decoded; the other records are stepped over.  On a hashed file (encode_sequence(state_hash=True)) with
+    verify=True every decoded frame's y_hat -- also of frames decoded for the chain's sake only -- is hashed and compared with the
+    file's entry before it becomes a condition or a picture: StateMismatch at the first difference.  verify=False, or an un-hashed
+    file: nothing is hashed.
     -> the cropped x_hat tensors [1,3,h,w] of the emitted frames in display order (an empty list with return_frames=False)"""
-    from . import codec, evaluation
+    from . import evaluation
     from . import functional as F
-    if isinstance(src, (bytes, bytearray, memoryview)):
-        data = bytes(src)
-    else:
-        fd, close = _open(src, "rb")
-        try:
-            data = fd.read()
-        finally:
-            if close:
-                fd.close()
+    data = _read_all(src)
     hdr = FileHeader.unpack(data)
     check_header(hdr, imodel, stem)
-    ranges = record_ranges(data, hdr.frames)
+    ranges, want = hashed_record_ranges(data, hdr)
     types = hdr.types()
+    starts = gop_starts(types)
     start, stop = (0, hdr.frames) if frames is None else (int(frames[0]), int(frames[1]))
     steps = decode_steps(types, concurrent_gops, start, stop)
     h, w = hdr.height, hdr.width
@@ -425,28 +559,14 @@ def decode_sequence(imodel, stem, src, write_to=None, concurrent_gops=8, frames=
         kept, y_cond = [None] * (stop - start), {}
         for step in steps:
             recs = [_read_record(data, ranges[i], hdr, i) for i, _, _ in step]
-            y_hat, x_hat = [None] * len(step), [None] * len(step)
-            for kind in ("I", "P"):
-                pos = [k for k, (_, t, _) in enumerate(step) if t == kind]
-                if not pos:
-                    continue
-                orders = {recs[k][0] for k in pos}
-                if len(orders) != 1:
-                    raise ValueError(f"the {kind} records of frames {[step[k][0] for k in pos]} mix symbol orders")
-                o = orders.pop()
-                strings, shapes = [recs[k][2] for k in pos], [recs[k][1] for k in pos]
-                if kind == "I" and getattr(imodel, "HAS_SPM", False):
-                    outs = codec.iframe_decompress_each(imodel, strings, shapes, order=o)
-                elif kind == "I":
-                    if o != "raster":
-                        raise ValueError(f"{hdr.imodel_name} codes in one shot: its records cannot be in wavefront order")
-                    outs = [imodel.decompress(s, sh) for s, sh in zip(strings, shapes)]
-                else:
-                    ys = codec.stem_decompress_each(stem, strings, shapes, [y_cond[step[k][2]] for k in pos], order=o)
-                    outs = [{"y_hat": y, "x_hat": imodel.getX(y)} for y in ys]
-                for k, d in zip(pos, outs):
-                    y_hat[k], x_hat[k] = d["y_hat"], d["x_hat"]
-            for k, (index, _, _) in enumerate(step):
+            y_hat, x_hat = _decode_step(imodel, stem, hdr, step, recs, y_cond)
+            if verify and want is not None:
+                for (index, _, _), got in zip(step, _hash_states(y_hat)):
+                    if got != want[index]:
+                        raise StateMismatch(index, starts[index], want[index], got)
+            for k, (index, kind, _) in enumerate(step):
+                if kind == "P":
+                    x_hat[k] = imodel.getX(y_hat[k])
                 if index < start:
                     continue                                                          # decoded for the chain's sake only
                 if writer is not None:
@@ -458,6 +578,43 @@ def decode_sequence(imodel, stem, src, write_to=None, concurrent_gops=8, frames=
         if close:
             sink.close()
     return kept if return_frames else []
+
+
+@torch.no_grad()
+def verify_sequence(imodel, stem, src, concurrent_gops=8):
+    """Check a hashed file against this decoder without making a picture: latents only -- neither getX nor g_s runs.  Every GOP is an
+    independent chain and is checked on its own: at its first frame whose decoded y_hat does not hash to the file's entry the GOP is
+    abandoned (what follows would be decoded under a wrong condition) and the other GOPs go on.
+    -> {"frames": n, "checked": frames hashed, "mismatches": [{"frame", "gop_start", "want", "got"}], "unchecked": [frames skipped behind
+    a mismatch]}, indices ascending.  ValueError for an un-hashed file: there is nothing to check it against."""
+    data = _read_all(src)
+    hdr = FileHeader.unpack(data)
+    check_header(hdr, imodel, stem)
+    ranges, want = hashed_record_ranges(data, hdr)
+    if want is None:
+        raise ValueError("the file carries no state hashes (it was written without state_hash=True): nothing to verify it against")
+    types = hdr.types()
+    starts = gop_starts(types)
+    checked, mismatches, dead, y_cond = 0, [], set(), {}
+    for step in decode_steps(types, concurrent_gops):
+        step = [s for s in step if starts[s[0]] not in dead]
+        if not step:
+            continue
+        recs = [_read_record(data, ranges[i], hdr, i) for i, _, _ in step]
+        y_hat, _ = _decode_step(imodel, stem, hdr, step, recs, y_cond, latents_only=True)
+        y_next = {}
+        for k, ((index, _, chain), got) in enumerate(zip(step, _hash_states(y_hat))):
+            checked += 1
+            if got != want[index]:
+                mismatches.append({"frame": index, "gop_start": starts[index], "want": want[index], "got": got})
+                dead.add(starts[index])
+            else:
+                y_next[chain] = y_hat[k]
+        y_cond = y_next
+    mismatches.sort(key=lambda m: m["frame"])
+    bad = {m["gop_start"]: m["frame"] for m in mismatches}
+    unchecked = [i for i in range(hdr.frames) if starts[i] in bad and i > bad[starts[i]]]
+    return {"frames": hdr.frames, "checked": checked, "mismatches": mismatches, "unchecked": unchecked}
 
 
 # ---- the command line ----------------------------------------------------------------------------------------------------------
@@ -495,18 +652,27 @@ def load_stem(cls_name, path, device):
     return net.to(device).eval()
 
 
+def print_report(report):
+    """verify_sequence's report as one JSON line on stdout, hashes in hex -> the exit status: 0 when clean, 3 on any mismatch"""
+    import json
+    out = dict(report, mismatches=[dict(m, want=f"{m['want']:016x}", got=f"{m['got']:016x}") for m in report["mismatches"]])
+    print(json.dumps(out))
+    return 3 if report["mismatches"] else 0
+
+
 def _parser():
     import argparse
     p = argparse.ArgumentParser(prog="python -m spatiotemporalentropymodel_amd.video", description="stand-alone sequence codec")
     sub = p.add_subparsers(dest="command", required=True)
-    for name in ("encode", "decode"):
+    for name in ("encode", "decode", "verify"):
         s = sub.add_parser(name)
         s.add_argument("--imodel", required=True, help="zoo name of the I-frame model")
         s.add_argument("--imodel-checkpoint", required=True)
         s.add_argument("--stem", default=None, help="STEM class name (not needed for an all-intra file)")
         s.add_argument("--stem-checkpoint", default=None)
         s.add_argument("--input", required=True)
-        s.add_argument("--output", required=True)
+        if name != "verify":
+            s.add_argument("--output", required=True)
         s.add_argument("--concurrent-gops", type=int, default=8)
         s.add_argument("--device", default="cuda:0")
     e, d = sub.choices["encode"], sub.choices["decode"]
@@ -518,12 +684,15 @@ def _parser():
     e.add_argument("--all-intra", action="store_true")
     e.add_argument("--order", default="raster", choices=("raster", "wavefront"))
     e.add_argument("--quality", type=int, default=4)
+    e.add_argument("--state-hash", action="store_true", help="write a hashed file: every frame's conditioning state, checked while decoding")
     d.add_argument("--frames", default=None, help="START:STOP, decode only these frames")
+    d.add_argument("--no-verify", action="store_true", help="do not check a hashed file's state hashes")
     return p
 
 
 def main(argv=None):
-    """-> the exit status: 0, or 2 after a refusal (ValueError), whose message goes to stderr"""
+    """-> the exit status: 0; 2 after a refusal (ValueError), whose message goes to stderr; 3 when a state hash did not match (`verify`
+    prints its report as JSON either way, `decode` stops at the first one)"""
     args = _parser().parse_args(argv)
     try:
         if (args.stem is None) != (args.stem_checkpoint is None):
@@ -534,8 +703,10 @@ def main(argv=None):
             from . import data
             seq = data.YUVSequence(args.input, args.width, args.height, args.bit_depth, frames=args.frames, device=args.device)
             res = encode_sequence(imodel, stem, seq, args.output, gop=args.gop, concurrent_gops=args.concurrent_gops, all_intra=args.all_intra,
-                                  order=args.order, quality=args.quality)
+                                  order=args.order, quality=args.quality, state_hash=args.state_hash)
             print(f"{len(res['frames'])} frames, {res['bytes']} bytes, {res['bpp_ave']:.6f} bpp")
+        elif args.command == "verify":
+            return print_report(verify_sequence(imodel, stem, args.input, concurrent_gops=args.concurrent_gops))
         else:
             rng = None
             if args.frames is not None:
@@ -544,8 +715,12 @@ def main(argv=None):
                     assert len(rng) == 2
                 except (ValueError, AssertionError):
                     raise ValueError(f"--frames is START:STOP, got {args.frames!r}") from None
-            decode_sequence(imodel, stem, args.input, write_to=args.output, concurrent_gops=args.concurrent_gops, frames=rng, return_frames=False)
+            decode_sequence(imodel, stem, args.input, write_to=args.output, concurrent_gops=args.concurrent_gops, frames=rng, return_frames=False,
+                            verify=not args.no_verify)
             print(f"decoded {args.input} into {args.output}")
+    except StateMismatch as e:
+        print(f"mismatch: {e}", file=sys.stderr)
+        return 3
     except ValueError as e:
         print(f"refused: {e}", file=sys.stderr)
         return 2

@@ -4,7 +4,8 @@ thing for the latent-domain STEM pairs; this module reuses its container helpers
 
     encode_sequence(model_i, model_p, frames, out, qmaps=... | rois=..., ...)    frames (+ maps or rectangles) -> file; no decompress
     decode_sequence(model_i, model_p, src, write_to=None, ...)                   file -> planar 4:2:0 frames (and the cropped x_hat)
-    python -m spatiotemporalentropymodel_amd.video_pixel encode|decode ...
+    verify_sequence(model_i, model_p, src)                                       file -> a report: every frame's state hash checked
+    python -m spatiotemporalentropymodel_amd.video_pixel encode|decode|verify ...
 
 evaluation.eval_gop_pixel compresses and decompresses every frame with the same objects, takes its quality maps as host tensors and
 crops and re-pads the reconstruction with eager torch between frames.  Here a frame costs the encoder one compress: the reconstruction
@@ -31,6 +32,11 @@ A record's first byte is the I kind for an I record and 128 + the P kind for a P
 an I-frame model of the zoo an I record therefore is byte for byte the record the reference's tool writes for that image.  The
 fingerprint is video.fingerprint.  The quality map is not in the file: it is encoder-side information, the decoder derives its
 modulation from z_hat (PDecoder).
+
+State hashes (opt-in, encode_sequence(state_hash=True); the format change is video.py's: bit 7 of the version byte, a trailer of `frames`
+u64 behind the last record).  The hashed state of a frame is its padded x_hat AFTER functional.rgb_window_recondition -- the whole padded
+tensor with its border zeroed, exactly the next P frame's condition.  Here the state is a picture, so checking it needs the synthesis:
+verify_sequence runs the whole decoder and only leaves out the planes and the file.
 """
 from __future__ import annotations
 
@@ -41,7 +47,8 @@ import sys
 import torch
 
 from . import bitstream
-from .video import _open, _planes_bytes, _Source, decode_steps, fingerprint, frame_types, record_ranges
+from .video import (STATE_HASH_BIT, StateMismatch, _open, _planes_bytes, _read_all, _read_state_hashes, _Source, decode_steps, fingerprint,
+                    frame_types, gop_starts, hashed_record_ranges, print_report, record_ranges, trailer_bytes)
 
 MAGIC = b"STPX"
 VERSION = 1
@@ -64,26 +71,28 @@ def _check_sides(h, w):
 
 
 class FileHeader:
-    """the file header as attributes (`_FIELDS`); `pack()` <-> `unpack(bytes)`"""
+    """the file header as attributes (`_FIELDS`); `pack()` <-> `unpack(bytes)`.  `state_hash` (outside `_FIELDS`: a bit of the version
+    byte, video.STATE_HASH_BIT) says that the file ends in a trailer of state hashes."""
 
-    def __init__(self, **kw):
+    def __init__(self, state_hash=False, **kw):
         if set(kw) != set(_FIELDS):
             raise TypeError(f"FileHeader takes exactly {_FIELDS}, got {sorted(kw)}")
         for k in _FIELDS:
             setattr(self, k, int(kw[k]))
+        self.state_hash = bool(state_hash)
 
     def astuple(self):
         return tuple(getattr(self, k) for k in _FIELDS)
 
     def __eq__(self, other):
-        return isinstance(other, FileHeader) and self.astuple() == other.astuple()
+        return isinstance(other, FileHeader) and self.astuple() == other.astuple() and self.state_hash == other.state_hash
 
     def __repr__(self):
-        return "FileHeader(" + ", ".join(f"{k}={getattr(self, k)}" for k in _FIELDS) + ")"
+        return "FileHeader(" + ", ".join(f"{k}={getattr(self, k)}" for k in _FIELDS) + (", state_hash=True" if self.state_hash else "") + ")"
 
     def pack(self):
         self.check()
-        return _HEADER.pack(MAGIC, VERSION, *self.astuple())
+        return _HEADER.pack(MAGIC, VERSION | (STATE_HASH_BIT if self.state_hash else 0), *self.astuple())
 
     @classmethod
     def unpack(cls, data):
@@ -94,9 +103,9 @@ class FileHeader:
             raise ValueError("this is a file of the latent-domain codec (magic b'STMV'): read it with spatiotemporalentropymodel_amd.video")
         if magic != MAGIC:
             raise ValueError(f"not a pixel-domain sequence file: magic {magic!r}, expected {MAGIC!r}")
-        if version != VERSION:
-            raise ValueError(f"pixel-domain sequence file version {version}, this module reads version {VERSION}")
-        hdr = cls(**dict(zip(_FIELDS, rest)))
+        if version & ~STATE_HASH_BIT != VERSION:
+            raise ValueError(f"pixel-domain sequence file version {version & ~STATE_HASH_BIT}, this module reads version {VERSION}")
+        hdr = cls(state_hash=bool(version & STATE_HASH_BIT), **dict(zip(_FIELDS, rest)))
         hdr.check()
         return hdr
 
@@ -163,12 +172,12 @@ def _takes_qmap(model):
     return bool(getattr(model, "QMAP", False))
 
 
-def _header_for(model_i, model_p, h, w, bit_depth, n, gop, all_intra, quality):
+def _header_for(model_i, model_p, h, w, bit_depth, n, gop, all_intra, quality, state_hash=False):
     types = frame_types(n, gop, all_intra)
     (ik, ia, ib), p = _check_models(model_i, model_p, "P" in types)
     pk, pa, pb = p if p is not None else (NO_P, 0, 0)
-    return FileHeader(width=w, height=h, bit_depth=bit_depth, frames=n, gop=gop, all_intra=int(bool(all_intra)), quality=quality, i_kind=ik, i_a=ia,
-                      i_b=ib, i_crc=fingerprint(model_i), p_kind=pk, p_a=pa, p_b=pb, p_crc=fingerprint(model_p) if p is not None else 0)
+    return FileHeader(state_hash=state_hash, width=w, height=h, bit_depth=bit_depth, frames=n, gop=gop, all_intra=int(bool(all_intra)),
+                      quality=quality, i_kind=ik, i_a=ia, i_b=ib, i_crc=fingerprint(model_i), p_kind=pk, p_a=pa, p_b=pb, p_crc=fingerprint(model_p) if p is not None else 0)
 
 
 def check_header(hdr, model_i, model_p):
@@ -220,6 +229,11 @@ def read_record(data, rng, hdr, index, kind):
     return (s0, s1), strings
 
 
+def read_state_hashes(data):
+    """video.read_state_hashes for this module's files: the state hashes in display order, or None for an un-hashed file"""
+    return _read_state_hashes(data, FileHeader, HEADER_BYTES)
+
+
 # ---- maps ----------------------------------------------------------------------------------------------------------------------
 def _map_source(qmaps, rois, level, h, w, device):
     """-> a function index -> the padded quality map [1,1,Hp,Wp] on the device, or None; to be called once per frame, in order"""
@@ -255,7 +269,7 @@ def _device_of(model):
 
 # ---- the encoder ---------------------------------------------------------------------------------------------------------------
 @torch.no_grad()
-def encode_sequence(model_i, model_p, frames, out, *, qmaps=None, rois=None, level=0.0, gop=12, all_intra=False, quality=4):
+def encode_sequence(model_i, model_p, frames, out, *, qmaps=None, rois=None, level=0.0, gop=12, all_intra=False, quality=4, state_hash=False):
     """Code `frames` (a data.YUVSequence, or a sequence of [3,h,w] tensors in [0,1] of one size; plain tensors make an 8-bit file) into
     `out` (a path or a binary file object).  Frame types are evaluation.eval_gop_pixel's; every record holds the strings and the shape
     it gives for that frame with the same maps.  qmaps: its four forms (None; one map for every frame; an iterable parallel to the
@@ -263,12 +277,15 @@ def encode_sequence(model_i, model_p, frames, out, *, qmaps=None, rois=None, lev
     (x0, y0, x1, y1, value[, feather]) for every frame, or a callable index -> such a list, rasterised on the device over the
     background `level` (functional.roi_map_padded).  A map goes only to the models that take one (QMAP).  Per frame: one compress with
     the reconstruction from the encoder's own symbols, one kernel that makes it the next condition in place, one record; no decompress.
-    model_p may be None with all_intra=True.
-    -> {"frames": [{"type", "bytes", "bpp"}] in display order, "bytes": the file's size, "bpp_ave"}"""
+    model_p may be None with all_intra=True.  state_hash=True: a hashed file -- bit 7 of the version byte and, behind the last record,
+    every frame's functional.state_hash of the reconditioned padded x_hat (the next condition); the hashes collect in one device buffer
+    that one copy fetches at the end.  The records are those of the un-hashed file.
+    -> {"frames": [{"type", "bytes", "bpp"}] in display order, "bytes": the file's size, "bpp_ave"} and, with state_hash, "state_hash":
+    the hashes in display order"""
     from . import functional as F
     device = _device_of(model_i)
     src = _Source(frames, device)
-    hdr = _header_for(model_i, model_p, src.h, src.w, src.bit_depth, src.n, gop, all_intra, quality)
+    hdr = _header_for(model_i, model_p, src.h, src.w, src.bit_depth, src.n, gop, all_intra, quality, state_hash)
     types = hdr.types()
     coders = [model_i] + ([model_p] if "P" in types else [])
     given = qmaps is not None or rois is not None
@@ -286,6 +303,7 @@ def encode_sequence(model_i, model_p, frames, out, *, qmaps=None, rois=None, lev
     try:
         fd.write(hdr.pack())
         per_frame, x_cond = [], None
+        hbuf = torch.empty(src.n, dtype=torch.int64, device=device) if state_hash else None
         for index, kind in enumerate(types):
             model = model_i if kind == "I" else model_p
             x = src.padded(index)
@@ -303,45 +321,46 @@ def encode_sequence(model_i, model_p, frames, out, *, qmaps=None, rois=None, lev
                 x_hat = enc["x_hat"]
             F.rgb_window_recondition(x_hat, (h, w))
             x_cond = x_hat
+            if state_hash:
+                F.state_hash(x_hat, out=hbuf[index:index + 1])
             rec = record_bytes(hdr.record_byte(kind), quality, (h, w), enc["shape"], enc["strings"])
             fd.write(rec)
             bits = sum(len(s[0]) for s in enc["strings"]) * 8.0
             per_frame.append({"type": kind, "bytes": len(rec), "bpp": bits / (h * w)})
+        hashes = F.state_hash_ints(hbuf) if state_hash else None
+        if state_hash:
+            fd.write(trailer_bytes(hashes))
     finally:
         if close:
             fd.close()
-    return {"frames": per_frame, "bytes": HEADER_BYTES + sum(f["bytes"] for f in per_frame),
-            "bpp_ave": sum(f["bpp"] for f in per_frame) / len(per_frame)}
+    res = {"frames": per_frame, "bytes": HEADER_BYTES + sum(f["bytes"] for f in per_frame) + (8 * src.n if state_hash else 0),
+           "bpp_ave": sum(f["bpp"] for f in per_frame) / len(per_frame)}
+    if state_hash:
+        res["state_hash"] = hashes
+    return res
 
 
 # ---- the decoder ---------------------------------------------------------------------------------------------------------------
-def _read_all(src):
-    if isinstance(src, (bytes, bytearray, memoryview)):
-        return bytes(src)
-    fd, close = _open(src, "rb")
-    try:
-        return fd.read()
-    finally:
-        if close:
-            fd.close()
-
-
 @torch.no_grad()
-def decode_sequence(model_i, model_p, src, write_to=None, frames=None, return_frames=True):
+def decode_sequence(model_i, model_p, src, write_to=None, frames=None, return_frames=True, verify=True):
     """Decode the file `src` (a path, bytes, or a binary file object) with nothing but the file and the two models: the quality map is
     encoder-side information and is not needed -- the decoder derives its modulation from z_hat (PDecoder).  The header is checked
     against the models (`check_header`: kind, widths, fingerprint), then every GOP is rebuilt from its records: I frames by model_i's
     decompress, P frames by model_p's given the previous frame's reconstruction.  One kernel per frame
     (functional.rgb_window_recondition) makes the decoded padded frame the next condition in place and, when write_to (a path or a
     binary file object) is given, writes the frame's planar 4:2:0 samples at the file's bit depth in the same pass.
-    frames=(start, stop): only those frames are emitted, and only the GOPs that cover them are decoded.
+    frames=(start, stop): only those frames are emitted, and only the GOPs that cover them are decoded.  On a hashed file
+    (encode_sequence(state_hash=True)) with verify=True every decoded frame's reconditioned x_hat -- also of frames decoded for the
+    chain's sake only -- is hashed and compared with the file's entry before it becomes a condition or leaves as a picture:
+    video.StateMismatch at the first difference.  verify=False, or an un-hashed file: nothing is hashed.
     -> the cropped x_hat tensors [1,3,h,w] of the emitted frames in display order, as copies (an empty list with return_frames=False)"""
     from . import functional as F
     data = _read_all(src)
     hdr = FileHeader.unpack(data)
-    ranges = record_ranges(data, hdr.frames, HEADER_BYTES)                           # the file's own consistency first: it costs nothing
+    ranges, want = hashed_record_ranges(data, hdr, HEADER_BYTES)                     # the file's own consistency first: it costs nothing
     check_header(hdr, model_i, model_p)
     types = hdr.types()
+    starts = gop_starts(types)
     start, stop = (0, hdr.frames) if frames is None else (int(frames[0]), int(frames[1]))
     steps = decode_steps(types, 1, start, stop)
     h, w = hdr.height, hdr.width
@@ -356,6 +375,10 @@ def decode_sequence(model_i, model_p, src, write_to=None, frames=None, return_fr
                 x_hat = model_p.decompress(strings, shape, x_cond)["x_hat"]
             emit = index >= start                                                     # otherwise decoded for the chain's sake only
             planes = F.rgb_window_recondition(x_hat, (h, w), hdr.bit_depth if emit and sink is not None else None)
+            if verify and want is not None:
+                got = F.state_hash_ints(F.state_hash(x_hat))[0]
+                if got != want[index]:
+                    raise StateMismatch(index, starts[index], want[index], got)
             x_cond = x_hat
             if planes is not None:
                 sink.write(_planes_bytes(planes))
@@ -366,6 +389,40 @@ def decode_sequence(model_i, model_p, src, write_to=None, frames=None, return_fr
         if close:
             sink.close()
     return kept
+
+
+@torch.no_grad()
+def verify_sequence(model_i, model_p, src):
+    """Check a hashed file against this decoder: every GOP is decoded on its own (the state is a picture, so the synthesis runs; no
+    planes, no file) and every frame's reconditioned x_hat is hashed and compared with the file's entry.  A GOP is abandoned at its
+    first mismatch -- what follows would be decoded under a wrong condition -- and the next GOP goes on.
+    -> video.verify_sequence's report: {"frames", "checked", "mismatches": [{"frame", "gop_start", "want", "got"}], "unchecked"}.
+    ValueError for an un-hashed file."""
+    from . import functional as F
+    data = _read_all(src)
+    hdr = FileHeader.unpack(data)
+    ranges, want = hashed_record_ranges(data, hdr, HEADER_BYTES)
+    check_header(hdr, model_i, model_p)
+    if want is None:
+        raise ValueError("the file carries no state hashes (it was written without state_hash=True): nothing to verify it against")
+    types = hdr.types()
+    starts = gop_starts(types)
+    h, w = hdr.height, hdr.width
+    checked, mismatches, unchecked, dead, x_cond = 0, [], [], None, None
+    for index, kind in enumerate(types):
+        if dead == starts[index]:
+            unchecked.append(index)
+            continue
+        shape, strings = read_record(data, ranges[index], hdr, index, kind)
+        x_hat = model_i.decompress(strings, shape)["x_hat"] if kind == "I" else model_p.decompress(strings, shape, x_cond)["x_hat"]
+        F.rgb_window_recondition(x_hat, (h, w))
+        got = F.state_hash_ints(F.state_hash(x_hat))[0]
+        checked += 1
+        if got != want[index]:
+            mismatches.append({"frame": index, "gop_start": starts[index], "want": want[index], "got": got})
+            dead = starts[index]
+        x_cond = x_hat
+    return {"frames": hdr.frames, "checked": checked, "mismatches": mismatches, "unchecked": unchecked}
 
 
 # ---- the command line ----------------------------------------------------------------------------------------------------------
@@ -431,14 +488,15 @@ def _parser():
     import argparse
     p = argparse.ArgumentParser(prog="python -m spatiotemporalentropymodel_amd.video_pixel", description="stand-alone pixel-domain sequence codec")
     sub = p.add_subparsers(dest="command", required=True)
-    for name in ("encode", "decode"):
+    for name in ("encode", "decode", "verify"):
         s = sub.add_parser(name)
         s.add_argument("--model-i", required=True, help="stem_roi_i, or the zoo name of an I-frame model")
         s.add_argument("--model-i-checkpoint", required=True)
         s.add_argument("--model-p", default=None, help=f"one of {PIXEL_P_CLASSES} (not needed for an all-intra file)")
         s.add_argument("--model-p-checkpoint", default=None)
         s.add_argument("--input", required=True)
-        s.add_argument("--output", required=True)
+        if name != "verify":
+            s.add_argument("--output", required=True)
         s.add_argument("--device", default="cuda:0")
     e, d = sub.choices["encode"], sub.choices["decode"]
     e.add_argument("--width", type=int, required=True)
@@ -451,7 +509,9 @@ def _parser():
     e.add_argument("--level", type=float, default=None, help="the quality level outside every rectangle, in [0, 1]")
     e.add_argument("--roi", action="append", default=[], help="x0,y0,x1,y1,value[,feather]: a rectangle of every frame (repeatable)")
     e.add_argument("--roi-file", default=None, help="lines `frame x0 y0 x1 y1 value [feather]`; # starts a comment")
+    e.add_argument("--state-hash", action="store_true", help="write a hashed file: every frame's conditioning state, checked while decoding")
     d.add_argument("--frames", default=None, help="START:STOP, decode only these frames")
+    d.add_argument("--no-verify", action="store_true", help="do not check a hashed file's state hashes")
     return p
 
 
@@ -468,7 +528,8 @@ def _cli_rois(args):
 
 
 def main(argv=None):
-    """-> the exit status: 0, or 2 after a refusal (ValueError), whose message goes to stderr"""
+    """-> the exit status: 0; 2 after a refusal (ValueError), whose message goes to stderr; 3 when a state hash did not match (`verify`
+    prints its report as JSON either way, `decode` stops at the first one)"""
     args = _parser().parse_args(argv)
     try:
         if (args.model_p is None) != (args.model_p_checkpoint is None):
@@ -480,8 +541,10 @@ def main(argv=None):
             from . import data
             seq = data.YUVSequence(args.input, args.width, args.height, args.bit_depth, frames=args.frames, device=args.device)
             res = encode_sequence(model_i, model_p, seq, args.output, rois=rois, level=args.level if args.level is not None else 0.0, gop=args.gop,
-                                  all_intra=args.all_intra, quality=args.quality)
+                                  all_intra=args.all_intra, quality=args.quality, state_hash=args.state_hash)
             print(f"{len(res['frames'])} frames, {res['bytes']} bytes, {res['bpp_ave']:.6f} bpp")
+        elif args.command == "verify":
+            return print_report(verify_sequence(model_i, model_p, args.input))
         else:
             rng = None
             if args.frames is not None:
@@ -490,8 +553,11 @@ def main(argv=None):
                     assert len(rng) == 2
                 except (ValueError, AssertionError):
                     raise ValueError(f"--frames is START:STOP, got {args.frames!r}") from None
-            decode_sequence(model_i, model_p, args.input, write_to=args.output, frames=rng, return_frames=False)
+            decode_sequence(model_i, model_p, args.input, write_to=args.output, frames=rng, return_frames=False, verify=not args.no_verify)
             print(f"decoded {args.input} into {args.output}")
+    except StateMismatch as e:
+        print(f"mismatch: {e}", file=sys.stderr)
+        return 3
     except ValueError as e:
         print(f"refused: {e}", file=sys.stderr)
         return 2

@@ -2,7 +2,7 @@
 beside the compositions they fold.
 
     python tools/pixel_codec_bench.py [--frames 12] [--gop 12] [--reps 3] [--launches 60]
-                                      [--part all|baseline] [--baseline FILE] [--out profiles/pixel_codec.json]
+                                      [--part all|baseline] [--baseline FILE] [--out profiles/pixel_codec.json] [--state-hash]
 
 Workload: `--frames` synthetic 1080p frames quantised to a raw 4:2:0 file at 8 and at 10 bits, gop `--gop`, stem_roi_i + stem_roi on
 closed-form weights (convolutions scaled by 0.7, as the tests' fixtures), four feathered rectangles per frame over the level 0.3.
@@ -20,6 +20,12 @@ closed-form weights (convolutions scaled by 0.7, as the tests' fixtures), four f
 
 `--part baseline` runs only what exists without video_pixel.py -- eval_gop_pixel and the compositions -- so that the same file, copied into
 a checkout of the parent commit, measures the parent in the same session; `--baseline FILE` puts that run's JSON under "parent".
+
+`--state-hash` measures the opt-in per-frame state hashes instead and writes (merges) the key "pixel" of profiles/state_hash.json
+(tools/video_codec_bench.py --state-hash writes "latent" and "kernel"): at 8 bits, alternating, `--reps` passes each -- encode_sequence
+without and with state_hash=True, decode_sequence of the un-hashed file, of the hashed file with and without verify, and verify_sequence,
+every repeat listed so that the spread shows.  With `--part baseline` only encode_sequence and decode_sequence run, without the new
+keywords: the parent commit's figures by the same tool in the same session (`--baseline FILE` stores them under "pixel"/"parent").
 Nothing is gated on these numbers.  Needs an MI355X: without a GPU it fails, it measures nothing on a CPU.
 """
 import argparse
@@ -133,6 +139,61 @@ def time_sequence(model_i, model_p, bits, args, tmp, baseline_only):
     return res
 
 
+def state_hash_main(args):
+    from spatiotemporalentropymodel_amd import data, video_pixel
+    dev = torch.device("cuda", 0)
+    base = args.part == "baseline"
+    res = {"device": torch.cuda.get_device_name(0), "part": args.part,
+           "workload": f"{args.frames} synthetic {W}x{H} frames at 8 bits, gop {args.gop}, stem_roi_i + stem_roi on closed-form weights, four "
+                       f"rectangles per frame over level {LEVEL}"}
+    with torch.no_grad(), tempfile.TemporaryDirectory() as tmp:
+        model_i, model_p = _models(dev)
+        raw = os.path.join(tmp, "src8.yuv")
+        _write_source(raw, args.frames, 8, dev)
+        seq = data.YUVSequence(raw, W, H, bit_depth=8, device=dev)
+        rois = [_boxes(t) for t in range(args.frames)]
+        plain, hashed, out = os.path.join(tmp, "plain.stpx"), os.path.join(tmp, "hashed.stpx"), os.path.join(tmp, "dec.yuv")
+        kw = dict(rois=rois, level=LEVEL, gop=args.gop)
+        routes = {"encode_sequence": lambda: video_pixel.encode_sequence(model_i, model_p, seq, plain, **kw),
+                  "decode_sequence": lambda: video_pixel.decode_sequence(model_i, model_p, plain, write_to=out, return_frames=False)}
+        if not base:
+            routes.update({
+                "encode_sequence_state_hash": lambda: video_pixel.encode_sequence(model_i, model_p, seq, hashed, state_hash=True, **kw),
+                "decode_sequence_verified": lambda: video_pixel.decode_sequence(model_i, model_p, hashed, write_to=out, return_frames=False),
+                "decode_sequence_verify_false": lambda: video_pixel.decode_sequence(model_i, model_p, hashed, write_to=out, return_frames=False,
+                                                                                    verify=False),
+                "verify_sequence": lambda: video_pixel.verify_sequence(model_i, model_p, hashed)})
+        for fn in routes.values():
+            fn()
+        times = {k: [] for k in routes}
+        for _ in range(args.reps):
+            for k, fn in routes.items():                         # alternating
+                times[k].append(_timed(fn) / args.frames)
+        res.update({"bits": 8, "frames": args.frames, "gop": args.gop, "reps": args.reps,
+                    "seconds_per_frame": {k: dict(_pct(v), repeats=v) for k, v in times.items()}})
+        if not base:
+            a, b = open(plain, "rb").read(), open(hashed, "rb").read()
+            res["records_equal_the_unhashed_files"] = b[5:len(a)] == a[5:] and len(b) == len(a) + 8 * args.frames
+            res["verify_report"] = video_pixel.verify_sequence(model_i, model_p, hashed)
+            m = {k: v["median"] for k, v in res["seconds_per_frame"].items()}
+            res["encode_with_hashes_over_without"] = m["encode_sequence_state_hash"] / m["encode_sequence"]
+            res["decode_verified_over_unhashed"] = m["decode_sequence_verified"] / m["decode_sequence"]
+            res["verify_sequence_over_decode_sequence"] = m["verify_sequence"] / m["decode_sequence"]
+    if args.baseline:
+        with open(args.baseline) as f:
+            res["parent"] = json.load(f)
+    merged = {}
+    if not base and os.path.exists(args.out):
+        with open(args.out) as f:
+            merged = json.load(f)
+    merged = res if base else dict(merged, pixel=res)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(merged, f, indent=1)
+        f.write("\n")
+    print(json.dumps(merged))
+
+
 def _alternate(fns, launches, warmup=10):
     for _ in range(warmup):
         for fn in fns.values():
@@ -190,11 +251,15 @@ def main():
     ap.add_argument("--launches", type=int, default=60)
     ap.add_argument("--part", default="all", choices=("all", "baseline"))
     ap.add_argument("--baseline", default=None, help="JSON of a `--part baseline` run on the parent commit, stored under \"parent\"")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "pixel_codec.json"))
+    ap.add_argument("--state-hash", action="store_true", help="measure the per-frame state hashes into profiles/state_hash.json instead")
+    ap.add_argument("--out", default=None, help="default: profiles/pixel_codec.json, with --state-hash profiles/state_hash.json")
     args = ap.parse_args()
+    args.out = args.out or os.path.join(REPO, "profiles", "state_hash.json" if args.state_hash else "pixel_codec.json")
     if not torch.cuda.is_available():
         sys.exit("pixel_codec_bench: no GPU -- this tool measures on an MI355X and has no other mode")
     torch.cuda.set_device(0)
+    if args.state_hash:
+        return state_hash_main(args)
     dev = torch.device("cuda", 0)
     base = args.part == "baseline"
     res = {"device": torch.cuda.get_device_name(0), "part": args.part,
