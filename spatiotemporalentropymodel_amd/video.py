@@ -12,33 +12,21 @@ buffer, the one-shot coder has the symbols and the means (`return_y_hat=True` of
 frames costs N encodes here, not N encodes and N decodes, and every record is the bytes eval_gop produces for that frame: GOPs are
 independent chains that advance side by side (evaluation.gop_schedule, the `*_each` entry points), transforms at batch 1.
 
-File layout (all integers big-endian, as in bitstream.py):
+File layout (seqfile.py's container -- frame types, record ranges, the state-hash trailer, the fingerprint and the order of checks are
+stated there -- with this header and this record rule; all integers big-endian):
 
     header   4s magic "STMV" | u8 version | u32 w | u32 h | u8 bit depth | u32 frames | u32 gop | u8 all_intra | u8 quality
              | u8 I-frame model id (bitstream.model_ids) | u16 N | u16 M | u32 fingerprint
              | u8 STEM class (index in STEM_CLASSES; 255: none, an all-intra file) | u16 N | u16 M | u32 fingerprint
     records  one per frame in display order, each written by bitstream.write_frame and read by bitstream.read_frame
 
-Frame k is an I or a P frame by its index and `gop` (evaluation.gop_schedule's rule), so a record needs no type field.  Every record's
-2-byte header names the I-FRAME model, also a P record's: the container's ids are the six zoo names, the STEM classes have none, and a P
-frame is a frame of that image model's latent space -- its g_s turns the decoded latent into pixels.  An I record therefore is byte for
-byte the record the reference's tool writes for that image.  Bit 7 of the second header byte marks wavefront symbol order
-(bitstream.ORDER_BIT).  A record is skipped without parsing its strings, by the length prefixes (`record_ranges`): decoding
-frames=(start, stop) touches only the GOPs that cover the range.
+Every record's 2-byte header names the I-FRAME model, also a P record's: the container's ids are the six zoo names, the STEM classes
+have none, and a P frame is a frame of that image model's latent space -- its g_s turns the decoded latent into pixels.  An I record
+therefore is byte for byte the record the reference's tool writes for that image.  Bit 7 of the second header byte marks wavefront
+symbol order (bitstream.ORDER_BIT).
 
-State hashes (opt-in: encode_sequence(state_hash=True), `encode --state-hash`).  The codec is closed-loop: frame t is decoded under
-priors computed from the decoder's own y_hat of frame t - 1, so a decoder whose arithmetic differs in one last bit -- another tile plan,
-another build of the library -- decodes plausible garbage from there to the end of the GOP.  A hashed file carries bit 7 in its version
-byte (STATE_HASH_BIT, in the manner of bitstream.ORDER_BIT) and, behind the last record, a trailer of `frames` u64: per frame in display
-order, functional.state_hash of the y_hat the next P frame is conditioned on, from the encoder's own reconstruction.  Header and records
-are byte for byte the un-hashed file's but for that bit; the trailer sits 8 * frames bytes from the end, so a partial decode finds its
-entries without parsing further.  decode_sequence compares every decoded frame's hash BEFORE the state becomes a condition and raises
-StateMismatch; verify_sequence checks a whole file on latents alone.  The hash covers the conditioning state: it proves that every
-symbol and every prior matched, not that g_s of an equal y_hat gives equal pixels.
-
-The fingerprint is zlib.crc32 over a model's state_dict in key order: each key's name, then the tensor's bytes (a masked convolution's
-weight through its mask: `fingerprint`).  It covers the weights and the integer CDF tables (buffers of the entropy models): a decoder with other weights, or with tables rebuilt on another host's libm,
-would decode garbage without noticing, so it refuses instead.  It is a check against mistakes, not against tampering.
+The hashed state of a frame (seqfile.py, "State hashes") is the y_hat the next P frame is conditioned on, so verify_sequence checks a
+file on latents alone.  The hash proves that every symbol and every prior matched, not that g_s of an equal y_hat gives equal pixels.
 
 Frames enter through functional.yuv420_to_rgb_padded (integer planes of a data.YUVSequence -> the padded fp32 frame, one kernel) and
 leave through functional.rgb_window_to_yuv420 (the window of the padded x_hat -> integer planes, one kernel): no eager-torch pad, crop
@@ -47,75 +35,27 @@ or copy of a frame on the device.  The pixel-domain (stem_roi) models have a cod
 from __future__ import annotations
 
 import io
-import os
-import struct
 import sys
-import zlib
 
 import torch
 
-from . import bitstream
+from . import bitstream, seqfile
+from .seqfile import (HEADER_BYTES, STATE_HASH_BIT, VERSION, _HEADER, StateMismatch, _open, _planes_bytes, _Source,  # noqa: F401  (this module's names too)
+                      decode_steps, fingerprint, frame_types, gop_starts, hashed_record_ranges, print_report, record_ranges, split_trailer,
+                      trailer_bytes)
 
-MAGIC = b"STMV"
-VERSION = 1
-#: bit 7 of the version byte: behind the last record the file has a trailer of one u64 state hash per frame
-STATE_HASH_BIT = 0x80
 #: the P-frame model's index in the file header
 STEM_CLASSES = ("SpatioTemporalPriorModelWithoutSPMTPM", "SpatioTemporalPriorModelWithoutSPM", "SpatioTemporalPriorModelWithoutTPM",
                 "SpatioTemporalPriorModel", "SpatioTemporalPriorModel_Res")
 NO_STEM = 255
-_HEADER = struct.Struct(">4sBIIBIIBB" "BHHI" "BHHI")
-HEADER_BYTES = _HEADER.size
-_FIELDS = ("width", "height", "bit_depth", "frames", "gop", "all_intra", "quality", "imodel_id", "imodel_n", "imodel_m", "imodel_crc",
-           "stem_class", "stem_n", "stem_m", "stem_crc")
 
 
-class FileHeader:
-    """the file header as attributes (`_FIELDS`); `pack()` <-> `unpack(bytes)`.  `state_hash` (outside `_FIELDS`: it is a bit of the
-    version byte, not a field of the struct) says that the file ends in a trailer of state hashes."""
+class FileHeader(seqfile.FileHeader):
+    """seqfile.FileHeader under the magic "STMV": the I-frame model by its id in bitstream.model_ids, the STEM model by its class"""
+    MAGIC = b"STMV"
+    FIELDS = seqfile.COMMON_FIELDS + ("imodel_id", "imodel_n", "imodel_m", "imodel_crc", "stem_class", "stem_n", "stem_m", "stem_crc")
 
-    def __init__(self, state_hash=False, **kw):
-        missing = set(_FIELDS) - set(kw)
-        if missing or set(kw) - set(_FIELDS):
-            raise TypeError(f"FileHeader takes exactly {_FIELDS}, got {sorted(kw)}")
-        for k in _FIELDS:
-            setattr(self, k, int(kw[k]))
-        self.state_hash = bool(state_hash)
-
-    def astuple(self):
-        return tuple(getattr(self, k) for k in _FIELDS)
-
-    def __eq__(self, other):
-        return isinstance(other, FileHeader) and self.astuple() == other.astuple() and self.state_hash == other.state_hash
-
-    def __repr__(self):
-        return "FileHeader(" + ", ".join(f"{k}={getattr(self, k)}" for k in _FIELDS) + (", state_hash=True" if self.state_hash else "") + ")"
-
-    def pack(self):
-        self.check()
-        return _HEADER.pack(MAGIC, VERSION | (STATE_HASH_BIT if self.state_hash else 0), *self.astuple())
-
-    @classmethod
-    def unpack(cls, data):
-        if len(data) < HEADER_BYTES:
-            raise ValueError(f"truncated file: the header is {HEADER_BYTES} bytes, got {len(data)}")
-        magic, version, *rest = _HEADER.unpack(data[:HEADER_BYTES])
-        if magic != MAGIC:
-            raise ValueError(f"not a sequence file: magic {magic!r}, expected {MAGIC!r}")
-        if version & ~STATE_HASH_BIT != VERSION:
-            raise ValueError(f"sequence file version {version & ~STATE_HASH_BIT}, this module reads version {VERSION}")
-        hdr = cls(state_hash=bool(version & STATE_HASH_BIT), **dict(zip(_FIELDS, rest)))
-        hdr.check()
-        return hdr
-
-    def check(self):
-        _check_sides(self.height, self.width)
-        if self.bit_depth not in (8, 10):
-            raise ValueError(f"bit depth is 8 or 10, got {self.bit_depth}")
-        if self.gop < 1 or self.frames < 1:
-            raise ValueError(f"a sequence has at least one frame and gop is at least 1, got {self.frames} frames, gop {self.gop}")
-        if self.all_intra not in (0, 1):
-            raise ValueError(f"the all_intra flag is 0 or 1, got {self.all_intra}")
+    def check_models(self):
         if self.imodel_id >= len(bitstream.MODEL_NAMES):
             raise ValueError(f"unknown I-frame model id {self.imodel_id}")
         if self.stem_class != NO_STEM and self.stem_class >= len(STEM_CLASSES):
@@ -127,62 +67,16 @@ class FileHeader:
     def imodel_name(self):
         return bitstream.MODEL_NAMES[self.imodel_id]
 
-    def types(self):
-        return frame_types(self.frames, self.gop, bool(self.all_intra))
+
+MAGIC, _FIELDS = FileHeader.MAGIC, FileHeader.FIELDS
 
 
-def _check_sides(h, w):
-    if h < 2 or w < 2 or h % 2 or w % 2:
-        raise ValueError(f"4:2:0 frames have even sides >= 2, got {w} x {h}")
+def read_state_hashes(data):
+    """seqfile.read_state_hashes for this module's files: the state hashes in display order, or None for an un-hashed file"""
+    return seqfile.read_state_hashes(data, FileHeader)
 
 
-def frame_types(n_frames, gop, all_intra=False):
-    """"I" | "P" per frame in display order: evaluation.gop_schedule's rule (frame k, 1-based, with k % gop == 1 is an I frame, and so is the first)"""
-    from .evaluation import gop_schedule
-    types = [None] * n_frames
-    for step in gop_schedule(n_frames, gop, 1, all_intra):
-        for index, kind, _ in step:
-            types[index] = kind
-    return types
-
-
-def decode_steps(types, concurrent_gops, start=0, stop=None):
-    """The order in which the decoder walks the records that frames [start, stop) need (pure).  A GOP that covers part of the range is
-    decoded from its I frame up to its last frame inside the range; GOPs outside it are not touched.  Up to `concurrent_gops` of the
-    needed GOPs advance together, as in evaluation.gop_schedule, whose steps these are for the whole sequence.
-    -> list of steps, each a list of (frame index, "I" | "P", chain)"""
-    n = len(types)
-    stop = n if stop is None else stop
-    if not 0 <= start < stop <= n:
-        raise ValueError(f"frames=({start}, {stop}) is no range of a sequence of {n} frames")
-    if concurrent_gops < 1:
-        raise ValueError(f"concurrent_gops is at least 1, got {concurrent_gops}")
-    starts = [i for i, t in enumerate(types) if t == "I"]
-    gops = [(c, range(a, min(b, stop))) for c, (a, b) in enumerate(zip(starts, starts[1:] + [n])) if b > start and a < stop]
-    steps = []
-    for g0 in range(0, len(gops), concurrent_gops):
-        group = gops[g0:g0 + concurrent_gops]
-        for s in range(max(len(r) for _, r in group)):
-            steps.append([(r[s], types[r[s]], chain) for chain, r in group if s < len(r)])
-    return steps
-
-
-def fingerprint(model):
-    """zlib.crc32 over the model's state_dict in key order: every key's name, then its tensor's bytes.  The weight of a masked
-    convolution is read through its mask (a key "<name>.mask" next to "<name>.weight"): the dead taps never reach a coded symbol, and a
-    forward pass zeroes them in place (layers.MaskedConv2d, as in the reference), so a checkpoint saved before the model's first forward
-    and one saved after it are the same codec"""
-    crc = 0
-    sd = model.state_dict()
-    for key, value in sd.items():
-        crc = zlib.crc32(key.encode(), crc)
-        mask = sd.get(key[:-len("weight")] + "mask") if key.endswith(".weight") else None
-        if mask is not None:
-            value = torch.where(mask != 0, value, torch.zeros_like(value))
-        crc = zlib.crc32(value.detach().cpu().contiguous().reshape(-1).view(torch.uint8).numpy().tobytes() if value.numel() else b"", crc)
-    return crc & 0xFFFFFFFF
-
-
+# ---- models --------------------------------------------------------------------------------------------------------------------
 def _imodel_classes():
     from . import zoo
     return {"bmshj2018-factorized": zoo.FactorizedPrior, "bmshj2018-hyperprior": zoo.ScaleHyperprior, "mbt2018-mean": zoo.MeanScaleHyperprior,
@@ -238,26 +132,15 @@ def _header_for(imodel, stem, h, w, bit_depth, n, gop, all_intra, quality, state
 
 
 def check_header(hdr, imodel, stem):
-    """ValueError unless the models passed in are the ones the file was written with: class, widths, fingerprint"""
-    types = hdr.types()
-    name, sidx = _check_models(imodel, stem, "P" in types)
-    if name != hdr.imodel_name:
-        raise ValueError(f"the file was coded with {hdr.imodel_name}, the I-frame model passed in is {name}")
-    if (int(imodel.N), int(imodel.M)) != (hdr.imodel_n, hdr.imodel_m):
-        raise ValueError(f"the file's {name} has (N, M) = ({hdr.imodel_n}, {hdr.imodel_m}), the model passed in ({imodel.N}, {imodel.M})")
-    if fingerprint(imodel) != hdr.imodel_crc:
-        raise ValueError(f"the I-frame model's weights or tables are not the ones the file was coded with (fingerprint {fingerprint(imodel):08x}, "
-                         f"file {hdr.imodel_crc:08x})")
-    if "P" not in types:
-        return
-    if sidx != hdr.stem_class:
-        raise ValueError(f"the file was coded with {STEM_CLASSES[hdr.stem_class]}, the STEM model passed in is {type(stem).__name__}")
-    if (int(stem.entropy_bottleneck.channels), int(stem.in_channels)) != (hdr.stem_n, hdr.stem_m):
-        raise ValueError(f"the file's STEM model has (N, M) = ({hdr.stem_n}, {hdr.stem_m}), the model passed in "
-                         f"({stem.entropy_bottleneck.channels}, {stem.in_channels})")
-    if fingerprint(stem) != hdr.stem_crc:
-        raise ValueError(f"the STEM model's weights or tables are not the ones the file was coded with (fingerprint {fingerprint(stem):08x}, "
-                         f"file {hdr.stem_crc:08x})")
+    """ValueError unless the models passed in are the ones the file was written with: class, widths, fingerprint.  A kind is the zoo
+    name on the I side and the STEM class on the P side; the widths are (N, M)."""
+    has_p = "P" in hdr.types()
+    name, sidx = _check_models(imodel, stem, has_p)
+    seqfile.check_side("I-frame", imodel, (hdr.imodel_name, hdr.imodel_name, (hdr.imodel_n, hdr.imodel_m), hdr.imodel_crc),
+                       (name, name, (int(imodel.N), int(imodel.M))), name, "(N, M) =")
+    if has_p:
+        seqfile.check_side("STEM", stem, (hdr.stem_class, STEM_CLASSES[hdr.stem_class], (hdr.stem_n, hdr.stem_m), hdr.stem_crc),
+                           (sidx, type(stem).__name__, (int(stem.entropy_bottleneck.channels), int(stem.in_channels))), "STEM model", "(N, M) =")
 
 
 # ---- records -------------------------------------------------------------------------------------------------------------------
@@ -266,29 +149,6 @@ def record_bytes(model_name, quality, order, size, shape, strings):
     buf = io.BytesIO()
     bitstream.write_frame(buf, bitstream.get_header(model_name, "mse", quality, order), size, shape, strings)
     return buf.getvalue()
-
-
-def record_ranges(data, n_frames, offset=HEADER_BYTES):
-    """[(first byte, one past the last)] of the `n_frames` records in `data` (the whole file as bytes) from `offset` on, found by the length
-    prefixes alone: 2 header bytes, 5 u32 (h, w, shape, the number of strings), then per string a u32 length and that many bytes.
-    ValueError when the file ends inside a record or goes on behind the last one."""
-    ranges, pos, total = [], offset, len(data)
-    for k in range(n_frames):
-        first = pos
-        if pos + 22 > total:
-            raise ValueError(f"truncated file: record {k} starts at byte {pos} of {total} and has no room for its fixed part")
-        n_strings = struct.unpack_from(">I", data, pos + 18)[0]
-        pos += 22
-        for _ in range(n_strings):
-            if pos + 4 > total:
-                raise ValueError(f"truncated file: record {k} ends inside a string's length at byte {total}")
-            pos += 4 + struct.unpack_from(">I", data, pos)[0]
-        if pos > total:
-            raise ValueError(f"truncated file: record {k} needs bytes up to {pos}, the file has {total}")
-        ranges.append((first, pos))
-    if pos != total:
-        raise ValueError(f"{total - pos} bytes behind the last of {n_frames} records")
-    return ranges
 
 
 def _read_record(data, rng, hdr, index):
@@ -300,68 +160,6 @@ def _read_record(data, rng, hdr, index):
     return bitstream.stream_order(header), tuple(shape), strings
 
 
-# ---- the state-hash trailer (shared with video_pixel.py) ------------------------------------------------------------------------
-class StateMismatch(ValueError):
-    """a decoded frame's conditioning state is not the one the encoder hashed: .frame, .gop_start (the index of its GOP's I frame),
-    .want (the file's hash) and .got (the decoder's), both ints in [0, 2^64)"""
-
-    def __init__(self, frame, gop_start, want, got):
-        super().__init__(f"state mismatch at frame {frame} (its GOP starts at frame {gop_start}): the file says {want:016x}, this decoder "
-                         f"computed {got:016x}; nothing decoded from this state on can be trusted")
-        self.frame, self.gop_start, self.want, self.got = int(frame), int(gop_start), int(want), int(got)
-
-
-def trailer_bytes(hashes):
-    """the trailer of a hashed file: one big-endian u64 per frame in display order"""
-    return struct.pack(f">{len(hashes)}Q", *hashes)
-
-
-def split_trailer(data, hdr, header_bytes=HEADER_BYTES):
-    """(header + records, state hashes) of the whole file `data`: the trailer is the last 8 * frames bytes of a hashed file (hdr.state_hash)
-    -> (data, None) for an un-hashed one.  ValueError when a hashed file has no room for its trailer; a trailer of another length shows
-    as records that end early or late (`hashed_record_ranges`)."""
-    if not hdr.state_hash:
-        return data, None
-    n = 8 * hdr.frames
-    if len(data) < header_bytes + n:
-        raise ValueError(f"truncated file: a state-hash trailer of {n} bytes ({hdr.frames} frames) does not fit {len(data) - header_bytes} bytes "
-                         "behind the header")
-    return data[:len(data) - n], list(struct.unpack_from(f">{hdr.frames}Q", data, len(data) - n))
-
-
-def hashed_record_ranges(data, hdr, header_bytes=HEADER_BYTES):
-    """record_ranges over the file without its trailer -> (ranges, state hashes or None).  ValueError when the records do not end
-    exactly where the trailer (or, in an un-hashed file, the file's end) begins."""
-    body, hashes = split_trailer(data, hdr, header_bytes)
-    try:
-        return record_ranges(body, hdr.frames, header_bytes), hashes
-    except ValueError as e:
-        if hashes is None:
-            raise
-        raise ValueError(f"the state-hash trailer is not the {8 * hdr.frames} bytes behind the last record: {e}") from None
-
-
-def _read_state_hashes(data, header_cls, header_bytes):
-    data = bytes(data)
-    hdr = header_cls.unpack(data)
-    return hashed_record_ranges(data, hdr, header_bytes)[1]
-
-
-def read_state_hashes(data):
-    """the state hashes of a sequence file (its bytes): a list of `frames` ints in display order, or None for an un-hashed file;
-    ValueError for a file whose trailer does not sit right behind its last record"""
-    return _read_state_hashes(data, FileHeader, HEADER_BYTES)
-
-
-def gop_starts(types):
-    """per frame, the index of its GOP's I frame"""
-    out, last = [], 0
-    for i, t in enumerate(types):
-        last = i if t == "I" else last
-        out.append(last)
-    return out
-
-
 def _hash_states(states):
     """functional.state_hash of every tensor in `states` ([1,C,H,W] each) into one device buffer, fetched with one copy -> ints"""
     from . import functional as F
@@ -369,61 +167,6 @@ def _hash_states(states):
     for k, t in enumerate(states):
         F.state_hash(t, out=buf[k:k + 1])
     return F.state_hash_ints(buf)
-
-
-def _read_all(src):
-    if isinstance(src, (bytes, bytearray, memoryview)):
-        return bytes(src)
-    fd, close = _open(src, "rb")
-    try:
-        return fd.read()
-    finally:
-        if close:
-            fd.close()
-
-
-# ---- sources -------------------------------------------------------------------------------------------------------------------
-class _Source:
-    """the frames of encode_sequence: a data.YUVSequence (integer planes through the ingest kernel) or a sequence of [3,h,w] tensors"""
-
-    def __init__(self, frames, device):
-        from . import data
-        self.device = device
-        self.seq = frames if isinstance(frames, data.YUVSequence) else None
-        if self.seq is not None:
-            self.n, self.h, self.w, self.bit_depth = len(frames), frames.height, frames.width, frames.bit_depth
-        else:
-            self.frames = frames if hasattr(frames, "__getitem__") and hasattr(frames, "__len__") else list(frames)
-            if len(self.frames) == 0:
-                raise ValueError("encode_sequence: no frames")
-            first = self.frames[0]
-            if first.dim() != 3 or first.shape[0] != 3:
-                raise ValueError(f"encode_sequence: frames are [3,h,w] tensors, got {tuple(first.shape)}")
-            self.n, self.h, self.w = len(self.frames), int(first.shape[1]), int(first.shape[2])
-            self.bit_depth = int(getattr(first, "bit_depth", 8))                      # plain tensors: 8 bits, as evaluation._source_planes
-        _check_sides(self.h, self.w)
-
-    def padded(self, index):
-        """frame `index` as the zero-padded [1,3,Hp,Wp] batch the image model reads (bitstream.pad's centred geometry, multiples of 64)"""
-        if self.seq is None:
-            x = self.frames[index]
-            if tuple(x.shape) != (3, self.h, self.w):
-                raise ValueError(f"encode_sequence: frame {index} is {tuple(x.shape)}, the first one [3, {self.h}, {self.w}]")
-            return bitstream.pad(x.unsqueeze(0).to(self.device), 64)
-        from . import functional as F
-        y, u, v = (p.to(self.device, non_blocking=True) for p in self.seq.planes(index))
-        return F.yuv420_to_rgb_padded(y, u, v, self.bit_depth, "bilinear", self.seq.clamp, multiple=64)
-
-
-def _device_of(model):
-    return next(model.parameters()).device
-
-
-def _open(target, mode):
-    """(file object, close it afterwards?) of a path or a binary file object"""
-    if isinstance(target, (str, os.PathLike)):
-        return open(target, mode), True
-    return target, False
 
 
 # ---- the encoder ---------------------------------------------------------------------------------------------------------------
@@ -440,7 +183,7 @@ def encode_sequence(imodel, stem, frames, out, gop=12, concurrent_gops=8, all_in
     the hashes in display order"""
     from . import codec, evaluation
     codec._check_order(order)
-    src = _Source(frames, _device_of(imodel))
+    src = _Source(frames, seqfile._device_of(imodel))
     hdr = _header_for(imodel, stem, src.h, src.w, src.bit_depth, src.n, gop, all_intra, quality, state_hash)
     name = hdr.imodel_name
     coders = [imodel] + ([stem] if hdr.stem_class != NO_STEM else [])
@@ -493,13 +236,6 @@ def encode_sequence(imodel, stem, frames, out, gop=12, concurrent_gops=8, all_in
 
 
 # ---- the decoder ---------------------------------------------------------------------------------------------------------------
-def _planes_bytes(planes):
-    from . import data
-    buf = io.BytesIO()
-    data._write_planes(buf, planes, append=True)
-    return buf.getvalue()
-
-
 def _decode_step(imodel, stem, hdr, step, recs, y_cond, latents_only=False):
     """the records `recs` of one step of decode_steps -> (y_hat, x_hat) per position: I frames by the image model's decompress (x_hat
     with it, unless latents_only: then no synthesis transform runs), P frames by the STEM model's given their chain's condition (x_hat
@@ -530,50 +266,58 @@ def _decode_step(imodel, stem, hdr, step, recs, y_cond, latents_only=False):
     return y_hat, x_hat
 
 
+def _walk(imodel, stem, hdr, data, ranges, steps, hashed, abandoned=lambda index: False, **more):
+    """The decoder's walk over `steps` (decode_steps): per step, its records are read and decoded (`_decode_step`, **more) and, when
+    `hashed`, all its y_hat are hashed with one fetch (`_hash_states`) -> yields, per step, [(index, kind, (y_hat, x_hat), hash or
+    None)] BEFORE any of these states becomes a condition.  The caller judges them; frames for which abandoned(index) holds -- when
+    their step comes up, or after the caller has seen them -- are left out and their chain ends."""
+    y_cond = {}
+    for step in steps:
+        step = [s for s in step if not abandoned(s[0])]
+        if not step:
+            continue
+        recs = [_read_record(data, ranges[i], hdr, i) for i, _, _ in step]
+        y_hat, x_hat = _decode_step(imodel, stem, hdr, step, recs, y_cond, **more)
+        got = _hash_states(y_hat) if hashed else [None] * len(step)
+        yield [(index, kind, (y_hat[k], x_hat[k]), got[k]) for k, (index, kind, _) in enumerate(step)]
+        y_cond = {chain: y_hat[k] for k, (index, _, chain) in enumerate(step) if not abandoned(index)}
+
+
 @torch.no_grad()
 def decode_sequence(imodel, stem, src, write_to=None, concurrent_gops=8, frames=None, return_frames=True, verify=True):
-    """Decode the file `src` (a path, bytes, or a binary file object) with nothing else: its header is checked against the two models
-    (`check_header`), then every GOP is rebuilt from its records -- I frames by the image model's decompress, P frames by the STEM model's
-    given the previous frame's decoded latent, pixels by getX -- with up to `concurrent_gops` GOPs side by side.  write_to (a path or a
-    binary file object) receives the frames in display order as raw planar 4:2:0 at the file's bit depth, quantised from the padded
-    x_hat by one kernel per frame (functional.rgb_window_to_yuv420).  frames=(start, stop): only those frames are emitted, and only the
-    GOPs that cover them are decoded; the other records are stepped over.  On a hashed file (encode_sequence(state_hash=True)) with
-    verify=True every decoded frame's y_hat -- also of frames decoded for the chain's sake only -- is hashed and compared with the
-    file's entry before it becomes a condition or a picture: StateMismatch at the first difference.  verify=False, or an un-hashed
-    file: nothing is hashed.
+    """Decode the file `src` (a path, bytes, or a binary file object) with nothing else: the file is checked, then its header against
+    the two models (seqfile.open_for_decoding, `check_header`), then every GOP is rebuilt from its records -- I frames by the image
+    model's decompress, P frames by the STEM model's given the previous frame's decoded latent, pixels by getX -- with up to
+    `concurrent_gops` GOPs side by side.  write_to (a path or a binary file object) receives the frames in display order as raw planar
+    4:2:0 at the file's bit depth, quantised from the padded x_hat by one kernel per frame (functional.rgb_window_to_yuv420).
+    frames=(start, stop): only those frames are emitted, and only the GOPs that cover them are decoded; the other records are stepped
+    over.  On a hashed file (encode_sequence(state_hash=True)) with verify=True every decoded frame's y_hat -- also of frames decoded
+    for the chain's sake only -- is hashed and compared with the file's entry before it becomes a condition or a picture:
+    StateMismatch at the first difference.  verify=False, or an un-hashed file: nothing is hashed.
     -> the cropped x_hat tensors [1,3,h,w] of the emitted frames in display order (an empty list with return_frames=False)"""
     from . import evaluation
     from . import functional as F
-    data = _read_all(src)
-    hdr = FileHeader.unpack(data)
-    check_header(hdr, imodel, stem)
-    ranges, want = hashed_record_ranges(data, hdr)
-    types = hdr.types()
-    starts = gop_starts(types)
+    hdr, data, ranges, want, types, starts = seqfile.open_for_decoding(src, FileHeader, lambda hdr: check_header(hdr, imodel, stem))
     start, stop = (0, hdr.frames) if frames is None else (int(frames[0]), int(frames[1]))
     steps = decode_steps(types, concurrent_gops, start, stop)
     h, w = hdr.height, hdr.width
     sink, close = _open(write_to, "wb") if write_to is not None else (None, False)
     try:
         writer = evaluation._InOrder(sink) if sink is not None else None
-        kept, y_cond = [None] * (stop - start), {}
-        for step in steps:
-            recs = [_read_record(data, ranges[i], hdr, i) for i, _, _ in step]
-            y_hat, x_hat = _decode_step(imodel, stem, hdr, step, recs, y_cond)
-            if verify and want is not None:
-                for (index, _, _), got in zip(step, _hash_states(y_hat)):
-                    if got != want[index]:
-                        raise StateMismatch(index, starts[index], want[index], got)
-            for k, (index, kind, _) in enumerate(step):
+        kept = [None] * (stop - start)
+        for decoded in _walk(imodel, stem, hdr, data, ranges, steps, verify and want is not None):
+            for index, _, _, got in decoded:
+                if got is not None and got != want[index]:
+                    raise StateMismatch(index, starts[index], want[index], got)
+            for index, kind, (y_hat, x_hat), _ in decoded:
                 if kind == "P":
-                    x_hat[k] = imodel.getX(y_hat[k])
+                    x_hat = imodel.getX(y_hat)
                 if index < start:
                     continue                                                          # decoded for the chain's sake only
                 if writer is not None:
-                    writer.put(index - start, _planes_bytes(F.rgb_window_to_yuv420(x_hat[k], (h, w), hdr.bit_depth)))
+                    writer.put(index - start, _planes_bytes(F.rgb_window_to_yuv420(x_hat, (h, w), hdr.bit_depth)))
                 if return_frames:
-                    kept[index - start] = bitstream.crop(x_hat[k], (h, w))
-            y_cond = {chain: y_hat[k] for k, (_, _, chain) in enumerate(step)}
+                    kept[index - start] = bitstream.crop(x_hat, (h, w))
     finally:
         if close:
             sink.close()
@@ -586,145 +330,65 @@ def verify_sequence(imodel, stem, src, concurrent_gops=8):
     independent chain and is checked on its own: at its first frame whose decoded y_hat does not hash to the file's entry the GOP is
     abandoned (what follows would be decoded under a wrong condition) and the other GOPs go on.
     -> {"frames": n, "checked": frames hashed, "mismatches": [{"frame", "gop_start", "want", "got"}], "unchecked": [frames skipped behind
-    a mismatch]}, indices ascending.  ValueError for an un-hashed file: there is nothing to check it against."""
-    data = _read_all(src)
-    hdr = FileHeader.unpack(data)
-    check_header(hdr, imodel, stem)
-    ranges, want = hashed_record_ranges(data, hdr)
-    if want is None:
-        raise ValueError("the file carries no state hashes (it was written without state_hash=True): nothing to verify it against")
-    types = hdr.types()
-    starts = gop_starts(types)
-    checked, mismatches, dead, y_cond = 0, [], set(), {}
-    for step in decode_steps(types, concurrent_gops):
-        step = [s for s in step if starts[s[0]] not in dead]
-        if not step:
-            continue
-        recs = [_read_record(data, ranges[i], hdr, i) for i, _, _ in step]
-        y_hat, _ = _decode_step(imodel, stem, hdr, step, recs, y_cond, latents_only=True)
-        y_next = {}
-        for k, ((index, _, chain), got) in enumerate(zip(step, _hash_states(y_hat))):
-            checked += 1
-            if got != want[index]:
-                mismatches.append({"frame": index, "gop_start": starts[index], "want": want[index], "got": got})
-                dead.add(starts[index])
-            else:
-                y_next[chain] = y_hat[k]
-        y_cond = y_next
-    mismatches.sort(key=lambda m: m["frame"])
-    bad = {m["gop_start"]: m["frame"] for m in mismatches}
-    unchecked = [i for i in range(hdr.frames) if starts[i] in bad and i > bad[starts[i]]]
-    return {"frames": hdr.frames, "checked": checked, "mismatches": mismatches, "unchecked": unchecked}
+    a mismatch]}, indices ascending (seqfile.VerifyReport).  ValueError for an un-hashed file: there is nothing to check it against."""
+    hdr, data, ranges, want, types, starts = seqfile.open_for_decoding(src, FileHeader, lambda hdr: check_header(hdr, imodel, stem), need_hashes=True)
+    report = seqfile.VerifyReport(hdr, starts, want)
+    for decoded in _walk(imodel, stem, hdr, data, ranges, decode_steps(types, concurrent_gops), True, report.abandoned, latents_only=True):
+        for index, _, _, got in decoded:
+            report.check(index, got)
+    return report.result()
 
 
 # ---- the command line ----------------------------------------------------------------------------------------------------------
-def _state_dict(path):
-    sd = torch.load(path, map_location="cpu")
-    if isinstance(sd, dict) and "state_dict" in sd and not any(torch.is_tensor(v) for v in sd.values()):
-        sd = sd["state_dict"]
-    if not isinstance(sd, dict) or not sd or not all(torch.is_tensor(v) for v in sd.values()):
-        raise ValueError(f"{path} holds no state_dict")
-    return sd
-
-
 def load_imodel(name, path, device):
     """an I-frame model of the zoo sized by, and loaded from, the checkpoint at `path` (a state_dict, tables included)"""
     classes = _imodel_classes()
     if name not in classes:
         raise ValueError(f'unknown I-frame model "{name}": one of {tuple(classes)}')
     try:
-        return classes[name].from_state_dict(_state_dict(path)).to(device).eval()
+        return classes[name].from_state_dict(seqfile._state_dict(path)).to(device).eval()
     except (KeyError, RuntimeError) as e:
         raise ValueError(f"{path} is no checkpoint of {name}: {e}") from e
 
 
 def load_stem(cls_name, path, device):
     """a STEM model of class `cls_name` sized by, and loaded from, the checkpoint at `path`"""
-    from . import models
     if cls_name not in STEM_CLASSES:
         raise ValueError(f'unknown STEM class "{cls_name}": one of {STEM_CLASSES}')
-    sd = _state_dict(path)
-    try:
-        net = getattr(models, cls_name)(sd["entropy_bottleneck.quantiles"].size(0), sd["HD.4.weight"].size(0) // 2)
-        net.load_state_dict(sd)
-    except (KeyError, RuntimeError) as e:
-        raise ValueError(f"{path} is no checkpoint of {cls_name}: {e}") from e
-    return net.to(device).eval()
-
-
-def print_report(report):
-    """verify_sequence's report as one JSON line on stdout, hashes in hex -> the exit status: 0 when clean, 3 on any mismatch"""
-    import json
-    out = dict(report, mismatches=[dict(m, want=f"{m['want']:016x}", got=f"{m['got']:016x}") for m in report["mismatches"]])
-    print(json.dumps(out))
-    return 3 if report["mismatches"] else 0
+    return seqfile.load_sized(cls_name, path, device, "entropy_bottleneck.quantiles", "HD.4.weight")
 
 
 def _parser():
     import argparse
     p = argparse.ArgumentParser(prog="python -m spatiotemporalentropymodel_amd.video", description="stand-alone sequence codec")
-    sub = p.add_subparsers(dest="command", required=True)
-    for name in ("encode", "decode", "verify"):
-        s = sub.add_parser(name)
-        s.add_argument("--imodel", required=True, help="zoo name of the I-frame model")
-        s.add_argument("--imodel-checkpoint", required=True)
-        s.add_argument("--stem", default=None, help="STEM class name (not needed for an all-intra file)")
-        s.add_argument("--stem-checkpoint", default=None)
-        s.add_argument("--input", required=True)
-        if name != "verify":
-            s.add_argument("--output", required=True)
+    subs = seqfile.add_common_options(p.add_subparsers(dest="command", required=True), "imodel", "zoo name of the I-frame model",
+                                      "stem", "STEM class name (not needed for an all-intra file)")
+    seqfile.add_coding_options(subs["encode"], subs["decode"])
+    for s in subs.values():
         s.add_argument("--concurrent-gops", type=int, default=8)
-        s.add_argument("--device", default="cuda:0")
-    e, d = sub.choices["encode"], sub.choices["decode"]
-    e.add_argument("--width", type=int, required=True)
-    e.add_argument("--height", type=int, required=True)
-    e.add_argument("--bit-depth", type=int, default=8)
-    e.add_argument("--frames", type=int, default=None, help="code the first so many frames")
-    e.add_argument("--gop", type=int, default=12)
-    e.add_argument("--all-intra", action="store_true")
-    e.add_argument("--order", default="raster", choices=("raster", "wavefront"))
-    e.add_argument("--quality", type=int, default=4)
-    e.add_argument("--state-hash", action="store_true", help="write a hashed file: every frame's conditioning state, checked while decoding")
-    d.add_argument("--frames", default=None, help="START:STOP, decode only these frames")
-    d.add_argument("--no-verify", action="store_true", help="do not check a hashed file's state hashes")
+    subs["encode"].add_argument("--order", default="raster", choices=("raster", "wavefront"))
     return p
+
+
+def _run(args):
+    if (args.stem is None) != (args.stem_checkpoint is None):
+        raise ValueError("--stem and --stem-checkpoint come together")
+    imodel = load_imodel(args.imodel, args.imodel_checkpoint, args.device)
+    stem = load_stem(args.stem, args.stem_checkpoint, args.device) if args.stem else None
+    gops = args.concurrent_gops
+    return seqfile.run_command(
+        args,
+        encode=lambda seq: encode_sequence(imodel, stem, seq, args.output, gop=args.gop, concurrent_gops=gops, all_intra=args.all_intra,
+                                           order=args.order, quality=args.quality, state_hash=args.state_hash),
+        decode=lambda rng: decode_sequence(imodel, stem, args.input, write_to=args.output, concurrent_gops=gops, frames=rng, return_frames=False,
+                                           verify=not args.no_verify),
+        verify=lambda: verify_sequence(imodel, stem, args.input, concurrent_gops=gops))
 
 
 def main(argv=None):
     """-> the exit status: 0; 2 after a refusal (ValueError), whose message goes to stderr; 3 when a state hash did not match (`verify`
     prints its report as JSON either way, `decode` stops at the first one)"""
-    args = _parser().parse_args(argv)
-    try:
-        if (args.stem is None) != (args.stem_checkpoint is None):
-            raise ValueError("--stem and --stem-checkpoint come together")
-        imodel = load_imodel(args.imodel, args.imodel_checkpoint, args.device)
-        stem = load_stem(args.stem, args.stem_checkpoint, args.device) if args.stem else None
-        if args.command == "encode":
-            from . import data
-            seq = data.YUVSequence(args.input, args.width, args.height, args.bit_depth, frames=args.frames, device=args.device)
-            res = encode_sequence(imodel, stem, seq, args.output, gop=args.gop, concurrent_gops=args.concurrent_gops, all_intra=args.all_intra,
-                                  order=args.order, quality=args.quality, state_hash=args.state_hash)
-            print(f"{len(res['frames'])} frames, {res['bytes']} bytes, {res['bpp_ave']:.6f} bpp")
-        elif args.command == "verify":
-            return print_report(verify_sequence(imodel, stem, args.input, concurrent_gops=args.concurrent_gops))
-        else:
-            rng = None
-            if args.frames is not None:
-                try:
-                    rng = tuple(int(v) for v in args.frames.split(":"))
-                    assert len(rng) == 2
-                except (ValueError, AssertionError):
-                    raise ValueError(f"--frames is START:STOP, got {args.frames!r}") from None
-            decode_sequence(imodel, stem, args.input, write_to=args.output, concurrent_gops=args.concurrent_gops, frames=rng, return_frames=False,
-                            verify=not args.no_verify)
-            print(f"decoded {args.input} into {args.output}")
-    except StateMismatch as e:
-        print(f"mismatch: {e}", file=sys.stderr)
-        return 3
-    except ValueError as e:
-        print(f"refused: {e}", file=sys.stderr)
-        return 2
-    return 0
+    return seqfile.exit_status(_run, _parser().parse_args(argv))
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 """The stand-alone sequence codec of the PIXEL-domain model pairs -- stem_roi_i + stem_roi driven by a quality map (the reference's
 variable-rate / region-of-interest codec), and an image model of the zoo + one of the fixed-rate pixel models.  video.py is the same
-thing for the latent-domain STEM pairs; this module reuses its container helpers and keeps a file format of its own.
+thing for the latent-domain STEM pairs; both are formats of seqfile.py's container.
 
     encode_sequence(model_i, model_p, frames, out, qmaps=... | rois=..., ...)    frames (+ maps or rectangles) -> file; no decompress
     decode_sequence(model_i, model_p, src, write_to=None, ...)                   file -> planar 4:2:0 frames (and the cropped x_hat)
@@ -19,22 +19,20 @@ frame with the same maps.
 `concurrent_gops` is deliberately not offered: these models code a frame in one shot and their transforms must run at batch 1 (README,
 "Why the transforms stay at batch 1"), so there is nothing to batch across GOPs.
 
-File layout (all integers big-endian; the struct shape of video.py's header under another magic, because video.FileHeader refuses
-every file that is not its own):
+File layout (seqfile.py's container -- frame types, record ranges, the state-hash trailer, the fingerprint and the order of checks are
+stated there -- with this header and this record rule; all integers big-endian):
 
     header   4s magic "STPX" | u8 version | u32 w | u32 h | u8 bit depth | u32 frames | u32 gop | u8 all_intra | u8 quality
              | u8 I kind (0..5: bitstream.model_ids, a, b = N, M; 64: stem_roi_i, a, b = bottleneck channels, in_channels) | u16 a | u16 b
              | u32 fingerprint
              | u8 P kind (index in PIXEL_P_CLASSES; 255: none, an all-intra file) | u16 a | u16 b | u32 fingerprint
-    records  one per frame in display order, in bitstream.write_frame's layout (video.record_ranges walks them)
+    records  one per frame in display order, in bitstream.write_frame's layout
 
 A record's first byte is the I kind for an I record and 128 + the P kind for a P record; its second byte is (quality - 1) & 0x0F.  For
-an I-frame model of the zoo an I record therefore is byte for byte the record the reference's tool writes for that image.  The
-fingerprint is video.fingerprint.  The quality map is not in the file: it is encoder-side information, the decoder derives its
-modulation from z_hat (PDecoder).
+an I-frame model of the zoo an I record therefore is byte for byte the record the reference's tool writes for that image.  The quality
+map is not in the file: it is encoder-side information, the decoder derives its modulation from z_hat (PDecoder).
 
-State hashes (opt-in, encode_sequence(state_hash=True); the format change is video.py's: bit 7 of the version byte, a trailer of `frames`
-u64 behind the last record).  The hashed state of a frame is its padded x_hat AFTER functional.rgb_window_recondition -- the whole padded
+The hashed state of a frame (seqfile.py, "State hashes") is its padded x_hat AFTER functional.rgb_window_recondition -- the whole padded
 tensor with its border zeroed, exactly the next P frame's condition.  Here the state is a picture, so checking it needs the synthesis:
 verify_sequence runs the whole decoder and only leaves out the planes and the file.
 """
@@ -46,12 +44,11 @@ import sys
 
 import torch
 
-from . import bitstream
-from .video import (STATE_HASH_BIT, StateMismatch, _open, _planes_bytes, _read_all, _read_state_hashes, _Source, decode_steps, fingerprint,
-                    frame_types, gop_starts, hashed_record_ranges, print_report, record_ranges, trailer_bytes)
+from . import bitstream, seqfile
+from .seqfile import (HEADER_BYTES, STATE_HASH_BIT, VERSION, _HEADER, StateMismatch, _open, _planes_bytes, _Source,  # noqa: F401  (this module's names too)
+                      decode_steps, fingerprint, frame_types, gop_starts, hashed_record_ranges, print_report, record_ranges, split_trailer,
+                      trailer_bytes)
 
-MAGIC = b"STPX"
-VERSION = 1
 #: the P-frame model's index in the file header
 PIXEL_P_CLASSES = ("stem_baseline", "stem_baselinev2", "stem_roi", "stem_roi_wo_gsc")
 NO_P = 255
@@ -59,64 +56,16 @@ NO_P = 255
 KIND_ROI_I = 64
 #: added to the P kind in a P record's first byte
 P_RECORD = 128
-_HEADER = struct.Struct(">4sBIIBIIBB" "BHHI" "BHHI")
-HEADER_BYTES = _HEADER.size
-_FIELDS = ("width", "height", "bit_depth", "frames", "gop", "all_intra", "quality", "i_kind", "i_a", "i_b", "i_crc", "p_kind", "p_a", "p_b",
-           "p_crc")
 
 
-def _check_sides(h, w):
-    if h < 2 or w < 2 or h % 2 or w % 2:
-        raise ValueError(f"4:2:0 frames have even sides >= 2, got {w} x {h}")
+class FileHeader(seqfile.FileHeader):
+    """seqfile.FileHeader under the magic "STPX": either model by its kind and two widths (a, b)"""
+    MAGIC = b"STPX"
+    FIELDS = seqfile.COMMON_FIELDS + ("i_kind", "i_a", "i_b", "i_crc", "p_kind", "p_a", "p_b", "p_crc")
+    NOUN = "pixel-domain sequence file"
+    FOREIGN = {b"STMV": "this is a file of the latent-domain codec (magic b'STMV'): read it with spatiotemporalentropymodel_amd.video"}
 
-
-class FileHeader:
-    """the file header as attributes (`_FIELDS`); `pack()` <-> `unpack(bytes)`.  `state_hash` (outside `_FIELDS`: a bit of the version
-    byte, video.STATE_HASH_BIT) says that the file ends in a trailer of state hashes."""
-
-    def __init__(self, state_hash=False, **kw):
-        if set(kw) != set(_FIELDS):
-            raise TypeError(f"FileHeader takes exactly {_FIELDS}, got {sorted(kw)}")
-        for k in _FIELDS:
-            setattr(self, k, int(kw[k]))
-        self.state_hash = bool(state_hash)
-
-    def astuple(self):
-        return tuple(getattr(self, k) for k in _FIELDS)
-
-    def __eq__(self, other):
-        return isinstance(other, FileHeader) and self.astuple() == other.astuple() and self.state_hash == other.state_hash
-
-    def __repr__(self):
-        return "FileHeader(" + ", ".join(f"{k}={getattr(self, k)}" for k in _FIELDS) + (", state_hash=True" if self.state_hash else "") + ")"
-
-    def pack(self):
-        self.check()
-        return _HEADER.pack(MAGIC, VERSION | (STATE_HASH_BIT if self.state_hash else 0), *self.astuple())
-
-    @classmethod
-    def unpack(cls, data):
-        if len(data) < HEADER_BYTES:
-            raise ValueError(f"truncated file: the header is {HEADER_BYTES} bytes, got {len(data)}")
-        magic, version, *rest = _HEADER.unpack(data[:HEADER_BYTES])
-        if magic == b"STMV":
-            raise ValueError("this is a file of the latent-domain codec (magic b'STMV'): read it with spatiotemporalentropymodel_amd.video")
-        if magic != MAGIC:
-            raise ValueError(f"not a pixel-domain sequence file: magic {magic!r}, expected {MAGIC!r}")
-        if version & ~STATE_HASH_BIT != VERSION:
-            raise ValueError(f"pixel-domain sequence file version {version & ~STATE_HASH_BIT}, this module reads version {VERSION}")
-        hdr = cls(state_hash=bool(version & STATE_HASH_BIT), **dict(zip(_FIELDS, rest)))
-        hdr.check()
-        return hdr
-
-    def check(self):
-        _check_sides(self.height, self.width)
-        if self.bit_depth not in (8, 10):
-            raise ValueError(f"bit depth is 8 or 10, got {self.bit_depth}")
-        if self.gop < 1 or self.frames < 1:
-            raise ValueError(f"a sequence has at least one frame and gop is at least 1, got {self.frames} frames, gop {self.gop}")
-        if self.all_intra not in (0, 1):
-            raise ValueError(f"the all_intra flag is 0 or 1, got {self.all_intra}")
+    def check_models(self):
         if self.i_kind != KIND_ROI_I and self.i_kind >= len(bitstream.MODEL_NAMES):
             raise ValueError(f"unknown I kind {self.i_kind}")
         if self.p_kind != NO_P and self.p_kind >= len(PIXEL_P_CLASSES):
@@ -128,12 +77,17 @@ class FileHeader:
     def i_name(self):
         return "stem_roi_i" if self.i_kind == KIND_ROI_I else bitstream.MODEL_NAMES[self.i_kind]
 
-    def types(self):
-        return frame_types(self.frames, self.gop, bool(self.all_intra))
-
     def record_byte(self, kind):
         """the first byte of an "I" | "P" record of this file"""
         return self.i_kind if kind == "I" else P_RECORD + self.p_kind
+
+
+MAGIC, _FIELDS = FileHeader.MAGIC, FileHeader.FIELDS
+
+
+def read_state_hashes(data):
+    """seqfile.read_state_hashes for this module's files: the state hashes in display order, or None for an un-hashed file"""
+    return seqfile.read_state_hashes(data, FileHeader)
 
 
 # ---- models --------------------------------------------------------------------------------------------------------------------
@@ -177,30 +131,18 @@ def _header_for(model_i, model_p, h, w, bit_depth, n, gop, all_intra, quality, s
     (ik, ia, ib), p = _check_models(model_i, model_p, "P" in types)
     pk, pa, pb = p if p is not None else (NO_P, 0, 0)
     return FileHeader(state_hash=state_hash, width=w, height=h, bit_depth=bit_depth, frames=n, gop=gop, all_intra=int(bool(all_intra)),
-                      quality=quality, i_kind=ik, i_a=ia, i_b=ib, i_crc=fingerprint(model_i), p_kind=pk, p_a=pa, p_b=pb, p_crc=fingerprint(model_p) if p is not None else 0)
+                      quality=quality, i_kind=ik, i_a=ia, i_b=ib, i_crc=fingerprint(model_i), p_kind=pk, p_a=pa, p_b=pb,
+                      p_crc=fingerprint(model_p) if p is not None else 0)
 
 
 def check_header(hdr, model_i, model_p):
-    """ValueError unless the models passed in are the ones the file was written with: class, widths, fingerprint"""
-    has_p = "P" in hdr.types()
-    (ik, ia, ib), p = _check_models(model_i, model_p, has_p)
-    if ik != hdr.i_kind:
-        raise ValueError(f"the file was coded with {hdr.i_name}, the I-frame model passed in is {type(model_i).__name__}")
-    if (ia, ib) != (hdr.i_a, hdr.i_b):
-        raise ValueError(f"the file's {hdr.i_name} has widths ({hdr.i_a}, {hdr.i_b}), the model passed in ({ia}, {ib})")
-    if fingerprint(model_i) != hdr.i_crc:
-        raise ValueError(f"the I-frame model's weights or tables are not the ones the file was coded with (fingerprint {fingerprint(model_i):08x}, "
-                         f"file {hdr.i_crc:08x})")
-    if not has_p:
-        return
-    pk, pa, pb = p
-    if pk != hdr.p_kind:
-        raise ValueError(f"the file was coded with {PIXEL_P_CLASSES[hdr.p_kind]}, the P-frame model passed in is {type(model_p).__name__}")
-    if (pa, pb) != (hdr.p_a, hdr.p_b):
-        raise ValueError(f"the file's {PIXEL_P_CLASSES[hdr.p_kind]} has widths ({hdr.p_a}, {hdr.p_b}), the model passed in ({pa}, {pb})")
-    if fingerprint(model_p) != hdr.p_crc:
-        raise ValueError(f"the P-frame model's weights or tables are not the ones the file was coded with (fingerprint {fingerprint(model_p):08x}, "
-                         f"file {hdr.p_crc:08x})")
+    """ValueError unless the models passed in are the ones the file was written with: class, widths, fingerprint.  A kind is the kind
+    byte of the header; the widths are its (a, b)."""
+    (ik, ia, ib), p = _check_models(model_i, model_p, "P" in hdr.types())
+    seqfile.check_side("I-frame", model_i, (hdr.i_kind, hdr.i_name, (hdr.i_a, hdr.i_b), hdr.i_crc), (ik, type(model_i).__name__, (ia, ib)), hdr.i_name)
+    if p is not None:
+        p_name = PIXEL_P_CLASSES[hdr.p_kind]
+        seqfile.check_side("P-frame", model_p, (hdr.p_kind, p_name, (hdr.p_a, hdr.p_b), hdr.p_crc), (p[0], type(model_p).__name__, p[1:]), p_name)
 
 
 # ---- records -------------------------------------------------------------------------------------------------------------------
@@ -229,18 +171,12 @@ def read_record(data, rng, hdr, index, kind):
     return (s0, s1), strings
 
 
-def read_state_hashes(data):
-    """video.read_state_hashes for this module's files: the state hashes in display order, or None for an un-hashed file"""
-    return _read_state_hashes(data, FileHeader, HEADER_BYTES)
-
-
 # ---- maps ----------------------------------------------------------------------------------------------------------------------
 def _map_source(qmaps, rois, level, h, w, device):
-    """-> a function index -> the padded quality map [1,1,Hp,Wp] on the device, or None; to be called once per frame, in order"""
+    """-> a function index -> the padded quality map [1,1,Hp,Wp] on the device, or None; to be called once per frame, in order.
+    At most one of qmaps and rois is given (encode_sequence has refused both)."""
     from . import evaluation
     from . import functional as F
-    if qmaps is not None and rois is not None:
-        raise ValueError("qmaps and rois are mutually exclusive: give the maps or the rectangles")
     if rois is not None:
         boxes_of = rois if callable(rois) else None
         if boxes_of is None:
@@ -263,10 +199,6 @@ def _map_source(qmaps, rois, level, h, w, device):
     return padded
 
 
-def _device_of(model):
-    return next(model.parameters()).device
-
-
 # ---- the encoder ---------------------------------------------------------------------------------------------------------------
 @torch.no_grad()
 def encode_sequence(model_i, model_p, frames, out, *, qmaps=None, rois=None, level=0.0, gop=12, all_intra=False, quality=4, state_hash=False):
@@ -283,14 +215,14 @@ def encode_sequence(model_i, model_p, frames, out, *, qmaps=None, rois=None, lev
     -> {"frames": [{"type", "bytes", "bpp"}] in display order, "bytes": the file's size, "bpp_ave"} and, with state_hash, "state_hash":
     the hashes in display order"""
     from . import functional as F
-    device = _device_of(model_i)
+    device = seqfile._device_of(model_i)
     src = _Source(frames, device)
     hdr = _header_for(model_i, model_p, src.h, src.w, src.bit_depth, src.n, gop, all_intra, quality, state_hash)
     types = hdr.types()
     coders = [model_i] + ([model_p] if "P" in types else [])
-    given = qmaps is not None or rois is not None
-    if given and qmaps is not None and rois is not None:
+    if qmaps is not None and rois is not None:
         raise ValueError("qmaps and rois are mutually exclusive: give the maps or the rectangles")
+    given = qmaps is not None or rois is not None
     if given and not any(_takes_qmap(m) for m in coders):
         raise ValueError(f"a quality map is given and none of the coding models takes one ({', '.join(type(m).__name__ for m in coders)})")
     if not given:
@@ -341,48 +273,55 @@ def encode_sequence(model_i, model_p, frames, out, *, qmaps=None, rois=None, lev
 
 
 # ---- the decoder ---------------------------------------------------------------------------------------------------------------
+def _walk(model_i, model_p, hdr, data, ranges, steps, hashed, planes_from=None, abandoned=lambda index: False):
+    """The decoder's walk over `steps` (decode_steps at one GOP at a time): per frame, its record is read and decoded -- I frames by
+    model_i's decompress, P frames by model_p's given the previous frame's state --, one kernel (functional.rgb_window_recondition)
+    makes the padded x_hat the next condition in place and, for the frames from `planes_from` on (None: for none), writes its integer
+    4:2:0 planes in the same pass, and, when `hashed`, the state is hashed and fetched -> yields (index, kind, (x_hat, planes or None),
+    hash or None) BEFORE the state becomes a condition.  Frames for which abandoned(index) holds when their turn comes are left out."""
+    from . import functional as F
+    x_cond = None
+    for (index, kind, _), in steps:
+        if abandoned(index):
+            continue
+        shape, strings = read_record(data, ranges[index], hdr, index, kind)
+        if kind == "I":
+            x_hat = model_i.decompress(strings, shape)["x_hat"]
+        else:
+            x_hat = model_p.decompress(strings, shape, x_cond)["x_hat"]
+        emit = planes_from is not None and index >= planes_from
+        planes = F.rgb_window_recondition(x_hat, (hdr.height, hdr.width), hdr.bit_depth if emit else None)
+        yield index, kind, (x_hat, planes), F.state_hash_ints(F.state_hash(x_hat))[0] if hashed else None
+        x_cond = x_hat
+
+
 @torch.no_grad()
 def decode_sequence(model_i, model_p, src, write_to=None, frames=None, return_frames=True, verify=True):
     """Decode the file `src` (a path, bytes, or a binary file object) with nothing but the file and the two models: the quality map is
-    encoder-side information and is not needed -- the decoder derives its modulation from z_hat (PDecoder).  The header is checked
-    against the models (`check_header`: kind, widths, fingerprint), then every GOP is rebuilt from its records: I frames by model_i's
-    decompress, P frames by model_p's given the previous frame's reconstruction.  One kernel per frame
+    encoder-side information and is not needed -- the decoder derives its modulation from z_hat (PDecoder).  The file is checked, then
+    its header against the models (seqfile.open_for_decoding, `check_header`: kind, widths, fingerprint), then every GOP is rebuilt from
+    its records: I frames by model_i's decompress, P frames by model_p's given the previous frame's reconstruction.  One kernel per frame
     (functional.rgb_window_recondition) makes the decoded padded frame the next condition in place and, when write_to (a path or a
     binary file object) is given, writes the frame's planar 4:2:0 samples at the file's bit depth in the same pass.
     frames=(start, stop): only those frames are emitted, and only the GOPs that cover them are decoded.  On a hashed file
     (encode_sequence(state_hash=True)) with verify=True every decoded frame's reconditioned x_hat -- also of frames decoded for the
     chain's sake only -- is hashed and compared with the file's entry before it becomes a condition or leaves as a picture:
-    video.StateMismatch at the first difference.  verify=False, or an un-hashed file: nothing is hashed.
+    StateMismatch at the first difference.  verify=False, or an un-hashed file: nothing is hashed.
     -> the cropped x_hat tensors [1,3,h,w] of the emitted frames in display order, as copies (an empty list with return_frames=False)"""
-    from . import functional as F
-    data = _read_all(src)
-    hdr = FileHeader.unpack(data)
-    ranges, want = hashed_record_ranges(data, hdr, HEADER_BYTES)                     # the file's own consistency first: it costs nothing
-    check_header(hdr, model_i, model_p)
-    types = hdr.types()
-    starts = gop_starts(types)
+    hdr, data, ranges, want, types, starts = seqfile.open_for_decoding(src, FileHeader, lambda hdr: check_header(hdr, model_i, model_p))
     start, stop = (0, hdr.frames) if frames is None else (int(frames[0]), int(frames[1]))
     steps = decode_steps(types, 1, start, stop)
     h, w = hdr.height, hdr.width
     sink, close = _open(write_to, "wb") if write_to is not None else (None, False)
     try:
-        kept, x_cond = [], None
-        for (index, kind, _), in steps:
-            shape, strings = read_record(data, ranges[index], hdr, index, kind)
-            if kind == "I":
-                x_hat = model_i.decompress(strings, shape)["x_hat"]
-            else:
-                x_hat = model_p.decompress(strings, shape, x_cond)["x_hat"]
-            emit = index >= start                                                     # otherwise decoded for the chain's sake only
-            planes = F.rgb_window_recondition(x_hat, (h, w), hdr.bit_depth if emit and sink is not None else None)
-            if verify and want is not None:
-                got = F.state_hash_ints(F.state_hash(x_hat))[0]
-                if got != want[index]:
-                    raise StateMismatch(index, starts[index], want[index], got)
-            x_cond = x_hat
+        kept = []
+        for index, _, (x_hat, planes), got in _walk(model_i, model_p, hdr, data, ranges, steps, verify and want is not None,
+                                                    planes_from=start if sink is not None else None):
+            if got is not None and got != want[index]:
+                raise StateMismatch(index, starts[index], want[index], got)
             if planes is not None:
                 sink.write(_planes_bytes(planes))
-            if emit and return_frames:
+            if index >= start and return_frames:                                      # otherwise decoded for the chain's sake only
                 top, left = (x_hat.size(2) - h) // 2, (x_hat.size(3) - w) // 2
                 kept.append(x_hat[:, :, top:top + h, left:left + w].clone())
     finally:
@@ -396,53 +335,23 @@ def verify_sequence(model_i, model_p, src):
     """Check a hashed file against this decoder: every GOP is decoded on its own (the state is a picture, so the synthesis runs; no
     planes, no file) and every frame's reconditioned x_hat is hashed and compared with the file's entry.  A GOP is abandoned at its
     first mismatch -- what follows would be decoded under a wrong condition -- and the next GOP goes on.
-    -> video.verify_sequence's report: {"frames", "checked", "mismatches": [{"frame", "gop_start", "want", "got"}], "unchecked"}.
-    ValueError for an un-hashed file."""
-    from . import functional as F
-    data = _read_all(src)
-    hdr = FileHeader.unpack(data)
-    ranges, want = hashed_record_ranges(data, hdr, HEADER_BYTES)
-    check_header(hdr, model_i, model_p)
-    if want is None:
-        raise ValueError("the file carries no state hashes (it was written without state_hash=True): nothing to verify it against")
-    types = hdr.types()
-    starts = gop_starts(types)
-    h, w = hdr.height, hdr.width
-    checked, mismatches, unchecked, dead, x_cond = 0, [], [], None, None
-    for index, kind in enumerate(types):
-        if dead == starts[index]:
-            unchecked.append(index)
-            continue
-        shape, strings = read_record(data, ranges[index], hdr, index, kind)
-        x_hat = model_i.decompress(strings, shape)["x_hat"] if kind == "I" else model_p.decompress(strings, shape, x_cond)["x_hat"]
-        F.rgb_window_recondition(x_hat, (h, w))
-        got = F.state_hash_ints(F.state_hash(x_hat))[0]
-        checked += 1
-        if got != want[index]:
-            mismatches.append({"frame": index, "gop_start": starts[index], "want": want[index], "got": got})
-            dead = starts[index]
-        x_cond = x_hat
-    return {"frames": hdr.frames, "checked": checked, "mismatches": mismatches, "unchecked": unchecked}
+    -> video.verify_sequence's report (seqfile.VerifyReport).  ValueError for an un-hashed file."""
+    hdr, data, ranges, want, types, starts = seqfile.open_for_decoding(src, FileHeader, lambda hdr: check_header(hdr, model_i, model_p), need_hashes=True)
+    report = seqfile.VerifyReport(hdr, starts, want)
+    for index, _, _, got in _walk(model_i, model_p, hdr, data, ranges, decode_steps(types, 1), True, abandoned=report.abandoned):
+        report.check(index, got)
+    return report.result()
 
 
 # ---- the command line ----------------------------------------------------------------------------------------------------------
 def load_model_i(name, path, device):
     """stem_roi_i, or an I-frame model of the zoo, sized by and loaded from the checkpoint at `path`"""
     from . import video
-    if name == "stem_roi_i":
-        return _load_pixel(name, path, device)
-    return video.load_imodel(name, path, device)
+    return _load_pixel(name, path, device) if name == "stem_roi_i" else video.load_imodel(name, path, device)
 
 
 def _load_pixel(cls_name, path, device):
-    from . import models, video
-    sd = video._state_dict(path)
-    try:
-        net = getattr(models, cls_name)(sd["entropy_bottleneck.quantiles"].size(0), sd["EPM.4.weight"].size(0) // 2)
-        net.load_state_dict(sd)
-    except (KeyError, RuntimeError) as e:
-        raise ValueError(f"{path} is no checkpoint of {cls_name}: {e}") from e
-    return net.to(device).eval()
+    return seqfile.load_sized(cls_name, path, device, "entropy_bottleneck.quantiles", "EPM.4.weight")
 
 
 def load_model_p(cls_name, path, device):
@@ -487,31 +396,13 @@ def parse_roi_file(lines):
 def _parser():
     import argparse
     p = argparse.ArgumentParser(prog="python -m spatiotemporalentropymodel_amd.video_pixel", description="stand-alone pixel-domain sequence codec")
-    sub = p.add_subparsers(dest="command", required=True)
-    for name in ("encode", "decode", "verify"):
-        s = sub.add_parser(name)
-        s.add_argument("--model-i", required=True, help="stem_roi_i, or the zoo name of an I-frame model")
-        s.add_argument("--model-i-checkpoint", required=True)
-        s.add_argument("--model-p", default=None, help=f"one of {PIXEL_P_CLASSES} (not needed for an all-intra file)")
-        s.add_argument("--model-p-checkpoint", default=None)
-        s.add_argument("--input", required=True)
-        if name != "verify":
-            s.add_argument("--output", required=True)
-        s.add_argument("--device", default="cuda:0")
-    e, d = sub.choices["encode"], sub.choices["decode"]
-    e.add_argument("--width", type=int, required=True)
-    e.add_argument("--height", type=int, required=True)
-    e.add_argument("--bit-depth", type=int, default=8)
-    e.add_argument("--frames", type=int, default=None, help="code the first so many frames")
-    e.add_argument("--gop", type=int, default=12)
-    e.add_argument("--all-intra", action="store_true")
-    e.add_argument("--quality", type=int, default=4)
+    subs = seqfile.add_common_options(p.add_subparsers(dest="command", required=True), "model-i", "stem_roi_i, or the zoo name of an I-frame model",
+                                      "model-p", f"one of {PIXEL_P_CLASSES} (not needed for an all-intra file)")
+    seqfile.add_coding_options(subs["encode"], subs["decode"])
+    e = subs["encode"]
     e.add_argument("--level", type=float, default=None, help="the quality level outside every rectangle, in [0, 1]")
     e.add_argument("--roi", action="append", default=[], help="x0,y0,x1,y1,value[,feather]: a rectangle of every frame (repeatable)")
     e.add_argument("--roi-file", default=None, help="lines `frame x0 y0 x1 y1 value [feather]`; # starts a comment")
-    e.add_argument("--state-hash", action="store_true", help="write a hashed file: every frame's conditioning state, checked while decoding")
-    d.add_argument("--frames", default=None, help="START:STOP, decode only these frames")
-    d.add_argument("--no-verify", action="store_true", help="do not check a hashed file's state hashes")
     return p
 
 
@@ -527,41 +418,25 @@ def _cli_rois(args):
     return lambda index: every + per_frame.get(index, [])
 
 
+def _run(args):
+    if (args.model_p is None) != (args.model_p_checkpoint is None):
+        raise ValueError("--model-p and --model-p-checkpoint come together")
+    rois = _cli_rois(args) if args.command == "encode" else None
+    model_i = load_model_i(args.model_i, args.model_i_checkpoint, args.device)
+    model_p = load_model_p(args.model_p, args.model_p_checkpoint, args.device) if args.model_p else None
+    return seqfile.run_command(
+        args,
+        encode=lambda seq: encode_sequence(model_i, model_p, seq, args.output, rois=rois, level=args.level if args.level is not None else 0.0,
+                                           gop=args.gop, all_intra=args.all_intra, quality=args.quality, state_hash=args.state_hash),
+        decode=lambda rng: decode_sequence(model_i, model_p, args.input, write_to=args.output, frames=rng, return_frames=False,
+                                           verify=not args.no_verify),
+        verify=lambda: verify_sequence(model_i, model_p, args.input))
+
+
 def main(argv=None):
     """-> the exit status: 0; 2 after a refusal (ValueError), whose message goes to stderr; 3 when a state hash did not match (`verify`
     prints its report as JSON either way, `decode` stops at the first one)"""
-    args = _parser().parse_args(argv)
-    try:
-        if (args.model_p is None) != (args.model_p_checkpoint is None):
-            raise ValueError("--model-p and --model-p-checkpoint come together")
-        rois = _cli_rois(args) if args.command == "encode" else None
-        model_i = load_model_i(args.model_i, args.model_i_checkpoint, args.device)
-        model_p = load_model_p(args.model_p, args.model_p_checkpoint, args.device) if args.model_p else None
-        if args.command == "encode":
-            from . import data
-            seq = data.YUVSequence(args.input, args.width, args.height, args.bit_depth, frames=args.frames, device=args.device)
-            res = encode_sequence(model_i, model_p, seq, args.output, rois=rois, level=args.level if args.level is not None else 0.0, gop=args.gop,
-                                  all_intra=args.all_intra, quality=args.quality, state_hash=args.state_hash)
-            print(f"{len(res['frames'])} frames, {res['bytes']} bytes, {res['bpp_ave']:.6f} bpp")
-        elif args.command == "verify":
-            return print_report(verify_sequence(model_i, model_p, args.input))
-        else:
-            rng = None
-            if args.frames is not None:
-                try:
-                    rng = tuple(int(v) for v in args.frames.split(":"))
-                    assert len(rng) == 2
-                except (ValueError, AssertionError):
-                    raise ValueError(f"--frames is START:STOP, got {args.frames!r}") from None
-            decode_sequence(model_i, model_p, args.input, write_to=args.output, frames=rng, return_frames=False, verify=not args.no_verify)
-            print(f"decoded {args.input} into {args.output}")
-    except StateMismatch as e:
-        print(f"mismatch: {e}", file=sys.stderr)
-        return 3
-    except ValueError as e:
-        print(f"refused: {e}", file=sys.stderr)
-        return 2
-    return 0
+    return seqfile.exit_status(_run, _parser().parse_args(argv))
 
 
 if __name__ == "__main__":

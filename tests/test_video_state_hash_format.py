@@ -49,6 +49,38 @@ def test_the_flag_is_bit_7_of_the_version_byte_and_nothing_else(fmt):
     assert "state_hash" in repr(hashed) and "state_hash" not in repr(plain)
 
 
+def test_both_headers_are_the_one_container_header(fmt):
+    """one class states the struct; a format adds its magic and the names of its model fields.  The layout, written out: magic, version,
+    w, h, bit depth, frames, gop, all_intra, quality, then per model a kind byte, two u16 and the u32 fingerprint"""
+    from spatiotemporalentropymodel_amd import seqfile
+    mod, plain, hashed, _ = fmt
+    assert issubclass(mod.FileHeader, seqfile.FileHeader) and mod.FileHeader is not seqfile.FileHeader
+    assert video.FileHeader is not video_pixel.FileHeader and mod._HEADER is seqfile._HEADER
+    magic, i_kind, p_kind = (b"STMV", 2, 4) if mod is video else (b"STPX", 64, 2)
+    want = struct.pack(">4sB" "IIBIIBB" "BHHI" "BHHI", magic, 1, 104, 120, 8, N, GOP, 0, 4, i_kind, 8, 16, 0xDEADBEEF, p_kind, 8, 16, 0x01020304)
+    assert plain.pack() == want and hashed.pack() == want[:4] + b"\x81" + want[5:]
+    other = video_pixel if mod is video else video
+    with pytest.raises(ValueError, match="magic"):
+        other.FileHeader.unpack(want)                                                   # a format reads its own files only
+
+
+def test_a_broken_file_is_refused_before_the_models_are_looked_at(fmt):
+    """the order of checks, the same in both codecs: the file's own consistency (it costs nothing), then the models.  A file cut inside
+    its last record and a model of no known class: the truncation is what is reported"""
+    mod, plain, hashed, recs = fmt
+    no_model = object()
+    for hdr, tail in ((plain, b""), (hashed, video.trailer_bytes(HASHES))):
+        good = hdr.pack() + b"".join(recs) + tail
+        cut = hdr.pack() + b"".join(recs)[:-1]                                          # one byte short, trailer gone with it
+        for data in (cut, good[:mod.HEADER_BYTES + sum(len(r) for r in recs[:-1]) + 23]):
+            with pytest.raises(ValueError, match="truncated"):
+                mod.decode_sequence(no_model, no_model, data)
+        with pytest.raises(ValueError, match="truncated"):
+            mod.verify_sequence(no_model, no_model, cut)
+        with pytest.raises(ValueError, match="none of"):                               # an intact file: now the models are what is wrong
+            mod.decode_sequence(no_model, no_model, good)
+
+
 @pytest.mark.parametrize("byte", [2, 0x82, 0, 0x80, 3, 0x41])
 def test_other_versions_stay_refused(fmt, byte):
     mod, plain, _, _ = fmt
